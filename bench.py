@@ -9,10 +9,14 @@ MI355X": strong scaling -- the hypothesis axis is cut into contiguous shards, ra
     [N > 1: all-reduce(MAX) of the packed int64 keys over RCCL -- the keys of 8 steps per collective, in stream order]
     decode the keys, gather R_pred = proposals[idx], hand the keys back empty   ONE launch per 8 steps (test_co3d.py:145-146)
 Inputs are resident in HBM before the timed region.  `value` = 50 000 x steps / time: the whole job's hypotheses per
-second ("scaling": "strong").  The same run also times, as named secondary records: the per-step-collective cadence
-(one all-reduce + select per step), weak scaling (50 000 hypotheses PER RANK), BASELINE.json configs[3] (B = 32 x 50 000
-split over the ranks), a two-stream variant of the step loop (independent pairs overlap one step's drain with the next one's
-ramp) and, at one rank, the shard timings that say what an N-GPU run can reach (`predicted_strong_scaling`).
+second ("scaling": "strong").
+
+A plain run sets up, pre-warms, runs `--warmup` untimed steps, times exactly `--steps` steps and prints the headline line;
+`--dump-outputs DIR` then also writes what the last timed step handed its caller (best score, global index and R_pred per
+pair) as DIR/<name>.npy.  With `--full` the same run also times, as named secondary records: the per-step-collective
+cadence (one all-reduce + select per step), weak scaling (50 000 hypotheses PER RANK), BASELINE.json configs[3] (B = 32 x
+50 000 split over the ranks), a two-stream variant of the step loop (independent pairs overlap one step's drain with the
+next one's ramp) and, at one rank, the shard timings that say what an N-GPU run can reach (`predicted_strong_scaling`).
 
 Launching: `python3 bench.py --gpus N` starts its own N worker processes (one per GPU, RANK / LOCAL_RANK /
 WORLD_SIZE / MASTER_* set, rendezvous on 127.0.0.1) BEFORE anything touches a GPU and relays rank 0's JSON
@@ -20,8 +24,9 @@ line; under an external launcher (`python -m torch.distributed.run --nproc-per-n
 which sets RANK / WORLD_SIZE) the process is a worker itself.  `--backend gloo` lets more ranks than GPUs
 share the visible device(s): a rehearsal of the multi-rank logic on a 1-GPU box, never a measurement.
 
-Prints ONE JSON line on rank 0 (see the task contract), with `roofline` for the fused kernel
-(fp32 MFMA bound) and `cpu_baseline` (the reference's torch-CPU op sequence on the host cores).
+Prints ONE JSON line on rank 0 (see the task contract); with `--full` it also carries `roofline` for the fused kernel
+(fp32 MFMA bound), the checks of the timed result against the materialised scores, the split-f16 side report and
+`cpu_baseline` (the reference's torch-CPU op sequence on the host cores).
 """
 import argparse
 import importlib
@@ -51,19 +56,29 @@ def parse_args():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=20)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beside the headline: in-kernel clock stamps and event "
+                         "brackets in the timed region (roofline), the timed result against the materialised scores, "
+                         "the secondary records, the split-f16 side report and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one handed its caller (best_score, best_idx, "
+                         "R_pred) as DIR/<name>.npy, float32 / float64")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave out the CPU baseline")
     ap.add_argument("--split-f16", action="store_true",
                     help="time the opt-in split-f16 kernel (AHV_SCORE_SPLIT_F16) instead of the all-fp32 default; "
-                         "by default it is only reported beside the fp32 headline")
+                         "by default it is only reported beside the fp32 headline (with --full)")
     ap.add_argument("--prewarm-ms", type=float, default=60.0,
                     help="minimum length of the untimed, time-based pre-warm (the same step, looped until the chip's "
                          "clock has settled: >= this many ms AND three consecutive kernel times within 1 %%; 0 disables)")
     ap.add_argument("--skip-secondary", "--skip-strong-scaling", dest="skip_secondary", action="store_true",
-                    help="leave out the secondary records (profiling runs: they launch the same kernel at other shapes, "
-                         "which would mix into rocprofv3's per-kernel averages)")
+                    help="with --full: leave out the secondary records (profiling runs: they launch the same kernel at "
+                         "other shapes, which would mix into rocprofv3's per-kernel averages)")
     ap.add_argument("--backend", default="nccl", help="process-group backend (nccl = RCCL; gloo only to rehearse "
                                                       "the multi-rank logic on a box with fewer GPUs than ranks)")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
 
 
 # ------------------------------------------------------------------------------------------------ parent
@@ -229,6 +244,23 @@ def kernel_source_sha() -> str:
         with open(os.path.join(REPO, "3dahv_amd", "csrc", name), "rb") as f:
             h.update(f.read())
     return h.hexdigest()
+
+
+def dump_outputs(path, out, dist, use_pg, rank):
+    """--dump-outputs: what the last timed step handed its caller, one DIR/<name>.npy per array -- best_score (B,) float32,
+    best_idx (B,) float64 (the global index; exact below 2**53), R_pred (B, 3, 3) float32.  Under a process group every rank
+    takes part (only the rank whose shard holds the winner has its R_pred row, the others zeros: their sum is that row);
+    rank 0 writes."""
+    import numpy as np
+    R_pred = out["R_pred"].clone()
+    if use_pg:
+        dist.all_reduce(R_pred, op=dist.ReduceOp.SUM)
+    if rank != 0:
+        return
+    os.makedirs(path, exist_ok=True)
+    arrays = {"best_score": out["best"].float(), "best_idx": out["idx"].double(), "R_pred": R_pred.float()}
+    for name, t in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), t.cpu().numpy())
 
 
 class VerifyLoop:
@@ -516,6 +548,37 @@ def worker(args):
             cand = cand[pick, torch.arange(cand.shape[1], device=cand.device)]
         return cand
 
+    def headline(dt, pre, out):
+        """The fields of every result line: what a plain run prints; --full adds its records to them."""
+        return {
+            "metric": "rotation hypotheses scored/sec (B=1)", "value": N_HYP * args.steps / dt, "unit": "hypotheses/s",
+            "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": dt / args.steps * 1e3,
+            "higher_is_better": True, "scaling": "strong", "vs_baseline": None,
+            "dtype": "f16 hi/lo split products, f32 accumulate" if split else "f32",
+            "data": "synthetic",
+            **pre,
+            "config": {"workload": "CO3D pair (BASELINE.json configs[1]): B=1, ONE set of N_hyp=50000 Haar rotations split "
+                                   "over the GPUs (contiguous shards, n_offset), source volume 16x8x8x8 (P=512 voxel sites x "
+                                   "16 ch), head 384->32->32, 64 positions",
+                       "n_hyp_per_gpu": n_local, "n_hyp_total": N_HYP,
+                       "parallelism": "hypothesis axis sharded x%d, 8-byte key all-reduce(max)" % world,
+                       "backend": "single process" if not use_pg else ("rccl" if args.backend == "nccl" else args.backend),
+                       "step": "ONE fused launch (forward_3d2d(tgt) + rotate + forward_3d2d + score + arg-max: "
+                               "ahv_verify_pair_f32)%s + ONE select launch per %d step(s) (decode + gather R_pred + key reset)" % (
+                                   " + ONE all-reduce(MAX) of the int64 keys of %d steps, in stream order" % loop.group
+                                   if use_pg else "", loop.group),
+                       "steps_per_collective": loop.group if use_pg else None, "steps_per_select": loop.group,
+                       "lanes": lanes,
+                       "lanes_note": None if lanes == 1 else "groups of %d steps alternate between %d streams, each with its own "
+                                     "key buffer and its own communicator: independent pairs overlap one step's drain with the "
+                                     "next step's hypotheses (AHV_BENCH_LANES=1 for the one-stream loop; with --full, secondary."
+                                     "n50k_b1_one_stream times it in this run)" % (loop.group, lanes),
+                       "ranks": ranks_info},
+            # what the timed region computed (with --full asserted against torch.max over the materialised scores of
+            # all ranks): lets a forced-process-group run be compared with a single-process run
+            "result": {"best_idx": int(out["idx"].item()), "best_score": float(out["best"].item())},
+        }
+
     # The cyclic garbage collector stays off from here to the end of the measurements: a generation-2 collection inside an
     # issue loop is a multi-millisecond host stall (the queue runs dry), and one BETWEEN the pre-warm and the timed steps
     # idles the GPU long enough to drop its clock (seen: the first 16 timed launches at 0.82 ... 0.70 ms).
@@ -524,6 +587,19 @@ def worker(args):
     gc.disable()
     with torch.no_grad():
         pre = prewarm(args.prewarm_ms)
+        if not args.full:
+            # a plain run: the step loop alone between the barriers -- no event brackets, no in-kernel clock stamps, nothing
+            # measured or checked after it
+            dt = timed(loop, args.steps, args.warmup)
+            gc.enable()
+            out = dict(loop.out)
+            if args.dump_outputs:
+                dump_outputs(args.dump_outputs, out, dist, use_pg, rank)
+            if rank == 0:
+                os.write(json_fd, (json.dumps(headline(dt, pre, out)) + "\n").encode())
+            if use_pg:
+                dist.destroy_process_group()
+            return
         stamps = torch.zeros(args.steps, 4 * ncu, dtype=torch.int64, device=dev)
         if lanes == 1:
             # fused kernel, HIP events on its stream, inside the timed region
@@ -543,6 +619,8 @@ def worker(args):
             kern_src = "one-lane calibration leg (%d steps, same shard, same collectives, %.4f ms per step) in front of the " \
                        "two-lane timed region: HIP events per group of %d launches" % (cal_steps, cal_dt / cal_steps * 1e3, cal.group)
         out = dict(loop.out)
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, out, dist, use_pg, rank)
         kern_pairs = bracket_ms(brackets)
         kern_list = [ms for ms, _ in kern_pairs]
         kern_ms = float(sum(ms * n for ms, n in kern_pairs) / sum(n for _, n in kern_pairs))
@@ -677,37 +755,13 @@ def worker(args):
                                "kernel_src_sha": sha, "formula": tj.get("formula"),
                                "note": "rocprofv3 --pmc passes of the same command; not measured in this run"}
         kname = "score_hypotheses_dual_kernel<false, true>"
-        res = {
-            "metric": "rotation hypotheses scored/sec (B=1)", "value": value, "unit": "hypotheses/s",
-            "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": dt / args.steps * 1e3,
-            "higher_is_better": True, "scaling": "strong", "vs_baseline": None, "dtype": "f32",
-            "data": "synthetic",
+        res = headline(dt, pre, out)
+        res.update({
             # the reference's literal cadence (test_co3d.py:145-146: torch.max + proposals[idx] after EVERY pair; with ranks,
             # one all-reduce per step too), timed in the same run on one stream; `value` amortises the select (and the
             # collective) over `steps_per_select` independent pairs -- the same cadence at every N
             "ms_per_step_select_every_step": None if per_step is None else per_step["ms_per_step"],
             "value_select_every_step": None if per_step is None else per_step["hypotheses_per_s"],
-            **pre,
-            "config": {"workload": "CO3D pair (BASELINE.json configs[1]): B=1, ONE set of N_hyp=50000 Haar rotations split "
-                                   "over the GPUs (contiguous shards, n_offset), source volume 16x8x8x8 (P=512 voxel sites x "
-                                   "16 ch), head 384->32->32, 64 positions",
-                       "n_hyp_per_gpu": n_local, "n_hyp_total": N_HYP,
-                       "parallelism": "hypothesis axis sharded x%d, 8-byte key all-reduce(max)" % world,
-                       "backend": "single process" if not use_pg else ("rccl" if args.backend == "nccl" else args.backend),
-                       "step": "ONE fused launch (forward_3d2d(tgt) + rotate + forward_3d2d + score + arg-max: "
-                               "ahv_verify_pair_f32)%s + ONE select launch per %d step(s) (decode + gather R_pred + key reset)" % (
-                                   " + ONE all-reduce(MAX) of the int64 keys of %d steps, in stream order" % loop.group
-                                   if use_pg else "", loop.group),
-                       "steps_per_collective": loop.group if use_pg else None, "steps_per_select": loop.group,
-                       "lanes": lanes,
-                       "lanes_note": None if lanes == 1 else "groups of %d steps alternate between %d streams, each with its own "
-                                     "key buffer and its own communicator: independent pairs overlap one step's drain with the "
-                                     "next step's hypotheses (AHV_BENCH_LANES=1 for the one-stream loop; secondary."
-                                     "n50k_b1_one_stream times it in this run)" % (loop.group, lanes),
-                       "ranks": ranks_info},
-            # what the timed region computed (asserted above against torch.max over the materialised scores of
-            # all ranks): lets a forced-process-group run be compared with a single-process run
-            "result": {"best_idx": int(out["idx"].item()), "best_score": float(out["best"].item())},
             "roofline": {"bound": "mfma", "achieved": achieved, "peak": PEAK_F32_MFMA_TFLOPS, "unit": "TFLOP/s",
                          "frac": achieved / PEAK_F32_MFMA_TFLOPS, "traffic": traffic, "traffic_source": traffic_src,
                          "kernel": kname, "kernel_ms": kern_ms,
@@ -731,9 +785,8 @@ def worker(args):
                          "frac_at_delivered_clock": (achieved / (PEAK_F32_MFMA_TFLOPS * clock_ghz / MAX_CLOCK_GHZ)
                                                      if clock_ghz else None)},
             "secondary": secondary,
-        }
+        })
         if split:  # opt-in kernel: priced against the f16 matrix peak (16 x the fp32 one)
-            res["dtype"] = "f16 hi/lo split products, f32 accumulate"
             res["roofline"].update(kernel="forward_3d2d_small_kernel + score_hypotheses_dual_kernel<true, false>",
                                    peak=16 * PEAK_F32_MFMA_TFLOPS,
                                    frac=achieved / (16 * PEAK_F32_MFMA_TFLOPS), frac_at_delivered_clock=None,

@@ -13,7 +13,7 @@ pytestmark = pytest.mark.gpu
 
 def test_bench_json_line():
     out = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--steps", "5", "--warmup", "2",
-                          "--no-cpu-baseline"], capture_output=True, text=True, timeout=600, cwd=REPO)
+                          "--full", "--no-cpu-baseline"], capture_output=True, text=True, timeout=600, cwd=REPO)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1
@@ -97,7 +97,8 @@ def test_bench_rccl_branch_on_one_gpu():
     collective of the world > 1 path -- the async key all-reduce ring, the barriers, the all-reduce of the time,
     the all-gather check -- so the first multi-GPU run is not the first run of that code.  Same arg-max and score
     as the single-process run."""
-    base = [sys.executable, os.path.join(REPO, "bench.py"), "--steps", "200", "--warmup", "20", "--no-cpu-baseline"]
+    base = [sys.executable, os.path.join(REPO, "bench.py"), "--steps", "200", "--warmup", "20", "--full",
+            "--no-cpu-baseline"]
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT")}
 
     def run(extra):
@@ -150,7 +151,7 @@ def test_bench_launches_its_own_ranks():
     # that the path with two communicators per rank is the one that runs)
     env["AHV_BENCH_TWO_LANES_MAX_N"] = "25000"
     out = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "2", "--backend", "gloo",
-                          "--steps", "4", "--warmup", "1", "--no-cpu-baseline"], capture_output=True, text=True,
+                          "--steps", "4", "--warmup", "1", "--full", "--no-cpu-baseline"], capture_output=True, text=True,
                          timeout=900, cwd=REPO, env=env)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
@@ -178,3 +179,50 @@ def test_bench_launches_its_own_ranks():
                           "--steps", "1", "--warmup", "0", "--no-cpu-baseline"], capture_output=True, text=True,
                          timeout=600, cwd=REPO, env=env)
     assert bad.returncode != 0 and "only 1 GPU(s) visible" in bad.stderr
+
+
+def test_plain_run_times_the_headline_alone_and_dumps_its_outputs(ahv, tmp_path):
+    """A plain run (no --full): exactly --steps timed steps, the headline fields and nothing measured beside them.
+    --dump-outputs writes what the last timed step handed its caller: the same arrays from every run with the same
+    arguments, and the same from two ranks that share the hypothesis set (gloo rehearsal on one GPU)."""
+    import numpy as np
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT")}
+    names = ("best_score", "best_idx", "R_pred")
+
+    def run(tag, *extra):
+        d = tmp_path / tag
+        out = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--steps", "13", "--warmup", "3",
+                              "--dump-outputs", str(d), *extra], capture_output=True, text=True, timeout=600, cwd=REPO,
+                             env=env)
+        assert out.returncode == 0, out.stderr[-3000:]
+        line = out.stdout.strip()
+        assert line.startswith("{") and "\n" not in line                      # stdout = the one JSON line
+        assert sorted(p.name for p in d.iterdir()) == sorted(n + ".npy" for n in names)
+        assert sum(p.stat().st_size for p in d.iterdir()) <= 64 << 20
+        return json.loads(line), {n: np.load(d / (n + ".npy")) for n in names}
+
+    a, da = run("a", "--gpus", "1")
+    assert a["n_gpus"] == 1 and a["steps"] == 13 and a["warmup"] == 3
+    assert a["metric"] == "rotation hypotheses scored/sec (B=1)" and a["unit"] == "hypotheses/s"
+    assert a["higher_is_better"] is True and a["dtype"] == "f32" and a["scaling"] == "strong"
+    assert abs(a["value"] - 50000 / (a["ms_per_step"] * 1e-3)) / a["value"] < 1e-6
+    assert a["config"]["n_hyp_total"] == 50000 and a["config"]["backend"] == "single process"
+    for k in ("roofline", "secondary", "cpu_baseline", "split_f16_kernel", "ms_per_step_select_every_step"):
+        assert k not in a, k
+    # the dumped arrays: what the line's `result` says, and R_pred = the winning hypothesis itself
+    assert da["best_score"].dtype == np.float32 and da["best_score"].shape == (1,)
+    assert da["best_idx"].dtype == np.float64 and da["best_idx"].shape == (1,)
+    assert da["R_pred"].dtype == np.float32 and da["R_pred"].shape == (1, 3, 3)
+    idx = a["result"]["best_idx"]
+    assert int(da["best_idx"][0]) == idx and float(da["best_score"][0]) == a["result"]["best_score"]
+    assert np.array_equal(da["R_pred"][0], ahv.rotations.haar_rotations_np(50000, seed=1000)[idx])
+    # same arguments: same inputs, same outputs
+    b, db = run("b", "--gpus", "1")
+    assert b["result"] == a["result"]
+    for n in names:
+        assert np.array_equal(db[n], da[n]), n
+    # two ranks, each scoring its shard of the same set: the same arrays (R_pred from the rank that owns the winner)
+    c, dc = run("c", "--gpus", "2", "--backend", "gloo")
+    assert c["n_gpus"] == 2 and c["config"]["n_hyp_per_gpu"] == 25000 and "secondary" not in c
+    for n in names:
+        assert np.array_equal(dc[n], da[n]), n

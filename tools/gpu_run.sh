@@ -50,10 +50,10 @@ tests)
     timeout -k 10 1000 python -m pytest tests -x -q -m gpu > $O/pytest.log 2>&1; echo "pytest rc=$?" | tee -a $O/pytest.log; tail -6 $O/pytest.log
     ;;
 bench)
-    timeout -k 10 600 python3 bench.py --gpus 1 --steps 20 --warmup 5 > $O/bench_20_5.json 2> $O/bench_20_5.err; echo "20/5 rc=$?"
-    timeout -k 10 600 python3 bench.py --gpus 1 --steps 200 --warmup 20 --no-cpu-baseline > $O/bench_200_20.json 2> $O/bench_200_20.err; echo "200/20 rc=$?"
-    AHV_BENCH_FORCE_PG=1 timeout -k 10 600 python3 bench.py --gpus 1 --steps 100 --warmup 10 --no-cpu-baseline > $O/bench_forced_pg.json 2> $O/bench_forced_pg.err; echo "forced pg rc=$?"
-    timeout -k 10 600 python3 bench.py --gpus 2 --backend gloo --steps 100 --warmup 10 --no-cpu-baseline > $O/bench_2rank_gloo.json 2> $O/bench_2rank_gloo.err; echo "2-rank gloo rc=$?"
+    timeout -k 10 600 python3 bench.py --gpus 1 --steps 20 --warmup 5 --full > $O/bench_20_5.json 2> $O/bench_20_5.err; echo "20/5 rc=$?"
+    timeout -k 10 600 python3 bench.py --gpus 1 --steps 200 --warmup 20 --full --no-cpu-baseline > $O/bench_200_20.json 2> $O/bench_200_20.err; echo "200/20 rc=$?"
+    AHV_BENCH_FORCE_PG=1 timeout -k 10 600 python3 bench.py --gpus 1 --steps 100 --warmup 10 --full --no-cpu-baseline > $O/bench_forced_pg.json 2> $O/bench_forced_pg.err; echo "forced pg rc=$?"
+    timeout -k 10 600 python3 bench.py --gpus 2 --backend gloo --steps 100 --warmup 10 --full --no-cpu-baseline > $O/bench_2rank_gloo.json 2> $O/bench_2rank_gloo.err; echo "2-rank gloo rc=$?"
     tail -c 1500 $O/bench_20_5.json
     ;;
 oplevel)
