@@ -4,42 +4,36 @@
 //
 //   scores[b][n] = 1/64 sum_pos <normalize(W2 relu(W1 slabs(rot(V_b, R_n))) + b2)[:, pos], tg_b[:, pos]>
 //
-// Three launches, nothing of the 32 KiB-per-hypothesis rotated volumes or 96 KiB slab tensors ever reaches HBM:
+// Four launches, nothing of the 32 KiB-per-hypothesis rotated volumes or 96 KiB slab tensors ever reaches HBM:
 //   1.  score_backward_head_kernel   recomputes the forward of each hypothesis (same code as the forward
 //       kernel), back-propagates through the score, the normalisation, GEMM2 and the ReLU and leaves
 //       du = dL/du (32 x 64 floats per hypothesis) in the caller's workspace; accumulates d feat_tgt, d W2, d b2.
-//   2a. score_backward_w1_kernel     re-gathers each quarter of the rotated volume, dW1 += du X^T in registers.
-//   2b. score_backward_volume_kernel forms dX = W1^T du and scatters it through the trilinear weights into a
-//       per-workgroup LDS image of dV that is flushed once per sample.
+//       (score_backward_head_saved_kernel instead takes u from the workspace, where the training forward left it.)
+//   2a. score_backward_w1_kernel     re-gathers each quarter of the rotated volume, dW1 += du X^T in registers;
+//       score_backward_w1_reduce_kernel sums the workgroups' partials.
+//   2b. score_backward_volume_rmw_kernel forms dX = W1^T du and scatters it through the trilinear weights into
+//       private fp32 LDS images of dV (plain read-modify-writes), flushed once per sample.
 // All contractions are fp32 MFMA 16x16x4 (one float per lane and operand, so any LDS layout can feed them).
 // Accumulation across waves/workgroups uses float atomics: gradients are reproducible to rounding, not bitwise.
 // Accumulation targets are zeroed by launch_zero_fill (ahv_ops.hip), never by hipMemsetAsync (not graph-safe here).
+// The LDS-atomic dV kernel of rounds 2-5 that 2b replaced is described in HISTORY.md (code: commit 86a1f1c).
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
 
 #include "ahv_device.h"
-#ifndef AHV_DIAG_NO_FP32_LOW_HALF  // (tools/kbench_bwd A/B build of the unprotected kernels)
 #define AHV_FP32_LOW_HALF  // these kernels leave registers free on their SIMDs: see low_half (ahv_dual.h)
-#endif
 #include "ahv_dual.h"
 
 namespace ahv {
 
 constexpr int kBwdThreads = 256;  // 4 waves, one per SIMD: 512 registers per wave
 
-// max |du| per sample is what the LDS-atomic dV kernel of rounds 2-5 sizes its fixed-point scale with.  The shipped dV kernel
-// (read-modify-write in fp32, round 6) does not need it, so the head kernels only compute it for the builds that launch the
-// atomic kernel (-DAHV_BWD_VOLUME_ATOMICS, tools/kbench_bwd): ~30 vector instructions per position tile otherwise spent for nothing.
-#if defined(AHV_BWD_VOLUME_ATOMICS) && !defined(AHV_BWD_DU_AMAX)
-#define AHV_BWD_DU_AMAX 1
-#endif
-
 // u / du of one hypothesis in the workspace (2 048 floats): the MFMA accumulator layout of the scorer, tile by tile --
 //   word(o, pos) = ((pos >> 4) * 2 + (o >> 4)) * 256 + (((o >> 2) & 3) * 16 + (pos & 15)) * 4 + (o & 3)
 // i.e. [t][m][lane = 16 kq + n][r] for o = 16 m + 4 kq + r, pos = 16 t + n.  A wave writes and reads a (t, m) fragment with
 // one 16-byte access per lane, the training forward's u and the head kernel's du share the words (du overwrites u tile
-// by tile), and a lane that wants du[4 sp + kq][16 t + n] (kernels 2b) finds the 64 lanes' words in one 256-byte run.
+// by tile), and a lane that wants du[4 sp + kq][16 t + n] (kernel 2b) finds the 64 lanes' words in one 256-byte run.
 __device__ __forceinline__ int du_word(int o, int pos)
 {
     return ((pos >> 4) * 2 + (o >> 4)) * 256 + (((o >> 2) & 3) * 16 + (pos & 15)) * 4 + (o & 3);
@@ -48,42 +42,6 @@ __device__ __forceinline__ int du_word(int o, int pos)
 // du image in LDS: du[o][pos] at o*64 + (pos ^ ((o & 7) << 2)).  The XOR keeps aligned groups of four
 // positions together (float4 fills) and spreads rows over banks for the transposed reads (k = pos).
 __device__ __forceinline__ int dimg(int o, int pos) { return o * 64 + (pos ^ ((o & 7) << 2)); }
-
-__device__ __forceinline__ void lds_add_i64(long long* p, long long v)
-{
-#ifdef AHV_DIAG_NO_ATOMICS  // diagnostic build of tools/kbench_bwd only (wrong results): price of the LDS atomics
-    asm volatile("" ::"v"(p), "v"(v));
-#else
-    __hip_atomic_fetch_add(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-#endif
-}
-
-// |x| < 2^40 -> nearest integer as int64 (there is no f32 -> i64 convert): add 1.5 * 2^52 in fp64, where one ulp
-// is exactly 1, and read the integer out of the mantissa.
-__device__ __forceinline__ long long to_fixed(float x)
-{
-    const double magic = 6755399441055744.0;  // 2^52 + 2^51
-    return __double_as_longlong((double)x + magic) - __double_as_longlong(magic);
-}
-
-// Corner weights and DENSE channel-last row offsets (16 words per voxel, voxel = z*64 + y*8 + x).
-__device__ __forceinline__ void tri_coef_dense(float (&w)[8], int (&a)[8], const float* Rm, float x, float y, float z)
-{
-    const float gx = Rm[0] * x + Rm[1] * y + Rm[2] * z;
-    const float gy = Rm[3] * x + Rm[4] * y + Rm[5] * z;
-    const float gz = Rm[6] * x + Rm[7] * y + Rm[8] * z;
-    float wx0, wx1, wy0, wy1, wz0, wz1;
-    int ox0, ox1, oy0, oy1, oz0, oz1;
-    axis_coef(gx, wx0, wx1, ox0, ox1, 16);
-    axis_coef(gy, wy0, wy1, oy0, oy1, 8 * 16);
-    axis_coef(gz, wz0, wz1, oz0, oz1, 64 * 16);
-    const float w00 = wz0 * wy0, w01 = wz0 * wy1, w10 = wz1 * wy0, w11 = wz1 * wy1;
-    w[0] = w00 * wx0; w[1] = w00 * wx1; w[2] = w01 * wx0; w[3] = w01 * wx1;
-    w[4] = w10 * wx0; w[5] = w10 * wx1; w[6] = w11 * wx0; w[7] = w11 * wx1;
-    const int a00 = oz0 + oy0, a01 = oz0 + oy1, a10 = oz1 + oy0, a11 = oz1 + oy1;
-    a[0] = a00 + ox0; a[1] = a00 + ox1; a[2] = a01 + ox0; a[3] = a01 + ox1;
-    a[4] = a10 + ox0; a[5] = a10 + ox1; a[6] = a11 + ox0; a[7] = a11 + ox1;
-}
 
 __device__ __forceinline__ void global_add(float* p, float v)
 {
@@ -97,7 +55,7 @@ __global__ __launch_bounds__(kBwdThreads, 1) void score_backward_head_kernel(
     const float* __restrict__ vol_src, const float* __restrict__ feat_tgt, const float* __restrict__ R,
     long r_batch_stride, const float* __restrict__ W1, const float* __restrict__ W2, const float* __restrict__ b2,
     int B, long N, const float* __restrict__ grad_scores, float* __restrict__ du_ws,
-    unsigned* __restrict__ du_max_bits, float* __restrict__ grad_feat_tgt, float* __restrict__ grad_W2, float* __restrict__ grad_b2)
+    float* __restrict__ grad_feat_tgt, float* __restrict__ grad_W2, float* __restrict__ grad_b2)
 {
     __shared__ __attribute__((aligned(1024))) float lds_src[kSrcFloats];  // at LDS address 0: see ahv_score.hip
     __shared__ __attribute__((aligned(16))) float lds_w1[kW1TableFloats];
@@ -150,7 +108,6 @@ __global__ __launch_bounds__(kBwdThreads, 1) void score_backward_head_kernel(
                     }
         }
         const float* Rb = R + (long)b * r_batch_stride;
-        float du_amax = 0.0f;
         for (long h = (long)wave * gridDim.x + xcd_residue(blockIdx.x, gridDim.x, gridDim.y); h < N; h += hstep) {
             float Rm[9];
 #pragma unroll
@@ -232,14 +189,7 @@ __global__ __launch_bounds__(kBwdThreads, 1) void score_backward_head_kernel(
 #pragma unroll
                 for (int t = 0; t < 4; ++t)
 #pragma unroll
-                    for (int r = 0; r < 4; ++r) {
-                        const float x = acc[m][t][r] > 0.0f ? du[m][t][r] : 0.0f;
-                        dst[((t * 2 + m) * 64 + lane) * 4 + r] = x;
-                        // max |du| of the sample (kernel 2b sizes its fixed-point scale with it); NaN / inf poison it
-#ifdef AHV_BWD_DU_AMAX
-                        du_amax = (x == x) ? fmaxf(du_amax, fabsf(x)) : __builtin_inff();
-#endif
-                    }
+                    for (int r = 0; r < 4; ++r) dst[((t * 2 + m) * 64 + lane) * 4 + r] = acc[m][t][r] > 0.0f ? du[m][t][r] : 0.0f;
 
             // dW2 += dv relu(u)^T: the contraction runs over positions, so both operands go through the
             // wave's LDS image once (dv as A, relu(u) as B).
@@ -273,13 +223,6 @@ __global__ __launch_bounds__(kBwdThreads, 1) void score_backward_head_kernel(
                 }
             wave_lds_fence();
         }
-#ifdef AHV_BWD_DU_AMAX
-#pragma unroll
-        for (int sft = 32; sft >= 1; sft >>= 1) du_amax = fmaxf(du_amax, __shfl_xor(du_amax, sft, 64));
-        if (lane == 0) atomicMax(du_max_bits + b, __float_as_uint(du_amax));  // non-negative floats order like uints
-#else
-        (void)du_amax; (void)du_max_bits;
-#endif
         float* gft = grad_feat_tgt + (long)b * (32 * 64);
 #pragma unroll
         for (int t = 0; t < 4; ++t)
@@ -321,7 +264,7 @@ constexpr int kSavedThreads = 512;
 __global__ __launch_bounds__(kSavedThreads, 2) void score_backward_head_saved_kernel(
     const float* __restrict__ feat_tgt, const float* __restrict__ W2, const float* __restrict__ b2,
     int B, long N, const float* __restrict__ grad_scores, float* __restrict__ du_ws,
-    unsigned* __restrict__ du_max_bits, float* __restrict__ grad_feat_tgt, float* __restrict__ grad_W2, float* __restrict__ grad_b2)
+    float* __restrict__ grad_feat_tgt, float* __restrict__ grad_W2, float* __restrict__ grad_b2)
 {
     __shared__ __attribute__((aligned(16))) float lds_tg[4 * 2 * 64 * 4];        // target fragments [t][m2][lane][r]
     __shared__ __attribute__((aligned(16))) float lds_dtg[8 * 4 * 2 * 64 * 4];   // per wave: d feat_tgt, same layout
@@ -367,7 +310,6 @@ __global__ __launch_bounds__(kSavedThreads, 2) void score_backward_head_saved_ke
             for (int i = 0; i < 8; ++i) *reinterpret_cast<f32x4*>(dtg + i * 256) = f32x4{0.f, 0.f, 0.f, 0.f};
         }
         __syncthreads();
-        float du_amax = 0.0f;
         long h = (long)wave * gridDim.x + xcd_residue(blockIdx.x, gridDim.x, gridDim.y);
         // u of (hypothesis, tile): two 16-byte loads per lane, requested a tile ahead (the last tile requests the next
         // hypothesis' first).  du overwrites u tile by tile, word for word (du_word): a tile's loads are consumed before its
@@ -455,11 +397,6 @@ __global__ __launch_bounds__(kSavedThreads, 2) void score_backward_head_saved_ke
                     // (u != u: the forward's exact path saved NaN for a sample with a non-finite voxel or weight)
                     x0[r] = a0[r] > 0.0f ? du0[r] : (a0[r] == a0[r] ? 0.0f : a0[r]);
                     x1[r] = a1[r] > 0.0f ? du1[r] : (a1[r] == a1[r] ? 0.0f : a1[r]);
-                    // max |du| of the sample (kernel 2b's LDS-atomic form sizes its fixed-point scale with it); NaN / inf poison it
-#ifdef AHV_BWD_DU_AMAX
-                    du_amax = (x0[r] == x0[r]) ? fmaxf(du_amax, fabsf(x0[r])) : __builtin_inff();
-                    du_amax = (x1[r] == x1[r]) ? fmaxf(du_amax, fabsf(x1[r])) : __builtin_inff();
-#endif
                 }
                 *reinterpret_cast<f32x4*>(dst + t * 512 + lane * 4) = x0;        // du over the tile's u, same words
                 *reinterpret_cast<f32x4*>(dst + t * 512 + 256 + lane * 4) = x1;
@@ -484,13 +421,6 @@ __global__ __launch_bounds__(kSavedThreads, 2) void score_backward_head_saved_ke
                 wave_lds_fence();
             }
         }
-#ifdef AHV_BWD_DU_AMAX
-#pragma unroll
-        for (int sft = 32; sft >= 1; sft >>= 1) du_amax = fmaxf(du_amax, __shfl_xor(du_amax, sft, 64));
-        if (lane == 0) atomicMax(du_max_bits + b, __float_as_uint(du_amax));  // non-negative floats order like uints
-#else
-        (void)du_amax; (void)du_max_bits;
-#endif
         float* gft = grad_feat_tgt + (long)b * (32 * 64);
 #pragma unroll
         for (int t = 0; t < 4; ++t)
@@ -520,12 +450,12 @@ __global__ __launch_bounds__(kSavedThreads, 2) void score_backward_head_saved_ke
 
 // ---------------------------------------------------------------------------------------------------
 // Kernels 2a / 2b.  Both walk the hypotheses again with du from the workspace.  They are separate launches
-// because each carries persistent state per wave (2a: the dW1 accumulators, 2b: the W1^T fragments; 96 registers
-// each since the outputs are split over the two waves of a SIMD) next to a gather / scatter that wants ~100 more:
-// together they spill, apart they do not.
-//   2a  score_backward_w1_kernel      re-gathers each quarter X of the rotated volume, dW1 += du X^T
-//   2b  score_backward_volume_kernel  dX = W1^T du per quarter, dV += trilinear^T dX in an LDS image of the
-//                                     sample's volume gradient, flushed once per sample
+// because each carries persistent state next to a gather / scatter that wants ~100 registers more (2a: the dW1
+// accumulators, 96 registers per wave since the output is split over the two waves of a SIMD; 2b: the W1^T fragments
+// and the private dV images, which fill the LDS).
+//   2a  score_backward_w1_kernel          re-gathers each quarter X of the rotated volume, dW1 += du X^T
+//   2b  score_backward_volume_rmw_kernel  dX = W1^T du per half volume, dV += trilinear^T dX in private LDS images
+//                                         of the sample's volume gradient, flushed once per sample
 // ---------------------------------------------------------------------------------------------------
 
 // LDS images of 2a, both LINEAR with a small pad so that every access is "per-lane base + compile-time constant"
@@ -536,7 +466,6 @@ __global__ __launch_bounds__(kSavedThreads, 2) void score_backward_head_saved_ke
 constexpr int kXwStride = 129;
 constexpr int kXwFloats = 16 * kXwStride;
 constexpr int kDuStride = 68;
-constexpr int kDuFloats = 32 * kDuStride;
 
 // Kernel 2a runs TWO waves per SIMD.  The 192 accumulator registers of dW1 are what kept it at one wave per
 // SIMD, where every LDS round trip and every VALU burst is exposed (the no-MFMA build of the one-wave kernel still
@@ -641,9 +570,6 @@ __device__ __forceinline__ void w1_load(W1Chunk& ck, const float* da, const floa
 template <int Q, int K>
 __device__ __forceinline__ void w1_mfma(f32x4 (&ax)[8], f32x4 (&ay)[8], f32x4 (&az)[4][2], const W1Chunk& ck)
 {
-#ifdef AHV_DIAG_W1_NO_MFMA  // diagnostic build of tools/kbench_bwd only (wrong results)
-    asm volatile("" ::"v"(ck.a[0]), "v"(ck.a[3]), "v"(ck.b[0]), "v"(ck.b[1]), "v"(ck.b[7]));
-#else
     if (K < 8) {
         constexpr int k0 = 4 * (K & 1);
 #pragma unroll
@@ -658,7 +584,6 @@ __device__ __forceinline__ void w1_mfma(f32x4 (&ax)[8], f32x4 (&ay)[8], f32x4 (&
             for (int a0 = 0; a0 < 2; ++a0)
                 az[Q][a0] = __builtin_amdgcn_mfma_f32_16x16x4f32(ck.a[i], ck.b[2 * i + a0], az[Q][a0], 0, 0, 0);
     }
-#endif
 }
 
 template <int Q, int K>
@@ -706,9 +631,6 @@ __device__ __forceinline__ void bwd_w1_quarter(f32x4 (&ax)[8], f32x4 (&ay)[8], f
 template <int Q>
 __device__ __forceinline__ void w1_gather(float* xbuf, const float* srcT, const GatherHyp& gh, const GatherDst& dst)
 {
-#ifdef AHV_DIAG_W1_NO_GATHER  // diagnostic build of tools/kbench_bwd only (wrong results)
-    asm volatile("" ::"v"(xbuf), "v"(dst.o0));
-#else
     float* d0 = xbuf + dst.o0;
     __builtin_amdgcn_s_setprio(1);  // the gathering wave is latency-bound, its partner streams MFMAs (ahv_dual.h)
     HatVoxel vx;
@@ -717,7 +639,6 @@ __device__ __forceinline__ void w1_gather(float* xbuf, const float* srcT, const 
     hat_voxel<Q>(vx, srcT, gh, 1);
     hat_one_pass<3, kXwStride>(vx, d0 + 32);
     __builtin_amdgcn_s_setprio(0);
-#endif
 }
 
 constexpr int kW1Threads = 512;
@@ -865,36 +786,6 @@ __global__ __launch_bounds__(256) void score_backward_w1_reduce_kernel(const flo
     if (hi > lo) global_add(grad_W1 + i, acc);
 }
 
-// ---- kernel 2b building blocks -------------------------------------------------------------------------
-// dX image of kernel 2b: dX[c][voxel], voxel = a0*64 + b*8 + e, rows kVxStride floats apart.  Deliberately NOT
-// the XOR-swizzled layout of the forward's quarter image: here every access is "per-lane base + compile-time
-// constant" (MFMA-result stores, their read-modify-writes and the scatter's reads), so the 16 stores / loads of
-// an MFMA group cost one address register and immediate offsets.  With the swizzle the lane-dependent XOR had
-// to be recomputed for each of them: ~80 VALU instructions per group of 16 MFMAs, more issue time than the
-// MFMAs' own (fp32 MFMA and VALU do not overlap).  The 4-float pad spreads the four k-quads of a store over
-// the banks; the residual 4-way conflicts of the x / y read-modify-writes cost LDS cycles nobody waits for.
-constexpr int kVxStride = 132;
-constexpr int kVxFloats = 16 * kVxStride;
-
-// MFMA with the A operand taken straight from an ACCUMULATOR register.  Kernel 2b keeps the 192 W1^T fragments
-// of a lane resident for the whole launch; with one wave per SIMD they fit the 256 AGPRs, but hipcc treats AGPRs
-// as spill space and re-reads every fragment through v_accvgpr_read (+ hazard nops) in front of its MFMA --
-// 768 extra VALU-slot instructions per hypothesis that the matrix pipe cannot overlap (measured: 0.79 ms of a
-// 1.65-ms kernel for 0.38 ms of MFMA work).  The "a" constraint makes the fragment an AGPR operand of the MFMA
-// itself (legal on gfx90a+: SrcA/SrcB may be AGPRs).  hipcc neither sees the instruction inside the statement nor
-// pads its hazards, so the statement does: `s_nop 1` in front covers a VALU write of an operand immediately
-// before it (2 wait states), and the LAST MFMA of an accumulation chain is followed by 12 wait states before
-// anything may read D (8-pass MFMA -> VALU / LDS reader).  Back-to-back MFMAs on the same accumulator need none.
-__device__ __forceinline__ void mfma_areg(f32x4& d, float a_in_agpr, float b)
-{
-    asm volatile("s_nop 1\n\tv_mfma_f32_16x16x4_f32 %0, %1, %2, %0" : "+v"(d) : "a"(a_in_agpr), "v"(b));
-}
-
-__device__ __forceinline__ void mfma_chain_end(f32x4& d0, f32x4& d1)
-{
-    asm volatile("s_nop 7\n\ts_nop 3" : "+v"(d0), "+v"(d1));
-}
-
 // du of one hypothesis as MFMA B operands, straight from the workspace into registers: lane (n, kq) holds
 // du[o = 4 sp + kq][pos = 16 t + n] for sp < 8, t < 4 -- 32 floats.  The x / y slabs of quarter Q use tile t = Q,
 // the z slab all four tiles, so no LDS image of du is needed in this kernel.
@@ -912,268 +803,19 @@ __device__ __forceinline__ void load_du_regs(DuRegs& d, const float* __restrict_
         for (int sp = 0; sp < 8; ++sp) d.v[t][sp] = p[(2 * t + (sp >> 2)) * 256 + (sp & 3) * 64];
 }
 
-// Kernel 2b runs TWO waves per SIMD, split by CHANNEL: wave role r = wave / 4 owns channels 8 r .. 8 r + 7 of
-// dV.  Everything downstream of du splits cleanly along that axis -- the rows of dX = W1^T du are (channel,
-// slab index), the scatter adds channel by channel -- so the pair shares nothing but the (atomic) dV image:
-//   * W1^T fragments per wave: x and y slabs k-tiles 4 r .. 4 r + 3 (channel = 2 kt + (kq >> 1)), z slab with the
-//     tile rows re-packed as (a0, channel - 8 r): 32 + 32 + 32 = 96 accumulator-file registers instead of 192,
-//     384 MFMAs per wave and hypothesis instead of 768, none wasted;
-//   * dX image per wave: 8 channels x 128 voxels; scatter lanes = 8 channels x 8 voxels per step.
-// Waves w and w + 4 (same SIMD) walk the same hypotheses independently, like kernel 2a.  The one-wave-per-SIMD
-// form of this kernel (1.44 ms) was the sum of its parts: 0.47 ms skeleton + 0.26 ms atomics + 0.69 ms for
-// 0.38 ms worth of MFMAs, nothing overlapping anything.
-constexpr int kVhFloats = 8 * kVxStride;  // half-channel dX image
-
-// one MFMA output tile = one accumulator fed by 8 k-steps; two tiles side by side (see mfma_areg)
-template <int Q>
-__device__ __forceinline__ void bwd_vol_dx(const float (&wx)[4][8], const float (&wy)[4][8], const float (&wz)[4][8],
-                                           const DuRegs& du, float* xbuf, int lane)
-{
-    const int n = lane & 15, kq = lane >> 4;
-    const int i0 = n >> 3, j = n & 7;
-    // z slab: tile rows = (a0' = row >> 3, c8 = row & 7); row = 4 kq + r; column = position (b = 2 t + i0, e = j)
-    {
-        float* zb = xbuf + 4 * (kq & 1) * kVxStride + (kq >> 1) * 64 + 8 * i0 + j;
-#pragma unroll
-        for (int t = 0; t < 4; t += 2) {
-            f32x4 d0 = f32x4{0.f, 0.f, 0.f, 0.f}, d1 = d0;
-#pragma unroll
-            for (int sp = 0; sp < 8; ++sp) {
-                mfma_areg(d0, wz[Q][sp], du.v[t][sp]);
-                mfma_areg(d1, wz[Q][sp], du.v[t + 1][sp]);
-            }
-            mfma_chain_end(d0, d1);
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                zb[r * kVxStride + 16 * t] = d0[r];
-                zb[r * kVxStride + 16 * (t + 1)] = d1[r];
-            }
-        }
-    }
-    wave_lds_fence();
-    // x: local channel = 2 kt + (kq >> 1), voxel = i0*64 + j*8 + 4 (kq & 1) + r;  y: voxel = i0*64 + (4 (kq & 1) + r)*8 + j
-#pragma unroll
-    for (int slab = 0; slab < 2; ++slab) {
-        float* rb = xbuf + (kq >> 1) * kVxStride + 64 * i0 + (slab == 0 ? 8 * j + 4 * (kq & 1) : 32 * (kq & 1) + j);
-        const int rs = slab == 0 ? 1 : 8;
-#pragma unroll
-        for (int kt = 0; kt < 4; kt += 2) {
-            f32x4 d0 = f32x4{0.f, 0.f, 0.f, 0.f}, d1 = d0;
-            float o0[4], o1[4];
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                o0[r] = rb[2 * kt * kVxStride + rs * r];
-                o1[r] = rb[(2 * kt + 2) * kVxStride + rs * r];
-            }
-#pragma unroll
-            for (int sp = 0; sp < 8; ++sp) {
-                mfma_areg(d0, slab == 0 ? wx[kt][sp] : wy[kt][sp], du.v[Q][sp]);
-                mfma_areg(d1, slab == 0 ? wx[kt + 1][sp] : wy[kt + 1][sp], du.v[Q][sp]);
-            }
-            mfma_chain_end(d0, d1);
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                rb[2 * kt * kVxStride + rs * r] = o0[r] + d0[r];
-                rb[(2 * kt + 2) * kVxStride + rs * r] = o1[r] + d1[r];
-            }
-        }
-        wave_lds_fence();
-    }
-}
-
-// Corner table of quarter Q (phase A, one voxel per lane and pass: the gather's map): 8 hat weights and the byte
-// offset of row (jz, jy, jx) in the image of dV; the eight corners sit at constant offsets from it (the base index
-// is clamped to [0, 6], see ahv_dual.h).  12 floats per voxel.
-constexpr int kCtRow = 12;
-// channel-last image of dV in 64-bit words, kDvRow = 17 words per voxel (16 channels + 1 pad): the voxels of a
-// scatter instruction then start on different banks instead of all on bank 0 (136-byte rows)
-constexpr int kDvRow = 17;
-constexpr int kDvCornerBytes(int n) { return (((n & 1) ? 1 : 0) + ((n & 2) ? 8 : 0) + ((n & 4) ? 64 : 0)) * kDvRow * 8; }
-
-template <int Q>
-__device__ __forceinline__ void bwd_vol_corners(float* ctab, const GatherHyp& h, const GatherDst& dst)
-{
-#pragma unroll
-    for (int p = 0; p < 2; ++p) {
-        float jx, jy, jz, wx0, wx1, wy0, wy1, wz0, wz1;
-        hat_axis(gather_coord<Q>(h, 0, p), jx, wx0, wx1);
-        hat_axis(gather_coord<Q>(h, 1, p), jy, wy0, wy1);
-        hat_axis(gather_coord<Q>(h, 2, p), jz, wz0, wz1);
-        const float w00 = wz0 * wy0, w01 = wz0 * wy1, w10 = wz1 * wy0, w11 = wz1 * wy1;
-        const float base = fmaf(jz, 64.0f * (kDvRow * 8), fmaf(jy, 8.0f * (kDvRow * 8), jx * (float)(kDvRow * 8)));  // bytes
-        float* row = ctab + (p ? dst.o1 : dst.o0) * kCtRow;
-        *reinterpret_cast<f32x4*>(row + 0) = f32x4{w00 * wx0, w00 * wx1, w01 * wx0, w01 * wx1};
-        *reinterpret_cast<f32x4*>(row + 4) = f32x4{w10 * wx0, w10 * wx1, w11 * wx0, w11 * wx1};
-        row[8] = __uint_as_float((unsigned)base);
-    }
-}
-
-// x (|x| < 2^31, scaled contribution) -> nearest integer, sign-extended to the 64-bit accumulator word.
-// v_cvt_rpi_i32_f32 = floor(x + 0.5): one instruction, no bias towards zero (v_cvt_i32_f32 truncates).
-__device__ __forceinline__ long long to_fixed32(float x)
-{
-    int i;
-    asm("v_cvt_rpi_i32_f32 %0, %1" : "=v"(i) : "v"(x));
-    return (long long)i;
-}
-
-// dV += trilinear^T dX (phase B): lane (c8, vq) adds local channel c8 of eight voxels per step, the voxels of a
-// step 4 apart in b and 2 apart in e, so that for a rotation their 2x2x2 corner footprints rarely share a word
-// (any R stays correct: the adds are atomic).  The image is 64-bit fixed point because ds_add_f32 is ~40x slower
-// than the integer LDS atomics on gfx950 (tools/lds_atomic_probe.cpp: 771 vs 19 (u32) / 28 (u64) cycles per
-// wave-instruction); every addend is rounded to a 32-bit integer (31 bits below the per-sample bound, finer than an
-// fp32 mantissa for all but the largest terms), the sums are exact and do not depend on the order of the adds.
-__device__ __forceinline__ void bwd_vol_scatter(const float* xbuf, const float* ctab, long long* dV, float fx_scale, int role, int lane)
-{
-    const int c8 = lane & 7, vq = lane >> 3;
-    char* dvc = reinterpret_cast<char*>(dV + 8 * role + c8);
-    const int vlane = 32 * (vq & 1) + 2 * (vq >> 1);  // b += 4 (vq & 1), e += 2 (vq >> 1)
-#pragma unroll 2
-    for (int st = 0; st < 16; ++st) {
-        // step -> (a0, b' < 4, e' < 2): voxel = a0*64 + (b' + 4 (vq&1))*8 + e' + 2 (vq>>1)
-        const int vox = vlane + (st >> 3) * 64 + ((st >> 1) & 3) * 8 + (st & 1);
-        const float d = xbuf[c8 * kVxStride + vox] * fx_scale;
-        const float* row = ctab + vox * kCtRow;
-        const f32x4 w0 = *reinterpret_cast<const f32x4*>(row + 0), w1 = *reinterpret_cast<const f32x4*>(row + 4);
-        char* base = dvc + __float_as_uint(row[8]);
-        // unconditional: a zero weight adds 0 to a valid row.  Branching on the weight put every atomic in its
-        // own basic block behind an s_waitcnt lgkmcnt(0), i.e. serialised their latencies.
-#pragma unroll
-        for (int nb = 0; nb < 4; ++nb) {
-            lds_add_i64(reinterpret_cast<long long*>(base + kDvCornerBytes(nb)), to_fixed32(w0[nb] * d));
-            lds_add_i64(reinterpret_cast<long long*>(base + kDvCornerBytes(4 + nb)), to_fixed32(w1[nb] * d));
-        }
-    }
-}
-
-constexpr int kVolThreads = 512;
-// the scattering wave (VALU + LDS latency) issues first, its partner streams MFMAs: same reasoning as the forward's gather
-#define AHV_VOL_PRIO(x) __builtin_amdgcn_s_setprio(x)
-
-__global__ __launch_bounds__(kVolThreads, 2) void score_backward_volume_kernel(
-    const float* __restrict__ R, long r_batch_stride, const float* __restrict__ W1, int B, long N,
-    const float* __restrict__ du_ws, const unsigned* __restrict__ du_max_bits, float* __restrict__ grad_vol)
-{
-    __shared__ __attribute__((aligned(16))) long long lds_dv[512 * kDvRow];   // channel-last, 64-bit fixed point
-    __shared__ __attribute__((aligned(16))) float lds_x[8 * kVhFloats];       // per wave: dX of its 8 channels
-    __shared__ __attribute__((aligned(16))) float lds_ct[8 * 128 * kCtRow];   // per wave: corner table of a quarter
-    __shared__ float lds_bound[4];
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int slot = wave & 3, role = wave >> 2;  // waves w and w + 4 share a SIMD and a hypothesis list
-    const int kq = lane >> 4, row = lane & 15;
-    float* xbuf = lds_x + wave * kVhFloats;
-    float* ctab = lds_ct + wave * (128 * kCtRow);
-
-    // |dX| <= (sum over the three slabs of max_k sum_o |W1[o][k]|) * max|du|: fixes the fixed-point scale per sample
-    {
-        float* colsum = lds_x;  // 384 floats of scratch before the hypothesis loop
-        for (int k = tid; k < 384; k += kVolThreads) {
-            float a = 0.0f;
-            for (int o = 0; o < 32; ++o) a += fabsf(W1[o * 384 + k]);
-            colsum[k] = a;
-        }
-        __syncthreads();
-        if (tid < 3) {
-            float m = 0.0f;
-            for (int k = 0; k < 128; ++k) m = fmaxf(m, colsum[128 * tid + k]);
-            lds_bound[tid] = m;
-        }
-        __syncthreads();
-    }
-    const float w1_bound = lds_bound[0] + lds_bound[1] + lds_bound[2];
-
-    // W1^T fragments of this wave's channel half, A operands of dX: [tile][k-step over o]: W1[o = 4 s' + kq][k]
-    //   x / y: k = 16 (4 role + kt) + row                 (channel 8 role + 2 kt + (row >> 3), slab index row & 7)
-    //   z:     k = 256 + (8 role + (row & 7)) * 8 + 2 q + (row >> 3)      (tile rows = (a0, local channel))
-    float wx[4][8], wy[4][8], wz[4][8];
-#pragma unroll
-    for (int sp = 0; sp < 8; ++sp) {
-        const float* w = W1 + (4 * sp + kq) * 384;
-#pragma unroll
-        for (int kt = 0; kt < 4; ++kt) {
-            wx[kt][sp] = w[16 * (4 * role + kt) + row];
-            wy[kt][sp] = w[128 + 16 * (4 * role + kt) + row];
-        }
-#pragma unroll
-        for (int q = 0; q < 4; ++q) wz[q][sp] = w[256 + (8 * role + (row & 7)) * 8 + 2 * q + (row >> 3)];
-    }
-    const GatherLane glane = gather_lane(lane);
-    const GatherDst gdst = gather_dst_linear(lane);
-
-    const long hstep = (long)gridDim.x * 4;
-    for (int b = blockIdx.y; b < B; b += gridDim.y) {
-        __syncthreads();
-        for (int i = tid; i < 512 * kDvRow; i += kVolThreads) lds_dv[i] = 0ll;
-        __syncthreads();
-        // every addend w * dX (w <= 1) is rounded to a 32-bit integer in units of 2^-fx_exp with |addend| < 2^30;
-        // the 64-bit words then have room for 2^33 of them
-        const float bound = w1_bound * __uint_as_float(du_max_bits[b]);
-        int ex = 0;
-        (void)frexpf(bound, &ex);
-        const bool usable = bound > 0.0f && bound < 3.0e38f;
-        const int fx_exp = usable ? min(max(30 - ex, -80), 80) : 0;
-        const float fx_scale = usable ? ldexpf(1.0f, fx_exp) : 0.0f;
-        const float* Rb = R + (long)b * r_batch_stride;
-        long h = (long)slot * gridDim.x + xcd_residue(blockIdx.x, gridDim.x, gridDim.y);
-        DuRegs du;
-        if (h < N) load_du_regs(du, du_ws + ((long)b * N + h) * 2048, lane);
-        for (; h < N; h += hstep) {
-            float Rm[9];
-#pragma unroll
-            for (int i = 0; i < 9; ++i) Rm[i] = Rb[h * 9 + i];
-            GatherHyp gh;
-            gather_hyp(gh, Rm, glane);
-            DuRegs nxt;  // the next hypothesis's du travels from HBM / L2 while this one is processed
-            const long hn = (h + hstep < N) ? h + hstep : h;
-            load_du_regs(nxt, du_ws + ((long)b * N + hn) * 2048, lane);
-            bwd_vol_dx<0>(wx, wy, wz, du, xbuf, lane);
-            AHV_VOL_PRIO(1);
-            bwd_vol_corners<0>(ctab, gh, gdst); wave_lds_fence();
-            bwd_vol_scatter(xbuf, ctab, lds_dv, fx_scale, role, lane); wave_lds_fence();
-            AHV_VOL_PRIO(0);
-            bwd_vol_dx<1>(wx, wy, wz, du, xbuf, lane);
-            AHV_VOL_PRIO(1);
-            bwd_vol_corners<1>(ctab, gh, gdst); wave_lds_fence();
-            bwd_vol_scatter(xbuf, ctab, lds_dv, fx_scale, role, lane); wave_lds_fence();
-            AHV_VOL_PRIO(0);
-            bwd_vol_dx<2>(wx, wy, wz, du, xbuf, lane);
-            AHV_VOL_PRIO(1);
-            bwd_vol_corners<2>(ctab, gh, gdst); wave_lds_fence();
-            bwd_vol_scatter(xbuf, ctab, lds_dv, fx_scale, role, lane); wave_lds_fence();
-            AHV_VOL_PRIO(0);
-            bwd_vol_dx<3>(wx, wy, wz, du, xbuf, lane);
-            AHV_VOL_PRIO(1);
-            bwd_vol_corners<3>(ctab, gh, gdst); wave_lds_fence();
-            bwd_vol_scatter(xbuf, ctab, lds_dv, fx_scale, role, lane); wave_lds_fence();
-            AHV_VOL_PRIO(0);
-            du = nxt;
-        }
-        __syncthreads();
-        // non-finite upstream gradients: the bound is inf/NaN, nothing was accumulated -> report NaN like autograd would
-        const float unscale = usable ? ldexpf(1.0f, -fx_exp) : (bound == 0.0f ? 0.0f : __builtin_nanf(""));
-        float* gv = grad_vol + (long)b * (16 * 512);
-        for (int i = tid; i < 16 * 512; i += kVolThreads) {
-            const int c = i >> 9, v = i & 511;
-            const long long a = lds_dv[v * kDvRow + c];
-            if (a != 0ll || !usable) global_add(gv + i, (float)a * unscale + (usable ? 0.0f : unscale));
-        }
-    }
-}
-
-
 // -------------------------------------------------------------------------------------------------
-// Kernel 2b, round 6: the same dV = sum_h trilinear_h^T (W1^T du_h), WITHOUT LDS atomics.
+// Kernel 2b, round 6: dV = sum_h trilinear_h^T (W1^T du_h), WITHOUT LDS atomics.
 //
-// What bounded score_backward_volume_kernel above (profiles/r06_training_pmc_summary.json, B = 32 x N = 9 000: 8.4 ms, 0.37 of
-// the fp32 matrix peak) is its scatter: 1 024 ds_add_u64 wave-instructions per hypothesis on a pipe the four SIMDs share, and
-// three vector instructions per atomic (scale, round to integer, sign-extend) that fp32 MFMAs cannot overlap -- 5 679 vector
+// What bounded the LDS-atomic kernel of rounds 2-5 (64-bit fixed-point image of dV; HISTORY.md, code: commit 86a1f1c;
+// profiles/r06_training_pmc_summary.json, B = 32 x N = 9 000: 8.4 ms, 0.37 of the fp32 matrix peak) is its scatter: 1 024
+// ds_add_u64 wave-instructions per hypothesis on a pipe the four SIMDs share, and three vector instructions per atomic
+// (scale, round to integer, sign-extend) that fp32 MFMAs cannot overlap -- 5 679 vector
 // instructions per hypothesis against 768 MFMAs.  A plain read-modify-write moves the same bytes with ONE packed FMA per two
 // channels, but it is only correct if no two lanes of an instruction (and no two waves) touch the same word.  Both can be
 // arranged:
 //   * between waves: a workgroup runs TWO hypotheses at a time (slots), each with a PRIVATE fp32 image of dV; the four waves
 //     of a slot (one per SIMD) own four channels each, so they share the hypothesis' corner table and never an address.  (Four
-//     private images -- one per hypothesis in flight, as kernel 2b has them in flight -- do not fit the 160 KB of LDS beside
+//     private images -- one per hypothesis in flight, as the atomic kernel had them in flight -- do not fit the 160 KB of LDS beside
 //     the dX images; hence four waves per hypothesis, split by channel.)
 //   * inside an instruction: lanes = 8 voxels x 8 corners, each lane the four channels of its wave (16 bytes).  The 8 corners of
 //     a voxel are 8 different rows; the 8 voxels are 4 apart in z, y and x, and for a rotation two lattice points 4 apart land
@@ -1182,7 +824,7 @@ __global__ __launch_bounds__(kVolThreads, 2) void score_backward_volume_kernel(
 //   * the forward's clamped footprint (base row in [0, 6], hat weights) gives corners outside the volume a weight of exactly
 //     0 on a row that may belong to another lane's voxel: such a corner is redirected to a trash row when the corner table is
 //     built (its byte offset is part of the table), so a zero weight never writes a live word back.
-// Sums are fp32 in the order the hypotheses arrive (the fixed-point image of kernel 2b was exact and order-free): the
+// Sums are fp32 in the order the hypotheses arrive (the fixed-point image of the atomic kernel was exact and order-free): the
 // gradients agree with the fp64 reference to ~1e-6 of their largest entry, like those of the other kernels.
 // Per hypothesis and wave: 192 MFMAs (x / y slabs: 2 row tiles of (channel, k); z slab: ONE row tile of (depth, channel) over
 // the four depths of a half volume -- quarters {H, H + 2} -- so that no MFMA row is wasted on four channels), 64 scatter
@@ -1515,15 +1157,15 @@ __global__ __launch_bounds__(kRmwThreads, 2) void score_backward_volume_rmw_kern
             if (slot == 0 && first && m == 0 && lane == 0) __hip_atomic_store(&lds_skew, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
             first = false;
             AHV_RMW_T(4);   // waiting for the table
-            AHV_VOL_PRIO(1);   // the scattering wave is latency-bound: it issues first, its SIMD partner streams MFMAs
+            __builtin_amdgcn_s_setprio(1);   // the scattering wave is latency-bound: it issues first, its SIMD partner streams MFMAs
             rmw_scatter_half<0>(xbuf, ctab, img_ch, rotation, lane);
-            AHV_VOL_PRIO(0);
+            __builtin_amdgcn_s_setprio(0);
             AHV_RMW_T(5);   // scatter half 0
             rmw_dx_half<1>(wx, wy, wz, du, xbuf, lane);
             AHV_RMW_T(6);   // dX half 1
-            AHV_VOL_PRIO(1);
+            __builtin_amdgcn_s_setprio(1);
             rmw_scatter_half<1>(xbuf, ctab, img_ch, rotation, lane);
-            AHV_VOL_PRIO(0);
+            __builtin_amdgcn_s_setprio(0);
             rmw_signal(&lds_sync[slot].done, lane);
             AHV_RMW_T(7);   // scatter half 1
             ++iter;
@@ -1549,16 +1191,16 @@ hipError_t launch_zero_fill(void* const* ptrs, const size_t* bytes, int count, h
 // ---- host-side launcher -------------------------------------------------------------------------------
 hipError_t launch_score_backward(const float* vol_src, const float* feat_tgt, const float* R, int64_t r_batch_stride,
                                  const float* W1, const float* W2, const float* b2, int B, int64_t N,
-                                 const float* grad_scores, float* du_ws, unsigned* du_max_bits, float* dw1_partials,
+                                 const float* grad_scores, float* du_ws, float* dw1_partials,
                                  float* grad_vol, float* grad_feat_tgt,
                                  float* grad_W1, float* grad_W2, float* grad_b2, int num_cu, hipStream_t stream, bool saved_u)
 {
     hipError_t e;
-    {   // accumulation targets (and the running maximum of |du|, bit pattern 0 = 0.0f): one zero-fill launch
-        void* const ptrs[6] = {grad_vol, grad_feat_tgt, grad_W1, grad_W2, grad_b2, du_max_bits};
-        const size_t bytes[6] = {sizeof(float) * (size_t)B * 8192, sizeof(float) * (size_t)B * 2048, sizeof(float) * 32 * 384,
-                                 sizeof(float) * 32 * 32, sizeof(float) * 32, (B > 0 && N > 0) ? sizeof(unsigned) * (size_t)B : 0};
-        if ((e = launch_zero_fill(ptrs, bytes, 6, stream)) != hipSuccess) return e;
+    {   // accumulation targets: one zero-fill launch
+        void* const ptrs[5] = {grad_vol, grad_feat_tgt, grad_W1, grad_W2, grad_b2};
+        const size_t bytes[5] = {sizeof(float) * (size_t)B * 8192, sizeof(float) * (size_t)B * 2048, sizeof(float) * 32 * 384,
+                                 sizeof(float) * 32 * 32, sizeof(float) * 32};
+        if ((e = launch_zero_fill(ptrs, bytes, 5, stream)) != hipSuccess) return e;
     }
     if (B == 0 || N == 0) return hipSuccess;
     int gy = B < num_cu ? B : num_cu;
@@ -1574,12 +1216,11 @@ hipError_t launch_score_backward(const float* vol_src, const float* feat_tgt, co
         if (gxs > need8) gxs = (int)need8;
         if (gxs < 1) gxs = 1;
         hipLaunchKernelGGL(score_backward_head_saved_kernel, dim3(gxs, gy), dim3(kSavedThreads), 0, stream, feat_tgt, W2, b2, B,
-                           (long)N, grad_scores, du_ws, du_max_bits, grad_feat_tgt, grad_W2, grad_b2);
+                           (long)N, grad_scores, du_ws, grad_feat_tgt, grad_W2, grad_b2);
     }
     else
         hipLaunchKernelGGL(score_backward_head_kernel, grid, dim3(kBwdThreads), 0, stream, vol_src, feat_tgt, R,
-                           (long)r_batch_stride, W1, W2, b2, B, (long)N, grad_scores, du_ws, du_max_bits, grad_feat_tgt, grad_W2,
-                           grad_b2);
+                           (long)r_batch_stride, W1, W2, b2, B, (long)N, grad_scores, du_ws, grad_feat_tgt, grad_W2, grad_b2);
     if ((e = hipGetLastError()) != hipSuccess) return e;
     hipLaunchKernelGGL(score_backward_w1_kernel, grid, dim3(kW1Threads), 0, stream, vol_src, R, (long)r_batch_stride,
                        B, (long)N, du_ws, dw1_partials);
@@ -1587,10 +1228,6 @@ hipError_t launch_score_backward(const float* vol_src, const float* feat_tgt, co
     hipLaunchKernelGGL(score_backward_w1_reduce_kernel, dim3(32 * 384 / 256, 16), dim3(256), 0, stream, dw1_partials,
                        gx * gy, grad_W1);
     if ((e = hipGetLastError()) != hipSuccess) return e;
-#ifdef AHV_BWD_VOLUME_ATOMICS  // rounds 2-5: the scatter as 64-bit fixed-point LDS atomics (kept for A/B builds: tools/kbench_bwd)
-    hipLaunchKernelGGL(score_backward_volume_kernel, grid, dim3(kVolThreads), 0, stream, R, (long)r_batch_stride, W1,
-                       B, (long)N, du_ws, du_max_bits, grad_vol);
-#else
     {   // two hypotheses per workgroup at a time: spread a short list over more workgroups
         int gxv = num_cu / gy;
         const int64_t need2 = (N + 1) / 2;
@@ -1599,7 +1236,6 @@ hipError_t launch_score_backward(const float* vol_src, const float* feat_tgt, co
         hipLaunchKernelGGL(score_backward_volume_rmw_kernel, dim3(gxv, gy), dim3(kRmwThreads), 0, stream, R, (long)r_batch_stride,
                            W1, B, (long)N, du_ws, grad_vol);
     }
-#endif
     return hipGetLastError();
 }
 

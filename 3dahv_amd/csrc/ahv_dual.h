@@ -359,9 +359,11 @@ __device__ __forceinline__ void hat_axis(float i, float& jf, float& w0, float& w
 // wave of another kernel sharing their SIMD.  Rounds 3-4 ruled that out for the scorers by occupancy -- two waves of 249-256
 // registers take all 512 of a SIMD (tests/test_isa_hazard.py still checks the allocation) -- but the waves of a workgroup
 // retire one by one, and beside the LAST wave of a SIMD a foreign wave fits.  Since round 5 every kernel that uses this
-// gather defines AHV_FP32_LOW_HALF (ahv_score.hip, ahv_backward.hip): measured cost 0.2-0.7 % (tools/kbench_lowhalf,
-// kbench_bwd_lowhalf: 0.6809 -> 0.6828 ms per 50 000 hypotheses, 2.576 -> 2.588 ms per backward; profiles/r04d_low_half_ab.txt).
-#if defined(AHV_FP32_LOW_HALF) || defined(AHV_DIAG_FP32_LOW_HALF)
+// gather defines AHV_FP32_LOW_HALF (ahv_score.hip, ahv_backward.hip; ahv_ops.hip issues no MFMAs and does not): measured
+// cost 0.2-0.7 % (0.6809 -> 0.6828 ms per 50 000 hypotheses, 2.576 -> 2.588 ms per backward; profiles/r04d_low_half_ab.txt).
+// The A/B builds with and without it, and the unprotected split-f16 build that shows the hazard itself, are described in
+// HISTORY.md; their code was last in commit 86a1f1c.
+#ifdef AHV_FP32_LOW_HALF
 constexpr bool kFp32LowHalf = true;
 #else
 constexpr bool kFp32LowHalf = false;
@@ -369,9 +371,7 @@ constexpr bool kFp32LowHalf = false;
 
 __device__ __forceinline__ float low_half(float x)
 {
-#ifndef AHV_DIAG_NO_LOW_HALF  // tools/first_launch_sweep.sh builds the unprotected kernel once, to show the hazard itself
     asm volatile("" : "+v"(x));
-#endif
     return x;
 }
 
@@ -414,10 +414,6 @@ __device__ __forceinline__ void hat_voxel_at(HatVoxel& v, const float* srcT, f32
     const float af = fmaf(jz, (float)(4 * kSrcPlaneRows * kSrcStride),
                           fmaf(jy, (float)(4 * kSrcRowsY * kSrcStride), jx * (float)(4 * kSrcStride)));
     v.base = reinterpret_cast<const char*>(srcT) + (unsigned)af;
-#ifdef AHV_DIAG_LINEAR_GATHER  // diagnostic only (wrong results): row = lane, so every b128 lane group of every corner
-    // request covers the 16 slots once -- the conflict-free bound of the gather (tools/kbench, profiles/r03_scorer_segments.txt)
-    v.base = reinterpret_cast<const char*>(srcT) + (threadIdx.x & 63) * (4 * kSrcStride);
-#endif
 }
 
 // pass p of quarter Q, Q a compile-time constant (the one-wave-per-hypothesis kernels)
@@ -495,10 +491,6 @@ __device__ __forceinline__ void hat_mirror(HatState& st, const float* srcT)
     const char* top = reinterpret_cast<const char*>(srcT) + kSrcMirrorBytes;
 #pragma unroll
     for (int k = 0; k < 2; ++k) st.vx[k].base = top - (st.vx[k].base - reinterpret_cast<const char*>(srcT));
-#ifdef AHV_DIAG_LINEAR_GATHER
-#pragma unroll
-    for (int k = 0; k < 2; ++k) st.vx[k].base = reinterpret_cast<const char*>(srcT) + (threadIdx.x & 63) * (4 * kSrcStride);
-#endif
 }
 
 // head of the mirrored quarter's gather (the counterpart of hat_prologue)

@@ -48,24 +48,10 @@ static int g_enc_probe_dup = 0;
 namespace ahv {
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
-// Output stores of the big launches (experiment knobs, A/B on one box with tools/kbench_enc): non-temporal stores leave less
-// dirty data in the L2s for the write-back at the end of a kernel, which sits between every two launches of this forward.
-#ifndef AHV_TILE_NT_STORES
-#define AHV_TILE_NT_STORES 1
-#endif
-#ifndef AHV_ROW_NT_STORES
-#define AHV_ROW_NT_STORES 0
-#endif
-#if AHV_TILE_NT_STORES
-#define AHV_TILE_STORE(p, v) __builtin_nontemporal_store((v), (p))
-#else
-#define AHV_TILE_STORE(p, v) (*(p) = (v))
-#endif
-#if AHV_ROW_NT_STORES
-#define AHV_ROW_STORE4(p, v) __builtin_nontemporal_store((v), reinterpret_cast<f32x4*>(p))
-#else
-#define AHV_ROW_STORE4(p, v) (*reinterpret_cast<f32x4*>(p) = (v))
-#endif
+// Output stores of the big launches (A/B on one box with tools/kbench_enc): the tile linear stores non-temporally, which
+// leaves less dirty data in the L2s for the write-back at the end of a kernel, which sits between every two launches of
+// this forward.  The row kernels (attention + output projection, LayerNorm / concat) store plainly: non-temporal stores
+// there measured 1 910 / 1 909 against 1 901 / 1 905 us per forward at B = 32, 317 against 309 us at B = 1 (HISTORY.md).
 
 
 constexpr int kMaxProb = 4;
@@ -446,9 +432,6 @@ struct TileArgs {
 // ahead 0.81; LDS-DMA 0.83; the issue order 0.90 (profiles/r05_tile_kernel_diag.txt).
 // TM = 4: 128 x 128 tiles (a wave owns 64 x 64), M >= 1024 rows of the FF projections.  TM = 2: 64 x 64 tiles (a wave owns
 // 32 x 32) for the 256-wide projections, whose 128-tiles would not fill the chip.
-#ifndef AHV_DIAG_TILE  // diagnostic only (wrong results): bit 1 no tile loads, 2 no fragment reads, 3 no barrier
-#define AHV_DIAG_TILE 0
-#endif
 template <int TM>
 struct TileFrags {
     f32x4 a[TM], b[TM];
@@ -565,8 +548,8 @@ __global__ __launch_bounds__(256, 2) void linear_tile_kernel(const TileArgs a)
     // branch would cost hipcc its count of what is in flight (it then waits for the fragment reads in front of the MFMAs).
     auto kstep = [&](int kt, const TileFrags<TM>& cur, TileFrags<TM>& nxt) {
         __builtin_amdgcn_sched_barrier(0);
-        if (!(AHV_DIAG_TILE & 2)) gload(kt + 3 < nk ? kt + 3 : nk - 1, (kt + 3) & 3);
-        if (!(AHV_DIAG_TILE & 4)) fread(nxt, (kt + 1) & 3);
+        gload(kt + 3 < nk ? kt + 3 : nk - 1, (kt + 3) & 3);
+        fread(nxt, (kt + 1) & 3);
         mma(cur);
         // issue order: the 3 TM memory instructions go BETWEEN the MFMAs (one per TM), where their issue slots are free --
         // all of them in front of the first MFMA leave the matrix pipe waiting whenever the SIMD's other wave stands at
@@ -584,7 +567,7 @@ __global__ __launch_bounds__(256, 2) void linear_tile_kernel(const TileArgs a)
         __builtin_amdgcn_sched_group_barrier(0x008, TM * TM, 0);
         __builtin_amdgcn_sched_barrier(0);
         __builtin_amdgcn_s_waitcnt(kWait);
-        if (!(AHV_DIAG_TILE & 8)) __builtin_amdgcn_s_barrier();
+        __builtin_amdgcn_s_barrier();
     };
     // prologue: tiles 0, 1, 2 requested; tiles 0 and 1 landed before the first barrier
     TileFrags<TM> f0, f1;
@@ -595,7 +578,6 @@ __global__ __launch_bounds__(256, 2) void linear_tile_kernel(const TileArgs a)
     __builtin_amdgcn_s_barrier();
     AHV_ENC_STAMP(1);
     fread(f0, 0);
-    if (AHV_DIAG_TILE & 4) fread(f1, 0);
     // (a wait here, or hipcc carries "f0 pending" into the loop)
     __builtin_amdgcn_s_waitcnt(0xc07f);  // lgkmcnt(0)
     for (int kt = 0; kt < nk; kt += 2) {  // nk is even (tile_eligible)
@@ -620,8 +602,8 @@ __global__ __launch_bounds__(256, 2) void linear_tile_kernel(const TileArgs a)
                     const long row = m0 + 64 * wr + 16 * i + 4 * kq + r;
                     const f32x2 y = geglu_pk(f32x2{acc[i][j][r] + bv, acc[i][j][r + 1] + bv},
                                              f32x2{acc[i][j + 2][r] + bg, acc[i][j + 2][r + 1] + bg});
-                    AHV_TILE_STORE(pr.P + row * H + col, y[0]);
-                    AHV_TILE_STORE(pr.P + (row + 1) * H + col, y[1]);
+                    __builtin_nontemporal_store(y[0], pr.P + row * H + col);
+                    __builtin_nontemporal_store(y[1], pr.P + (row + 1) * H + col);
                 }
         }
     } else {
@@ -634,7 +616,7 @@ __global__ __launch_bounds__(256, 2) void linear_tile_kernel(const TileArgs a)
             for (int i = 0; i < TM; ++i)
 #pragma unroll
                 for (int r = 0; r < 4; ++r)
-                    AHV_TILE_STORE(P + (long)(m0 + 16 * TM * wr + 16 * i + 4 * kq + r) * pr.N + col, acc[i][j][r] + bias);
+                    __builtin_nontemporal_store(acc[i][j][r] + bias, P + (long)(m0 + 16 * TM * wr + 16 * i + 4 * kq + r) * pr.N + col);
         }
     }
     AHV_ENC_STAMP(6);
@@ -669,16 +651,13 @@ struct AttnOutArgs {
 // w of W_out (64 MFMAs).  96 dependent MFMAs per wave instead of 192, a quarter of the K / V loads.  The result is
 // one split-K slab PER HEAD, P[h][M][256]; ln_kernel sums the four.
 // -------------------------------------------------------------------------------------------------
-// QT query tiles per workgroup (round 6 experiment, QT = 1 ships): a workgroup can walk several 16-query tiles of its
-// (sample, head) with the K, V and W_out fragments it holds in registers (96 of the ~100 KB a workgroup reads; only Q changes
-// per tile, requested a tile ahead).  At B = 32 it changes nothing (see AHV_ATTN_QT at the launch): the launch is bound by the
-// dependent chain of a tile (16 + 16 + 64 MFMAs, two barriers, a softmax), not by its 100 MB of L2 reads.
+// One query tile per workgroup.  Walking 2 or 4 tiles of a (sample, head) with the K, V and W_out fragments held in registers
+// (round 6) changed nothing at B = 32 -- 1 964 / 1 958 / 1 960 us per forward for 1 / 2 / 4 tiles, 17.6-18.1 us per launch
+// either way: the launch is bound by the dependent chain of a tile (16 + 16 + 64 MFMAs, two barriers, a softmax), not by its
+// 100 MB of L2 reads (HISTORY.md; the multi-tile code was last in commit 86a1f1c).
 // (sample, head) pairs from which attention_sample_head_kernel runs (tools/kbench_enc, both kernels alternating on one box, us per
 // forward: B = 8 -- 64 pairs -- 751 with the tile-wise kernel / 784 with this one; B = 16: 1 106 / 1 111; B = 24: 1 606 / 1 596; B = 32: 1 919 / 1 895)
-#ifndef AHV_ATTN_PAIR_MIN_WGS
-#define AHV_ATTN_PAIR_MIN_WGS 192
-#endif
-template <int QT>
+constexpr int kAttnPairMinWgs = 192;
 __global__ __launch_bounds__(256) void attention_heads_kernel(const AttnOutArgs a, int M)
 {
     __shared__ float sm[4][16][2];                                   // per wave and query: (max, sum)
@@ -687,9 +666,9 @@ __global__ __launch_bounds__(256) void attention_heads_kernel(const AttnOutArgs 
     const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int pi = (int)blockIdx.x / a.B, b = (int)blockIdx.x - pi * a.B;
     const AttnOutProb pr = a.p[pi];
-    const int it0 = blockIdx.y * QT, h = blockIdx.z;
+    const int it = blockIdx.y, h = blockIdx.z;
     const int c16 = lane & 15, kq = lane >> 4;
-    const float* q = pr.Q + (long)(b * 64 + it0 * 16 + c16) * pr.ldq + h * 64 + 4 * kq;
+    const float* q = pr.Q + (long)(b * 64 + it * 16 + c16) * pr.ldq + h * 64 + 4 * kq;
     const float* k = pr.K + (long)(b * 64 + w * 16 + c16) * pr.ldkv + h * 64 + 4 * kq;
     const float* v = pr.V + (long)(b * 64 + w * 16 + 4 * kq) * pr.ldkv + h * 64 + c16;
     AHV_ENC_STAMP(0);
@@ -711,21 +690,17 @@ __global__ __launch_bounds__(256) void attention_heads_kernel(const AttnOutArgs 
         for (int dt = 0; dt < 4; ++dt)
             wf[nt][dt] = *reinterpret_cast<const f32x4*>(pr.Wo + (long)(w * 64 + nt * 16 + c16) * 256 + h * 64 + 16 * dt + 4 * kq);
     __builtin_amdgcn_sched_barrier(0);
+    // One trip: what remains of the multi-tile form.  hipcc schedules the loads above and the chain below as separate
+    // regions because of the loop; without it, it emits a different (unmeasured) schedule.
 #pragma unroll 1
-    for (int t = 0; t < QT; ++t) {
-        f32x4 qn[4];   // the next tile's queries travel while this one is processed (the last tile re-reads itself)
-        if (QT > 1) {
-            const float* qq = q + (long)(t + 1 < QT ? t + 1 : t) * 16 * pr.ldq;
-#pragma unroll
-            for (int ds = 0; ds < 4; ++ds) qn[ds] = *reinterpret_cast<const f32x4*>(qq + 16 * ds);
-        }
+    for (int t = 0; t < 1; ++t) {
         // S^T[j = 16 w + 4 kq + r][i = c16]
         f32x4 st = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
         for (int ds = 0; ds < 4; ++ds)
 #pragma unroll
             for (int s = 0; s < 4; ++s) st = __builtin_amdgcn_mfma_f32_16x16x4f32(ka[ds][s], qb[ds][s], st, 0, 0, 0);
-        if (t == 0) AHV_ENC_STAMP(1);
+        AHV_ENC_STAMP(1);
         float m = -INFINITY;
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
@@ -746,9 +721,9 @@ __global__ __launch_bounds__(256) void attention_heads_kernel(const AttnOutArgs 
             sm[w][c16][0] = m;
             sm[w][c16][1] = l;
         }
-        if (t == 0) AHV_ENC_STAMP(2);
+        AHV_ENC_STAMP(2);
         __syncthreads();
-        if (t == 0) AHV_ENC_STAMP(3);
+        AHV_ENC_STAMP(3);
         float mg = -INFINITY;
 #pragma unroll
         for (int u = 0; u < 4; ++u) mg = fmaxf(mg, sm[u][c16][0]);
@@ -768,8 +743,8 @@ __global__ __launch_bounds__(256) void attention_heads_kernel(const AttnOutArgs 
         }
 #pragma unroll
         for (int dt = 0; dt < 4; ++dt) *reinterpret_cast<f32x4*>(&so[w][dt][lane][0]) = ot[dt];
-        if (t == 0) AHV_ENC_STAMP(4);
-        __syncthreads();   // (also: everybody has read sm, the next tile may overwrite it; so is rewritten behind the next tile's first barrier)
+        AHV_ENC_STAMP(4);
+        __syncthreads();
 #pragma unroll
         for (int dt = 0; dt < 4; ++dt) {
             ot[dt] = *reinterpret_cast<const f32x4*>(&so[0][dt][lane][0]);
@@ -787,15 +762,12 @@ __global__ __launch_bounds__(256) void attention_heads_kernel(const AttnOutArgs 
 #pragma unroll
                 for (int nt = 0; nt < 4; ++nt)
                     acc[nt] = __builtin_amdgcn_mfma_f32_16x16x4f32(wf[nt][dt][r], ot[dt][r], acc[nt], 0, 0, 0);
-        float* out = pr.P + ((long)h * M + b * 64 + (it0 + t) * 16 + c16) * 256 + w * 64 + 4 * kq;
-        if (t == 0) { asm volatile("" :: "v"(acc[0]), "v"(acc[1]), "v"(acc[2]), "v"(acc[3])); AHV_ENC_STAMP(5); }
+        float* out = pr.P + ((long)h * M + b * 64 + it * 16 + c16) * 256 + w * 64 + 4 * kq;
+        asm volatile("" :: "v"(acc[0]), "v"(acc[1]), "v"(acc[2]), "v"(acc[3]));
+        AHV_ENC_STAMP(5);
 #pragma unroll
-        for (int nt = 0; nt < 4; ++nt) AHV_ROW_STORE4(out + nt * 16, acc[nt]);
-        if (t == QT - 1) AHV_ENC_STAMP(6);
-        if (QT > 1) {
-#pragma unroll
-            for (int ds = 0; ds < 4; ++ds) qb[ds] = qn[ds];
-        }
+        for (int nt = 0; nt < 4; ++nt) *reinterpret_cast<f32x4*>(out + nt * 16) = acc[nt];
+        AHV_ENC_STAMP(6);
     }
 }
 
@@ -951,7 +923,7 @@ __global__ __launch_bounds__(256) void attention_sample_head_kernel(const AttnOu
                 for (int i = 0; i < 4; ++i) acc[i] = __builtin_amdgcn_mfma_f32_16x16x4f32(wf[i][dt], ot[dt][r], acc[i], 0, 0, 0);
         }
 #pragma unroll
-        for (int i = 0; i < 4; ++i) AHV_ROW_STORE4(out + 16 * (4 * ng + i), acc[i]);
+        for (int i = 0; i < 4; ++i) *reinterpret_cast<f32x4*>(out + 16 * (4 * ng + i)) = acc[i];
     }
     AHV_ENC_STAMP(6);
 }
@@ -997,10 +969,10 @@ __global__ __launch_bounds__(256) void ln_kernel(const LnArgs a)
     const float rstd = 1.0f / sqrtf(var + 1e-5f);
     const f32x4 y = d * rstd * gam + bet;
     if (CONCAT) {
-        AHV_ROW_STORE4(pr.out + (long)row * 512 + 4 * lane, xin);
-        AHV_ROW_STORE4(pr.out + (long)row * 512 + 256 + 4 * lane, y);
+        *reinterpret_cast<f32x4*>(pr.out + (long)row * 512 + 4 * lane) = xin;
+        *reinterpret_cast<f32x4*>(pr.out + (long)row * 512 + 256 + 4 * lane) = y;
     } else {
-        AHV_ROW_STORE4(pr.out + (long)row * 256 + 4 * lane, xin + y);
+        *reinterpret_cast<f32x4*>(pr.out + (long)row * 256 + 4 * lane) = xin + y;
     }
 }
 
@@ -1154,7 +1126,6 @@ static hipError_t launch_linear(const LinSpec* specs, int nprob, long ldx, long 
         if (i < nprob) tiles += sp.N / cols;
     }
     const dim3 grid(tiles, KS, M / 64);
-#ifndef AHV_ENC_NO_STAGED
     if (mode != 2 && (a.Kc == 256 || (a.Kc == 512 && mode == 0)) && (!wide || (KS == 1 && a.Kc == 512))) {  // K-pipelined form (same grid)
         if (mode == 1 && a.Kc == 256) AHV_ENC_LAUNCH((linear_staged_kernel<1, 256, false, 1>), grid, dim3(512), 0, s, a);
         else if (mode == 0 && wide && a.Kc == 512) AHV_ENC_LAUNCH((linear_staged_kernel<2, 512, true>), grid, dim3(512), 0, s, a);
@@ -1163,15 +1134,10 @@ static hipError_t launch_linear(const LinSpec* specs, int nprob, long ldx, long 
         else return hipErrorInvalidValue;
         return hipGetLastError();
     }
-#endif
-    if (mode == 1 && Kw == 32) AHV_ENC_LAUNCH((linear_kernel<1, 32, false, 1>), grid, dim3(512), 0, s, a);
-    else if (mode == 2 && Kw == 32) AHV_ENC_LAUNCH((linear_kernel<1, 32, false, 2>), grid, dim3(512), 0, s, a);
+    // every plain and GEGLU projection (mode 0) and the 2-D convolutions (mode 1) of this file take the staged form above;
+    // the 3-D convolutions (mode 2) stay with linear_kernel
+    if (mode == 2 && Kw == 32) AHV_ENC_LAUNCH((linear_kernel<1, 32, false, 2>), grid, dim3(512), 0, s, a);
     else if (mode == 2 && Kw == 16) AHV_ENC_LAUNCH((linear_kernel<1, 16, false, 2>), grid, dim3(512), 0, s, a);
-    else if (mode != 0) return hipErrorInvalidValue;
-    else if (wide && Kw == 64 && KS == 1) AHV_ENC_LAUNCH((linear_kernel<2, 64, true>), grid, dim3(512), 0, s, a);
-    else if (!wide && Kw == 64) AHV_ENC_LAUNCH((linear_kernel<1, 64, false>), grid, dim3(512), 0, s, a);
-    else if (!wide && Kw == 32 && !geglu_h) AHV_ENC_LAUNCH((linear_kernel<1, 32, false>), grid, dim3(512), 0, s, a);
-    else if (!wide && Kw == 16 && !geglu_h) AHV_ENC_LAUNCH((linear_kernel<1, 16, false>), grid, dim3(512), 0, s, a);
     else return hipErrorInvalidValue;
     return hipGetLastError();
 }
@@ -1179,10 +1145,8 @@ static hipError_t launch_linear(const LinSpec* specs, int nprob, long ldx, long 
 // Many-row path of two-problem plain / GEGLU linears (both streams in one launch); KS = 1 output layout.
 static bool tile_eligible(int M, int K, int N, int geglu_h)
 {
-#ifndef AHV_TILE_MIN_M
-#define AHV_TILE_MIN_M 1024
-#endif
-    if (M < AHV_TILE_MIN_M || (M & 127) || (K & 31)) return false;  // K per split: an even number of 16-wide k-steps
+    constexpr int kTileMinM = 1024;
+    if (M < kTileMinM || (M & 127) || (K & 31)) return false;  // K per split: an even number of 16-wide k-steps
     return geglu_h > 0 ? (geglu_h % 64 == 0 && N == 2 * geglu_h) : (N % 128 == 0);
 }
 
@@ -1190,12 +1154,10 @@ static bool tile_eligible(int M, int K, int N, int geglu_h)
 // 256-wide projections (K = 256, N = 256 / 512 / 768) at many rows: 64 x 64 tiles instead of the skinny kernel, whose
 // workgroups re-read their 64 x 256 X tile once per 16 output columns.  Measured per forward (tools/kbench_enc, graph):
 // B = 32: 2040 -> 2012 us (17.3 against 21.5 us per launch); B = 16: 1238 -> 1253; B = 8: 753 -> 761; B = 4: 490 -> 508.
-#ifndef AHV_TILE64_MIN_M
-#define AHV_TILE64_MIN_M 2048
-#endif
+constexpr int kTile64MinM = 2048;
 static bool tile64_eligible(const LinSpec* specs, int nprob, int M, int K)
 {
-    if (M < AHV_TILE64_MIN_M || (M & 63) || (K & 31) || nprob > kMaxProb) return false;
+    if (M < kTile64MinM || (M & 63) || (K & 31) || nprob > kMaxProb) return false;
     for (int i = 0; i < nprob; ++i)
         if (specs[i].N & 63) return false;
     return true;
@@ -1285,17 +1247,12 @@ static int run_block_pair(const ahv_block_weights* const w[2], const float* cons
             ao.p[i] = AttnOutProb{ws[i].qkv, ws[i].kv, ws[i].kv + 256, w[i]->w_out, ws[i].part, 256, 512};
     }
     {   // attention and the output projection in ONE launch (attention_heads_kernel), then norm1 + concat
-#ifndef AHV_ATTN_QT   // A/B knob (tools/kbench_enc): query tiles per workgroup at B >= 32.  Measured in round 6: 1 / 2 / 4 tiles per
-#define AHV_ATTN_QT 1   // workgroup give 1 964 / 1 958 / 1 960 us per forward (17.6-18.1 us per launch either way): not the re-reads
-#endif                  // of K, V and W_out bound this launch but the dependent chain of one tile; the one-tile form stays
 #ifdef AHV_ENC_PROBE
         ao.stamps = AHV_ENC_STAMP_PTR;
 #endif
         // from 192 (sample, head) pairs on (B >= 24): one workgroup per pair (attention_sample_head_kernel)
-        if (2 * B * 4 >= AHV_ATTN_PAIR_MIN_WGS) AHV_ENC_LAUNCH(attention_sample_head_kernel, dim3(2 * B, 4), dim3(256), 0, s, ao, M);
-        else if (B >= 32 && AHV_ATTN_QT == 4) AHV_ENC_LAUNCH(attention_heads_kernel<4>, dim3(2 * B, 1, 4), dim3(256), 0, s, ao, M);
-        else if (B >= 32 && AHV_ATTN_QT == 2) AHV_ENC_LAUNCH(attention_heads_kernel<2>, dim3(2 * B, 2, 4), dim3(256), 0, s, ao, M);
-        else AHV_ENC_LAUNCH(attention_heads_kernel<1>, dim3(2 * B, 4, 4), dim3(256), 0, s, ao, M);
+        if (2 * B * 4 >= kAttnPairMinWgs) AHV_ENC_LAUNCH(attention_sample_head_kernel, dim3(2 * B, 4), dim3(256), 0, s, ao, M);
+        else AHV_ENC_LAUNCH(attention_heads_kernel, dim3(2 * B, 4, 4), dim3(256), 0, s, ao, M);
         AHV_TRY(hipGetLastError(), "attention + out projection");
         LnArgs ln;
         ln.KS = 4; ln.M = M;  // one slab per head
@@ -1313,23 +1270,19 @@ static int run_block_pair(const ahv_block_weights* const w[2], const float* cons
         else AHV_TRY(launch_linear(sp, 2, 512, 512, M, 512, 1, 2048, s), "ff in + geglu");
         LnArgs ln;
         ln.M = M;
-#ifndef AHV_FFOUT_KS8_MAX_M
-#define AHV_FFOUT_KS8_MAX_M 128
-#endif
+        constexpr int kFfOutKs8MaxM = 128;   // skinny FF out: 8 K-splits up to B = 2 (below)
         // FF out on tiles: N = 256 gives only 2 column tiles per stream, so the K split has to fill the chip -- 8 ways up to
         // M = 1024 (B = 16: 256 workgroups instead of 128; forward 1 213 -> 1 117 us), 4 ways from M = 2048 (B = 32: 256
         // workgroups; 8 ways measured 1.3 % SLOWER there: 16 k-steps per workgroup and an 8-slab LayerNorm)
-#ifndef AHV_FFOUT_TILED_KS8_MAX_M
-#define AHV_FFOUT_TILED_KS8_MAX_M 1024
-#endif
-        if (tiled && M <= AHV_FFOUT_TILED_KS8_MAX_M) {
+        constexpr int kFfOutTiledKs8MaxM = 1024;
+        if (tiled && M <= kFfOutTiledKs8MaxM) {
             for (int i = 0; i < 2; ++i) sp[i] = LinSpec{ws[i].part, w[i]->w_ff2, ws[i].part + (size_t)M * 2048, nullptr, 256};
             AHV_TRY(launch_linear_tile(sp, 2, 2048, 2048, M, 2048, 8, 0, s, 128), "ff out (tiled, split-K 8)");
             ln.KS = 8;
             for (int i = 0; i < 2; ++i)
                 ln.p[i] = LnProb{ws[i].part + (size_t)M * 2048, w[i]->b_ff2, w[i]->ln2_g, w[i]->ln2_b, x[i], out[i]};
             AHV_ENC_LAUNCH((ln_kernel<false, 8>), dim3((M + 3) / 4, 2), dim3(256), 0, s, ln);
-        } else if (tiled || M > AHV_FFOUT_KS8_MAX_M) {
+        } else if (tiled || M > kFfOutKs8MaxM) {
             // FF out: 4 K-splits x [M][256] = [M][1024] floats: fits the qkv + kv scratch (1280 per row), free by now
             for (int i = 0; i < 2; ++i) sp[i] = LinSpec{ws[i].part, w[i]->w_ff2, ws[i].qkv, nullptr, 256};
             if (tiled) AHV_TRY(launch_linear_tile(sp, 2, 2048, 2048, M, 2048, 4, 0, s, 128), "ff out (tiled, split-K 4)");

@@ -19,18 +19,15 @@ namespace ahv {
 // No LDS besides the source image (47.5 KiB) -> three workgroups = 12 waves per CU at <= 168 registers (ring depth 2:
 // 3 and 4 rows spill).  First built with a per-wave LDS image and 16-byte stores (8 waves per CU): 1.245 ms against
 // 1.19-1.21 ms for this one on the same box, N = 200 000 (5.27 vs 5.43-5.52 TB/s; the minimum of ten launches 5.8).
-// What bounds it is the store stream itself: the same kernel with the gather removed (-DAHV_DIAG_ROT_STORE_ONLY) and
-// tools/store_probe.cpp (this store pattern, others, and a plain fill, from the same persistent grid) write 6.55 GB at
-// 5.3-6.1 TB/s whatever the pattern -- one 32 KiB region per wave, ~3 000 regions open at once -- and the gather with its
-// bank conflicts switched off (-DAHV_DIAG_LINEAR_GATHER) is no faster.
+// What bounds it is the store stream itself: the same kernel with the gather removed and tools/store_probe.cpp (this store
+// pattern, others, and a plain fill, from the same persistent grid) write 6.55 GB at 5.3-6.1 TB/s whatever the pattern --
+// one 32 KiB region per wave, ~3 000 regions open at once -- and the gather with its bank conflicts switched off is no
+// faster (diagnostic builds of round 5, HISTORY.md; their code was last in commit 86a1f1c).
 // A NaN / inf voxel: the workgroup sees it while staging and every hypothesis of the launch goes through
 // exact_gather_quarter_global (ahv_exact.h: grid_sample's per-corner zeros padding, utils.py:129) instead.
 // ---------------------------------------------------------------------------------
 constexpr int kRotThreads = 256;
-#ifndef AHV_DIAG_ROT_DEPTH
-#define AHV_DIAG_ROT_DEPTH 2
-#endif
-constexpr int kRotDepth = AHV_DIAG_ROT_DEPTH;  // rows the gather requests ahead: 2 -> 160 registers, 3 / 4 -> 8 / 22 spills and slower
+constexpr int kRotDepth = 2;  // rows the gather requests ahead: 2 -> 160 registers, 3 / 4 -> 8 / 22 spills and slower
 
 // Where a blended voxel goes: straight to out[n][c][...], one non-temporal 4-byte store per channel.  In a pass the 64 lanes
 // own the voxels (a0, 4 p + bq, e) of the quarter -- two runs of 32 consecutive floats per channel plane -- so every store
@@ -43,13 +40,7 @@ struct RotStoreGlobal {
     {
         float* dst = d[p];
 #pragma unroll
-        for (int c = 0; c < 16; ++c) {
-#ifdef AHV_DIAG_ROT_TEMPORAL
-            dst[c * 512] = o[c >> 1][c & 1];
-#else
-            __builtin_nontemporal_store(o[c >> 1][c & 1], dst + c * 512);
-#endif
-        }
+        for (int c = 0; c < 16; ++c) __builtin_nontemporal_store(o[c >> 1][c & 1], dst + c * 512);
     }
 };
 
@@ -58,13 +49,7 @@ __device__ __forceinline__ void rot_quarter(HatState& st, float* oq, const Gathe
 {
     f32x2 o[8];
     const RotStoreGlobal store = {{oq + (MIR ? dst.m0 : dst.o0), oq + (MIR ? dst.m1 : dst.o1)}};
-#ifdef AHV_DIAG_ROT_STORE_ONLY   // the store stream alone (wrong results): what the gather costs on top of it
-    for (int c = 0; c < 8; ++c) o[c] = f32x2{st.vx[0].w[0], st.vx[1].w[0]};
-    store(0, o);
-    store(1, o);
-#else
     HatSteps<0, RotStoreGlobal, MIR>::run(st, o, store);
-#endif
 }
 
 __global__ __launch_bounds__(kRotThreads, 3) void rotate_volume_16x8_kernel(
@@ -106,12 +91,6 @@ __global__ __launch_bounds__(kRotThreads, 3) void rotate_volume_16x8_kernel(
             gather_hyp(gh, Rm, glane);
             HatState st;
             // quarters in the order 0, 3, 1, 2: quarter 3 - Q is the point mirror of quarter Q and reuses its set-up
-#ifdef AHV_DIAG_ROT_STORE_ONLY
-            st.vx[0].w[0] = gh.ixy[0][0]; st.vx[1].w[0] = gh.izp[1];
-            rot_quarter<false>(st, o, gdst); rot_quarter<true>(st, o + 3 * 128, gdst);
-            rot_quarter<false>(st, o + 128, gdst); rot_quarter<true>(st, o + 2 * 128, gdst);
-            continue;
-#endif
             hat_prologue<0, kFp32LowHalf, kRotDepth>(st, srcT, gh);
             rot_quarter<false>(st, o, gdst);
             hat_prologue_mirror<kRotDepth>(st, srcT);

@@ -14,13 +14,11 @@
 // target features forward_3d2d(vol_tgt) built inside the launch: ahv_verify_pair_f32) and <true, false> (GEMM1 as
 // split-f16 MFMA products, opt-in through AHV_SCORE_SPLIT_F16; ahv_split.h).  The remainder of a launch that fills
 // less than a quarter of the wave slots is scored by TEAMS of four waves per hypothesis (ahv_team.h).
-#ifndef AHV_DIAG_NO_FP32_LOW_HALF  // (tools/kbench A/B build of the unprotected fp32 scorers)
 // The fp32 scorers keep every scalar they broadcast over a register pair in the LOW half too (low_half, ahv_dual.h).  Rounds 3-4
 // relied on occupancy instead (two waves of > 248 registers own the SIMD: no foreign XDL wave fits) -- true while both waves
 // run, but the older wave of a SIMD retires ~110 us before its partner, and in that tail a wave of another stream's XDL
 // kernel CAN land beside the remaining one.  75 more vector instructions per hypothesis (2 555 -> 2 630): +0.3 %.
 #define AHV_FP32_LOW_HALF
-#endif
 #include "ahv_dual.h"
 #include "ahv_split.h"
 #include "ahv_team.h"
@@ -117,23 +115,6 @@ __device__ __forceinline__ float hyp_score_rs(const f32x4 (&v)[2][4], const f32x
     return hyp_score_tail(ss, dt);
 }
 
-#ifdef AHV_DIAG_STAGE
-// Diagnostic builds only (tools/team_stage_diff.py): instead of the score a hypothesis returns an order-independent XOR
-// checksum of the BITS of one intermediate stage -- 1: GEMM1 pre-activations u, 2: head outputs v, 3: per-position sums of
-// squares and dot products, 4: per-position cosines -- computed the same way by a lone wave and by a team, so that the first
-// stage at which the two formulations differ can be read off.
-__device__ __forceinline__ unsigned diag_wave_xor(unsigned x)
-{
-#pragma unroll
-    for (int sft = 32; sft >= 1; sft >>= 1) x ^= (unsigned)__shfl_xor((int)x, sft, 64);
-    return x;
-}
-__device__ __forceinline__ unsigned diag_bits4(const f32x4& a)
-{
-    return __float_as_uint(a[0]) ^ (__float_as_uint(a[1]) * 3u) ^ (__float_as_uint(a[2]) * 5u) ^ (__float_as_uint(a[3]) * 7u);
-}
-#endif
-
 // A team member's share of hyp_score_rs (ahv_team.h): the sums of position tile t alone, associated exactly as
 // hyp_score_tail associates them -- lane rows (kq 0 + kq 2) + (kq 1 + kq 3), the normalisation per position, the row_shr
 // steps of wave_sum_dpp over the tile's 16 positions (rows 1-3 enter as zeros: x + 0 is exact).  Lane 63 returns P_t; the
@@ -149,10 +130,6 @@ __device__ __forceinline__ float team_tile_score(const f32x4 (&v)[2], const f32x
     ss += __shfl_xor(ss, 16, 64);
     dt += __shfl_xor(dt, 16, 64);
     const float c = lane < 16 ? dt * __builtin_amdgcn_rsqf(fmaxf(ss, 1e-24f)) : 0.0f;
-#ifdef AHV_DIAG_STAGE
-    if (AHV_DIAG_STAGE == 3) return __uint_as_float(diag_wave_xor(lane < 16 ? (__float_as_uint(ss) ^ (__float_as_uint(dt) * 3u)) : 0u));
-    if (AHV_DIAG_STAGE == 4) return __uint_as_float(diag_wave_xor(lane < 16 ? __float_as_uint(c) : 0u));
-#endif
     return wave_sum_dpp(c);
 }
 
@@ -311,10 +288,6 @@ __device__ __forceinline__ void score_hypotheses_body(
         lds_t_entry[0] = __builtin_amdgcn_s_memrealtime();
         lds_t_entry[1] = __builtin_amdgcn_s_memtime();
     }
-#ifdef AHV_DIAG_CODE_SHIFT  // diagnostic builds only (tools/first_launch.cpp): moves all the code below by 4 bytes per unit,
-    // i.e. to another position inside the 64-byte instruction-fetch lines
-    asm volatile(".rept %0\n s_nop 0\n .endr" ::"n"(AHV_DIAG_CODE_SHIFT));
-#endif
     const int tid = threadIdx.x;
     const int lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -438,7 +411,8 @@ __device__ __forceinline__ void score_hypotheses_body(
         __syncthreads();
         // a sample with a NaN / inf voxel or head weight leaves the hot loop for the exact path (ahv_exact.h); uniform
         const bool nf_w = __builtin_amdgcn_readfirstlane((int)lds_nf.weights) != 0;
-#ifdef AHV_DIAG_NO_EXACT  // diagnostic builds (tools/kbench): without the exact path's call, to price its mere presence
+#ifdef AHV_DIAG_NO_EXACT  // diagnostic builds without the exact path's call: tools/kbench prices its mere presence with it, and
+                          // tests/test_isa_hazard.py::test_scorers_use_no_scratch_memory checks the scorers' own registers
         const bool exact = false;
 #else
         const bool exact = nf_w || (unsigned)__builtin_amdgcn_readfirstlane((int)lds_nf.src_gen) == gen;
@@ -554,11 +528,7 @@ __device__ __forceinline__ void score_hypotheses_body(
                 float Rt = Rb[ht * 9 + rl];
                 auto team_emit = [&]() {  // member 0, behind an arrive point: the partials of the round before are complete
                     const float* pp = lds_team.part[team][(team_rounds + 1u) & 1u];
-#ifdef AHV_DIAG_STAGE
-                    const float sc = __uint_as_float(__float_as_uint(pp[0]) ^ __float_as_uint(pp[1]) ^ __float_as_uint(pp[2]) ^ __float_as_uint(pp[3]));
-#else
                     const float sc = ((pp[3] + pp[2]) + (pp[1] + pp[0])) * (1.0f / 64.0f);  // wave_sum_dpp's last two steps
-#endif
                     if (scores_s != nullptr && lane == 0) scores_s[(long)b * N_s + h_prev] = sc;
                     const key_t key = pack_key(sc, (unsigned)(n_offset_s + h_prev));
                     best = key > best ? key : best;
@@ -580,11 +550,7 @@ __device__ __forceinline__ void score_hypotheses_body(
                     team_head(v, u, f);
                     const f32x4 g0 = *reinterpret_cast<const f32x4*>(lds_src + ((2 * member) * 64 + lane) * kSrcStride + 16);
                     const f32x4 g1 = *reinterpret_cast<const f32x4*>(lds_src + ((2 * member + 1) * 64 + lane) * kSrcStride + 16);
-                    float tot = team_tile_score<kFp32LowHalf>(v, g0, g1, lane);
-#ifdef AHV_DIAG_STAGE
-                    if (AHV_DIAG_STAGE == 1) tot = __uint_as_float(diag_wave_xor(diag_bits4(u[0]) ^ (diag_bits4(u[1]) * 11u)));
-                    if (AHV_DIAG_STAGE == 2) tot = __uint_as_float(diag_wave_xor(diag_bits4(v[0]) ^ (diag_bits4(v[1]) * 11u)));
-#endif
+                    const float tot = team_tile_score<kFp32LowHalf>(v, g0, g1, lane);
                     if (lane == 63) lds_team.part[team][team_rounds & 1u][member] = tot;
                     ++team_rounds;
                     h_prev = ht;
@@ -630,9 +596,7 @@ __device__ __forceinline__ void score_hypotheses_body(
                 }
             }
         } else {
-#ifndef AHV_DIAG_TEAMS_LAST
         if constexpr (!SPLIT && !SAVE_U) score_remainder_by_teams();   // (the training forward runs single waves only: n_main = N)
-#endif
         // Hypothesis h -> (workgroup h % gridDim.x, wave slot (h / gridDim.x) % 8): a partial last round of the persistent
         // grid spreads over ALL CUs with few waves each instead of filling some CUs completely and leaving the rest idle.
         // The deal inside a workgroup is STATIC.  The older wave of a SIMD issues first and finishes its share ~110 us before
@@ -743,22 +707,6 @@ __device__ __forceinline__ void score_hypotheses_body(
                     for (int m2 = 0; m2 < 2; ++m2)
                         tg[t][m2] = *reinterpret_cast<const f32x4*>(lds_src + ((2 * t + m2) * 64 + lane) * kSrcStride + 16);
                 s = hyp_score_rs<kFp32LowHalf>(v, tg, lane);
-#ifdef AHV_DIAG_STAGE
-                {
-                    unsigned x = 0;
-                    if (AHV_DIAG_STAGE == 1) for (int t = 0; t < 4; ++t) x ^= diag_bits4(acc[0][t]) ^ (diag_bits4(acc[1][t]) * 11u);
-                    if (AHV_DIAG_STAGE == 2) for (int t = 0; t < 4; ++t) x ^= diag_bits4(v[0][t]) ^ (diag_bits4(v[1][t]) * 11u);
-                    if (AHV_DIAG_STAGE >= 3) {
-                        float ss[4], dt[4];
-                        for (int t = 0; t < 4; ++t) hyp_tile_sums<kFp32LowHalf>(ss[t], dt[t], v[0][t], v[1][t], tg[t][0], tg[t][1]);
-                        const float s1 = swap_add16(swap_add32(ss[0], ss[2]), swap_add32(ss[1], ss[3]));
-                        const float d1 = swap_add16(swap_add32(dt[0], dt[2]), swap_add32(dt[1], dt[3]));
-                        const float c = d1 * __builtin_amdgcn_rsqf(fmaxf(s1, 1e-24f));
-                        x = AHV_DIAG_STAGE == 3 ? (__float_as_uint(s1) ^ (__float_as_uint(d1) * 3u)) : __float_as_uint(c);
-                    }
-                    s = __uint_as_float(diag_wave_xor(x));
-                }
-#endif
             }
             if (scores_s != nullptr && lane == 0) scores_s[(long)b * N_s + h] = s;
             const key_t key = pack_key(s, (unsigned)(n_offset_s + h));
@@ -769,9 +717,6 @@ __device__ __forceinline__ void score_hypotheses_body(
             tsum[10] += 1;
 #endif
         }
-#ifdef AHV_DIAG_TEAMS_LAST  // diagnostic builds (tools/kbench): the remainder behind the main rounds, as in round 4
-        if constexpr (!SPLIT) score_remainder_by_teams();
-#endif
 #ifdef AHV_STAMPS
         if (lane == 0) {
             const int gw = (blockIdx.x * 8 + wave) & 2047;

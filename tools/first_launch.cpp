@@ -1,12 +1,10 @@
 // first_launch.cpp -- developer diagnostic for the split-f16 scorer (not part of the product).
 // Scores the same rotations with the split kernel in a process' FIRST launch and in later ones and compares each with
 // the fp32 kernel (run afterwards, so that the split kernel really is the first thing the process launches).
-// Together with two build knobs it is the regression check for the packed-fp32 op_sel hazard (low_half, ahv_dual.h):
-//   -DAHV_DIAG_CODE_SHIFT=k            moves the kernel's code by 4k bytes inside the 64-byte fetch lines (k = 0..15: the
-//                                      first-launch failures came and went with the position of the MFMA groups in them)
-//   -DAHV_DIAG_MFMA_GAP='"s_nop 7"'    leaves the matrix pipe idle between any two MFMAs of the split GEMM (turned ~1 % of
-//                                      the first launch's first hypotheses into 80 % of all scores before the fix)
-// tools/first_launch_sweep.sh builds and runs the lot.  Usage: first_launch [N] [sequence of A/B launches, default ABAAB]
+// Built with -DAHV_DIAG_MFMA_GAP='"s_nop 7"', which leaves the matrix pipe idle between any two MFMAs of the split GEMM (it
+// turned ~1 % of the first launch's first hypotheses into 80 % of all scores before the fix), it is the regression check
+// for the packed-fp32 op_sel hazard (low_half, ahv_dual.h; tests/test_gpu_split.py).
+// Usage: first_launch [N] [sequence of A/B launches, default ABAAB]
 #include "../3dahv_amd/csrc/ahv_score.hip"
 
 #include <algorithm>

@@ -1,7 +1,7 @@
 #!/bin/bash
 # GPU-side passes of a round, one sub-command each (through gpurun: `gpurun -- bash tools/gpu_run.sh <cmd> [tag]`).
 # Everything writes under gpurun_out/<tag>/; what is kept goes to profiles/ by hand.
-#   teams     bit-identity of team and lone-wave scores + kernel times of small launches, both team orders
+#   teams     bit-identity of team and lone-wave scores + kernel times of small launches with and without teams
 #   quick     the whole GPU test suite + kernel times at three sizes
 #   ab        two kbench builds alternating on one box
 #   stamps    in-kernel stamps of small launches (where a 6 250-hypothesis launch spends its time)
@@ -28,7 +28,7 @@ teams)
     timeout -k 10 600 python -m pytest tests/test_gpu_parity.py tests/test_gpu_verify.py tests/test_gpu_refine.py -x -q -m gpu > $O/pytest.log 2>&1
     echo "pytest rc=$?" | tee -a $O/pytest.log; tail -5 $O/pytest.log
     (for n in 6144 6250 2154 12500 25000 50000 1000 300; do for v in 3 5; do
-        kb kbench $n 300 $v 0 0; kb kbench $n 300 $v 0 1; kb kbench_teams_last $n 300 $v 0 0
+        kb kbench $n 300 $v 0 0; kb kbench $n 300 $v 0 1
     done; done) > $O/team_head.txt 2>&1
     grep -E "^--|variant [35]: 0|max" $O/team_head.txt | tail -60
     ;;

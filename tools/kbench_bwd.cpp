@@ -1,13 +1,9 @@
-// kbench_bwd.cpp -- developer micro-benchmark of the scorer's three backward kernels at the reference's training
-// size (B = 12 per-sample rotation sets of N = 3000), kernel by kernel, with diagnostic switches
-// (-DAHV_DIAG_NO_ATOMICS, -DAHV_DIAG_NO_DX: wrong results, to price a component).  Not part of the product.
+// kbench_bwd.cpp -- developer micro-benchmark of the scorer's backward kernels at the reference's training size
+// (B = 12 per-sample rotation sets of N = 3000), kernel by kernel.  Not part of the product.
 // Build: hipcc --offload-arch=gfx950 -O3 -std=c++17 -fno-slp-vectorize -I3dahv_amd/csrc -Iinclude tools/kbench_bwd.cpp -o tools/kbench_bwd
-// (the kernels as the library launches them).  With -DAHV_BWD_DU_AMAX -o tools/kbench_bwd_atomics the head kernels also produce
-// max |du| per sample and the LDS-atomic dV kernel of rounds 2-5 is timed and compared beside the read-modify-write one.
+// (the kernels as the library launches them; -DAHV_RMW_STAMPS adds the dV kernel's in-kernel phase times).
 #include "../3dahv_amd/csrc/ahv_backward.hip"
 
-#include <algorithm>
-#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <random>
@@ -40,12 +36,11 @@ int main(int argc, char** argv)
                              t * (j * k - i * r), t * (i * k - j * r), t * (j * k + i * r), 1 - t * (i * i + j * j)};
         for (int e = 0; e < 9; ++e) R[n * 9 + e] = (float)m[e];
     }
-    float *dvol, *dft, *dR, *dW1, *dW2, *db2, *dgs, *dws, *gvol, *gvol2, *gft, *gW1, *gW2, *gb2, *dpart;
-    unsigned* dmax;
+    float *dvol, *dft, *dR, *dW1, *dW2, *db2, *dgs, *dws, *gvol, *gft, *gW1, *gW2, *gb2, *dpart;
     CK(hipMalloc(&dvol, vol.size() * 4)); CK(hipMalloc(&dft, ft.size() * 4)); CK(hipMalloc(&dR, R.size() * 4));
     CK(hipMalloc(&dW1, W1.size() * 4)); CK(hipMalloc(&dW2, W2.size() * 4)); CK(hipMalloc(&db2, b2.size() * 4));
-    CK(hipMalloc(&dgs, gs.size() * 4)); CK(hipMalloc(&dws, (size_t)B * N * 2048 * 4)); CK(hipMalloc(&dmax, B * 4));
-    CK(hipMalloc(&dpart, (size_t)1024 * 32 * 384 * 4)); CK(hipMalloc(&gvol, vol.size() * 4)); CK(hipMalloc(&gvol2, vol.size() * 4)); CK(hipMalloc(&gft, ft.size() * 4)); CK(hipMalloc(&gW1, W1.size() * 4));
+    CK(hipMalloc(&dgs, gs.size() * 4)); CK(hipMalloc(&dws, (size_t)B * N * 2048 * 4));
+    CK(hipMalloc(&dpart, (size_t)1024 * 32 * 384 * 4)); CK(hipMalloc(&gvol, vol.size() * 4)); CK(hipMalloc(&gft, ft.size() * 4)); CK(hipMalloc(&gW1, W1.size() * 4));
     CK(hipMalloc(&gW2, W2.size() * 4)); CK(hipMalloc(&gb2, b2.size() * 4));
     CK(hipMemcpy(dvol, vol.data(), vol.size() * 4, hipMemcpyHostToDevice)); CK(hipMemcpy(dft, ft.data(), ft.size() * 4, hipMemcpyHostToDevice));
     CK(hipMemcpy(dR, R.data(), R.size() * 4, hipMemcpyHostToDevice)); CK(hipMemcpy(dW1, W1.data(), W1.size() * 4, hipMemcpyHostToDevice));
@@ -55,55 +50,36 @@ int main(int argc, char** argv)
     CK(hipDeviceGetAttribute(&cu, hipDeviceAttributeMultiprocessorCount, 0));
     int gy = B < cu ? B : cu, gx = cu / gy;
     const dim3 grid(gx, gy);
-    hipEvent_t e[7];
+    hipEvent_t e[5];
     for (auto& x : e) CK(hipEventCreate(&x));
-    double t[5] = {0, 0, 0, 0, 0};
+    double t[4] = {0, 0, 0, 0};
     for (int it = -2; it < iters; ++it) {
         CK(hipMemsetAsync(gvol, 0, vol.size() * 4, 0)); CK(hipMemsetAsync(gft, 0, ft.size() * 4, 0));
         CK(hipMemsetAsync(gW1, 0, W1.size() * 4, 0)); CK(hipMemsetAsync(gW2, 0, 4096, 0)); CK(hipMemsetAsync(gb2, 0, 128, 0));
-        CK(hipMemsetAsync(dmax, 0, B * 4, 0));
         CK(hipEventRecord(e[0], 0));
         hipLaunchKernelGGL(ahv::score_backward_head_kernel, grid, dim3(ahv::kBwdThreads), 0, 0, dvol, dft, dR, (long)(N * 9), dW1, dW2, db2,
-                           B, N, dgs, dws, dmax, gft, gW2, gb2);
+                           B, N, dgs, dws, gft, gW2, gb2);
         CK(hipEventRecord(e[1], 0));
         hipLaunchKernelGGL(ahv::score_backward_w1_kernel, grid, dim3(ahv::kW1Threads), 0, 0, dvol, dR, (long)(N * 9), B, N, dws, dpart);
         hipLaunchKernelGGL(ahv::score_backward_w1_reduce_kernel, dim3(32 * 384 / 256, 16), dim3(256), 0, 0, dpart, gx * gy, gW1);
         CK(hipEventRecord(e[2], 0));
-#ifdef AHV_BWD_DU_AMAX   // the LDS-atomic dV kernel of rounds 2-5 (needs max |du| per sample from the head kernel: kbench_bwd_atomics)
-        hipLaunchKernelGGL(ahv::score_backward_volume_kernel, grid, dim3(ahv::kVolThreads), 0, 0, dR, (long)(N * 9), dW1, B, N, dws, dmax, gvol);
-#endif
+        hipLaunchKernelGGL(ahv::score_backward_volume_rmw_kernel, grid, dim3(ahv::kRmwThreads), 0, 0, dR, (long)(N * 9), dW1, B, N, dws, gvol);
         CK(hipEventRecord(e[3], 0));
-        // round 6: the same gradient without LDS atomics (private fp32 images, read-modify-write), into its own buffer
-        CK(hipMemsetAsync(gvol2, 0, vol.size() * 4, 0));
-        CK(hipEventRecord(e[4], 0));
-        hipLaunchKernelGGL(ahv::score_backward_volume_rmw_kernel, grid, dim3(ahv::kRmwThreads), 0, 0, dR, (long)(N * 9), dW1, B, N, dws, gvol2);
-        CK(hipEventRecord(e[5], 0));
         {   // the training pair's head kernel (u from the workspace; for the clock any 8 KB per hypothesis will do: du stands in)
             int gxs = cu / gy;
             if (gxs > (N + 7) / 8) gxs = (int)((N + 7) / 8);
             hipLaunchKernelGGL(ahv::score_backward_head_saved_kernel, dim3(gxs < 1 ? 1 : gxs, gy), dim3(ahv::kSavedThreads), 0, 0, dft, dW2, db2,
-                               B, N, dgs, dws, dmax, gft, gW2, gb2);
+                               B, N, dgs, dws, gft, gW2, gb2);
         }
-        CK(hipEventRecord(e[6], 0));
-        CK(hipEventSynchronize(e[6]));
+        CK(hipEventRecord(e[4], 0));
+        CK(hipEventSynchronize(e[4]));
         CK(hipGetLastError());
-        if (it >= 0) {
-            for (int k = 0; k < 3; ++k) { float ms; CK(hipEventElapsedTime(&ms, e[k], e[k + 1])); t[k] += ms; }
-            float ms; CK(hipEventElapsedTime(&ms, e[4], e[5])); t[3] += ms;
-            CK(hipEventElapsedTime(&ms, e[5], e[6])); t[4] += ms;
-        }
+        if (it >= 0)
+            for (int k = 0; k < 4; ++k) { float ms; CK(hipEventElapsedTime(&ms, e[k], e[k + 1])); t[k] += ms; }
     }
-    std::vector<float> hv(vol.size()), hv2(vol.size());
+    std::vector<float> hv(vol.size());
     CK(hipMemcpy(hv.data(), gvol, vol.size() * 4, hipMemcpyDeviceToHost));
-    CK(hipMemcpy(hv2.data(), gvol2, vol.size() * 4, hipMemcpyDeviceToHost));
-    double mx = 0, md = 0;
-    for (size_t i = 0; i < hv.size(); ++i) { mx = std::max(mx, (double)std::fabs(hv[i])); md = std::max(md, (double)std::fabs(hv[i] - hv2[i])); }
-#ifdef AHV_BWD_DU_AMAX
-    printf("B=%d N=%ld: head %.3f ms  dW1 %.3f ms  dV %.3f ms (LDS atomics)  total %.3f ms   (grad_vol[0..2] = %g %g %g)\n", B, N, t[0] / iters,
-           t[1] / iters, t[2] / iters, (t[0] + t[1] + t[2]) / iters, hv[0], hv[1], hv[2]);
-#else
-    printf("B=%d N=%ld: head %.3f ms  dW1 %.3f ms   (grad_vol[0..2] = %g %g %g)\n", B, N, t[0] / iters, t[1] / iters, hv2[0], hv2[1], hv2[2]);
-#endif
+    printf("B=%d N=%ld: head %.3f ms  dW1 %.3f ms   (grad_vol[0..2] = %g %g %g)\n", B, N, t[0] / iters, t[1] / iters, hv[0], hv[1], hv[2]);
 #ifdef AHV_RMW_STAMPS
     {
         unsigned long long hs[64];
@@ -119,14 +95,8 @@ int main(int argc, char** argv)
         }
     }
 #endif
-#ifdef AHV_BWD_DU_AMAX
-    printf("           dV read-modify-write kernel %.3f ms  total with it %.3f ms   max |difference| / max |dV| = %.2e\n", t[3] / iters,
-           (t[0] + t[1] + t[3]) / iters, md / mx);
-#else
-    (void)md; (void)mx;
-    printf("           dV read-modify-write kernel %.3f ms  recomputing backward %.3f ms\n", t[3] / iters, (t[0] + t[1] + t[3]) / iters);
-#endif
-    printf("           head kernel of the training pair (u saved by the forward) %.3f ms  total with it %.3f ms\n", t[4] / iters,
-           (t[4] + t[1] + t[3]) / iters);
+    printf("           dV read-modify-write kernel %.3f ms  recomputing backward %.3f ms\n", t[2] / iters, (t[0] + t[1] + t[2]) / iters);
+    printf("           head kernel of the training pair (u saved by the forward) %.3f ms  total with it %.3f ms\n", t[3] / iters,
+           (t[3] + t[1] + t[2]) / iters);
     return 0;
 }

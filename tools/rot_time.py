@@ -1,7 +1,5 @@
 #!/usr/bin/env python3
-"""Developer tool: time ops.rotate_volume at N = 200 000 with the library given as argv[1] (default: the in-tree build).
-`make -C 3dahv_amd/csrc BUILD=tools/_dbg/lin CXXFLAGS="... -DAHV_DIAG_LINEAR_GATHER"` gives the conflict-free bound of the
-gather (wrong results): how much of the kernel's time is LDS bank conflicts."""
+"""Developer tool: time ops.rotate_volume at N = 200 000 with the library given as argv[1] (default: the in-tree build)."""
 import importlib, os, sys, torch
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, REPO)

@@ -1,6 +1,5 @@
 // tile_probe: linear_tile_kernel (ahv_encoder.hip) alone at chosen (M, K, N / H), events around 20 launches.
-// Build: hipcc --offload-arch=gfx950 -O3 -std=c++17 [-DAHV_DIAG_TILE=<mask>] -I3dahv_amd/csrc -Iinclude tools/tile_probe.cpp -o tools/tile_probe
-// AHV_DIAG_TILE (wrong results, timing only): bit 1 no tile loads, 2 no fragment reads, 3 no barrier.
+// Build: hipcc --offload-arch=gfx950 -O3 -std=c++17 -I3dahv_amd/csrc -Iinclude tools/tile_probe.cpp -o tools/tile_probe
 #include "../3dahv_amd/csrc/ahv_encoder.hip"
 #include <cstdio>
 #include <cstdlib>
