@@ -20,6 +20,8 @@ AHV_SCORE_NO_TEAMS = 4
 AHV_SCORE_SPARE_CUS_SHIFT = 8
 AHV_SELECT_RESET_KEY = 1
 AHV_KEY_EMPTY = -(1 << 63)
+AHV_TOPK_MAX_K = 64
+AHV_TOPK_RESET_LIST = 1
 
 _vp = ctypes.c_void_p
 _i64 = ctypes.c_int64
@@ -74,6 +76,11 @@ SIGNATURES["ahv_score_hypotheses_train_f32"] = (_int, [_vp, _vp, _vp, _i64, _vp,
 SIGNATURES["ahv_transformer_workspace_bytes"] = (ctypes.c_size_t, [_int])
 SIGNATURES["ahv_transformer_blocks_f32"] = (_int, [ctypes.POINTER(BlockWeights), _int, _vp, _vp, _int, _vp,
                                                    ctypes.c_size_t, _vp])
+SIGNATURES["ahv_topk_workspace_bytes"] = (ctypes.c_size_t, [_int, _i64, _int])
+SIGNATURES["ahv_topk_f32"] = (_int, [_vp, _int, _i64, _i64, _int, _vp, _vp, ctypes.c_size_t, _u32, _vp])
+SIGNATURES["ahv_topk_merge_keys"] = (_int, [_vp, _int, _int, _int, _vp, _u32, _vp])
+SIGNATURES["ahv_select_topk_f32"] = (_int, [_vp, _int, _vp, _i64, _i64, _i64, _int, _vp, _vp, _vp, _u32, _vp])
+SIGNATURES["ahv_compose_rotations_topk_f32"] = (_int, [_vp, _int, _vp, _i64, _i64, _i64, _vp, _i64, _int, _vp, _vp])
 
 # measurement / developer entry points (include/ahv_diag.h): not part of the drop-in boundary
 DIAG_SIGNATURES = {

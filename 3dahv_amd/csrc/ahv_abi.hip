@@ -25,6 +25,13 @@ hipError_t launch_compose_rotations(const int64_t*, const float*, int64_t, int64
 hipError_t launch_select_rotation(int64_t*, const float*, int64_t, int64_t, int64_t, int, float*, float*, int64_t*, bool,
                                   hipStream_t);
 hipError_t launch_fill_keys(int64_t*, int, hipStream_t);
+int topk_parts(int64_t N);
+hipError_t launch_topk(const float*, int, int64_t, int64_t, int, int64_t*, int64_t*, bool, hipStream_t);
+hipError_t launch_topk_merge(const int64_t*, int, int, int, int64_t*, bool, hipStream_t);
+hipError_t launch_select_topk(int64_t*, int, const float*, int64_t, int64_t, int64_t, int, float*, float*, int64_t*, bool,
+                              hipStream_t);
+hipError_t launch_compose_rotations_topk(const int64_t*, int, const float*, int64_t, int64_t, int64_t, const float*, int64_t,
+                                         int, float*, hipStream_t);
 hipError_t launch_random_rotations(uint64_t, uint64_t, int64_t, float*, hipStream_t);
 hipError_t launch_so3_grid(int64_t, int64_t, int64_t, float*, hipStream_t);
 hipError_t launch_score_backward(const float*, const float*, const float*, int64_t, const float*, const float*,
@@ -515,6 +522,95 @@ int ahv_argmax_f32(const float* scores, int B, int64_t N, int64_t n_offset, int6
     if (cu < 0) return fail(AHV_EDEVICE, "no usable HIP device");
     hipError_t e = ahv::launch_argmax(scores, B, N, n_offset, best_key, cu, s);
     if (e != hipSuccess) return hip_fail("argmax: launch", e);
+    return AHV_OK;
+}
+
+// ---- K best hypotheses ---------------------------------------------------------------------------------
+static bool bad_k(int K) { return K < 1 || K > AHV_TOPK_MAX_K; }
+
+size_t ahv_topk_workspace_bytes(int B, int64_t N, int K)
+{
+    if (B <= 0 || N <= 0 || bad_k(K)) return 0;
+    const int parts = ahv::topk_parts(N);
+    return parts <= 1 ? 0 : sizeof(int64_t) * (size_t)parts * (size_t)B * (size_t)K;
+}
+
+int ahv_topk_f32(const float* scores, int B, int64_t N, int64_t n_offset, int K, int64_t* keys, void* workspace,
+                 size_t workspace_bytes, unsigned flags, void* stream)
+{
+    if (bad_k(K)) return fail(AHV_EINVAL, "topk: K = %d outside 1..%d", K, AHV_TOPK_MAX_K);
+    if (B < 0 || N < 0) return fail(AHV_EINVAL, "topk: negative size");
+    if (B > 65535) return fail(AHV_EINVAL, "topk: B > 65535");
+    if (n_offset < 0 || n_offset + N > 4294967296ll) return fail(AHV_EINVAL, "topk: n_offset + N must fit in 32 bits");
+    if (flags & ~AHV_TOPK_RESET_LIST) return fail(AHV_EINVAL, "topk: unknown flags 0x%x", flags);
+    if (B == 0) return AHV_OK;
+    if (!keys || (N > 0 && !scores)) return fail(AHV_EINVAL, "topk: null pointer");
+    const size_t need = ahv_topk_workspace_bytes(B, N, K);
+    if (need && (!workspace || workspace_bytes < need || (reinterpret_cast<uintptr_t>(workspace) & 7)))
+        return fail(AHV_EINVAL, "topk: needs an 8-byte aligned workspace of %zu bytes (ahv_topk_workspace_bytes), got %zu", need,
+                    workspace_bytes);
+    const bool reset = (flags & AHV_TOPK_RESET_LIST) != 0;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (N == 0) {
+        if (!reset) return AHV_OK;
+        hipError_t e = ahv::launch_fill_keys(keys, B * K, s);
+        if (e != hipSuccess) return hip_fail("topk: list reset", e);
+        return AHV_OK;
+    }
+    hipError_t e = ahv::launch_topk(scores, B, N, n_offset, K, keys, static_cast<int64_t*>(workspace), !reset, s);
+    if (e != hipSuccess) return hip_fail("topk: launch", e);
+    return AHV_OK;
+}
+
+int ahv_topk_merge_keys(const int64_t* lists, int P, int B, int K, int64_t* keys, unsigned flags, void* stream)
+{
+    if (bad_k(K)) return fail(AHV_EINVAL, "topk_merge_keys: K = %d outside 1..%d", K, AHV_TOPK_MAX_K);
+    if (B < 0 || P < 0) return fail(AHV_EINVAL, "topk_merge_keys: negative size");
+    if (B > 65535) return fail(AHV_EINVAL, "topk_merge_keys: B > 65535");
+    if (flags & ~AHV_TOPK_RESET_LIST) return fail(AHV_EINVAL, "topk_merge_keys: unknown flags 0x%x", flags);
+    if (B == 0) return AHV_OK;
+    if (!keys || (P > 0 && !lists)) return fail(AHV_EINVAL, "topk_merge_keys: null pointer");
+    const bool reset = (flags & AHV_TOPK_RESET_LIST) != 0;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (P == 0) {
+        if (!reset) return AHV_OK;
+        hipError_t e = ahv::launch_fill_keys(keys, B * K, s);
+        if (e != hipSuccess) return hip_fail("topk_merge_keys: list reset", e);
+        return AHV_OK;
+    }
+    hipError_t e = ahv::launch_topk_merge(lists, P, B, K, keys, !reset, s);
+    if (e != hipSuccess) return hip_fail("topk_merge_keys: launch", e);
+    return AHV_OK;
+}
+
+int ahv_select_topk_f32(int64_t* keys, int K, const float* R, int64_t r_batch_stride, int64_t n_offset, int64_t N, int B,
+                        float* R_out, float* scores_out, int64_t* idx_out, unsigned flags, void* stream)
+{
+    if (bad_k(K)) return fail(AHV_EINVAL, "select_topk: K = %d outside 1..%d", K, AHV_TOPK_MAX_K);
+    if (B < 0 || N < 0) return fail(AHV_EINVAL, "select_topk: negative size");
+    if (flags & ~AHV_SELECT_RESET_KEY) return fail(AHV_EINVAL, "select_topk: unknown flags 0x%x", flags);
+    if (B == 0) return AHV_OK;
+    if (!keys) return fail(AHV_EINVAL, "select_topk: null keys");
+    if (R_out && (!R || N == 0)) return fail(AHV_EINVAL, "select_topk: R_out needs a rotation set");
+    if (r_batch_stride != 0 && r_batch_stride < N * 9) return fail(AHV_EINVAL, "select_topk: bad r_batch_stride");
+    hipError_t e = ahv::launch_select_topk(keys, K, R, r_batch_stride, n_offset, N, B, R_out, scores_out, idx_out,
+                                           (flags & AHV_SELECT_RESET_KEY) != 0, static_cast<hipStream_t>(stream));
+    if (e != hipSuccess) return hip_fail("select_topk: launch", e);
+    return AHV_OK;
+}
+
+int ahv_compose_rotations_topk_f32(const int64_t* keys, int K, const float* R, int64_t r_batch_stride, int64_t n_offset,
+                                   int64_t N, const float* D, int64_t N2, int B, float* out, void* stream)
+{
+    if (bad_k(K)) return fail(AHV_EINVAL, "compose_rotations_topk: K = %d outside 1..%d", K, AHV_TOPK_MAX_K);
+    if (B < 0 || N < 0 || N2 < 0) return fail(AHV_EINVAL, "compose_rotations_topk: negative size");
+    if (B == 0 || N2 == 0) return AHV_OK;
+    if (!keys || !R || !D || !out) return fail(AHV_EINVAL, "compose_rotations_topk: null pointer");
+    if (N == 0) return fail(AHV_EINVAL, "compose_rotations_topk: empty rotation set");
+    if (r_batch_stride != 0 && r_batch_stride < N * 9) return fail(AHV_EINVAL, "compose_rotations_topk: bad r_batch_stride");
+    hipError_t e = ahv::launch_compose_rotations_topk(keys, K, R, r_batch_stride, n_offset, N, D, N2, B, out,
+                                                      static_cast<hipStream_t>(stream));
+    if (e != hipSuccess) return hip_fail("compose_rotations_topk: launch", e);
     return AHV_OK;
 }
 

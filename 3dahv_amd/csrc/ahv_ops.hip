@@ -585,6 +585,200 @@ __global__ void select_rotation_kernel(key_t* __restrict__ best_key, const float
 }
 
 // ---------------------------------------------------------------------------------
+// K best hypotheses (the list counterpart of argmax_kernel / select_rotation_kernel / compose_rotations_kernel).
+// A list is K packed keys in descending SIGNED order, distinct, padded with kKeyEmpty.  With pack_key as it is that order
+// is torch.sort(scores, dim=1, descending=True, stable=True) truncated to K (NaN first, lowest index among equal
+// scores, -0 = +0); it is NOT torch.topk's order, which leaves ties unspecified.
+//
+// Everything on the critical path stays inside ONE wave: no barrier and no LDS round trip per round.
+//  - scores -> lists (topk_kernel<true>): a workgroup of four waves walks tiles of kTopkTile scores; a lane holds four
+//    candidates (one 16-byte load), and each wave on its own runs K knock-out rounds over its 256 -- a wave-wide max by DPP
+//    row operations, the lane that offered the winner moves to its largest key strictly below it -- and leaves a sorted
+//    K-list in LDS.  The four wave lists and the workgroup's running list are then merged by counting ranks (a fresh
+//    list: all keys distinct) or, when the caller's list is merged into in the same launch, by their HEADS.
+//  - lists -> list (merge_heads): one lane per sorted list; a round is the wave-wide max of the heads, and every lane
+//    whose head is the winner steps to its next entry (so a key met in several lists is taken once).  Up to 63 lists and
+//    the running list per pass; more lists are taken in passes.  This is ahv_topk_merge_keys, and the second launch of
+//    ahv_topk_f32.
+// Order, distinctness and the tie rule fall out of the integer compare.  A sample's N scores are spread over up to
+// kTopkMaxParts workgroups whose lists go to the workspace; the second launch merges them into the caller's list ACROSS A
+// KERNEL BOUNDARY -- no ticket, no loads that must dodge a stale per-XCD L2 line.  N <= one tile: one launch, straight into
+// the list.  (The first version ran every round workgroup-wide -- eight candidates per lane, four LDS words and a barrier
+// per round, in both launches: 1.1 us per round and pair of launches, slower than torch.topk + gather at K = 64.)
+// ---------------------------------------------------------------------------------
+constexpr int kTopkThreads = 256;
+constexpr int kTopkPerLane = 4;
+constexpr int kTopkTile = kTopkThreads * kTopkPerLane;  // 1024 scores per tile
+constexpr int kTopkMaxParts = 63;                       // partial lists per sample: with the running list, one lane each
+constexpr int kTopkMaxK = 64;
+
+// wave 0 only: merge sorted lists by their heads into out[0..K) (LDS).  mine: this lane's list (K keys, descending), or
+// nullptr for a lane without one.
+__device__ __forceinline__ void merge_heads(const key_t* mine, int K, key_t* out)
+{
+    const int lane = threadIdx.x & 63;
+    int pos = 0;
+    key_t head = mine ? mine[0] : kKeyEmpty;
+    for (int r = 0; r < K; ++r) {
+        const key_t m = wave_max_key_dpp(head);
+        if (lane == 0) out[r] = m;
+        if (m == kKeyEmpty) {  // fewer than K distinct keys: pad (uniform over the wave)
+            for (int j = r + 1 + lane; j < K; j += 64) out[j] = kKeyEmpty;
+            break;
+        }
+        while (head >= m) {  // my head won (or repeats the winner): step past it; kKeyEmpty < m ends the walk
+            ++pos;
+            head = pos < K ? mine[pos] : kKeyEmpty;
+        }
+    }
+}
+
+// one wave, K knock-out rounds over the lanes' candidates c[0..kTopkPerLane): out[0..K) (LDS) = the wave's sorted list
+__device__ __forceinline__ void wave_knock_out(const key_t (&c)[kTopkPerLane], int K, key_t* out)
+{
+    const int lane = threadIdx.x & 63;
+    key_t mine = c[0];
+#pragma unroll
+    for (int i = 1; i < kTopkPerLane; ++i) mine = c[i] > mine ? c[i] : mine;
+    for (int r = 0; r < K; ++r) {
+        const key_t m = wave_max_key_dpp(mine);
+        if (lane == 0) out[r] = m;
+        if (m == kKeyEmpty) {
+            for (int j = r + 1 + lane; j < K; j += 64) out[j] = kKeyEmpty;
+            break;
+        }
+        if (mine == m) {  // knocked out: my largest key strictly below the winner
+            key_t nxt = kKeyEmpty;
+#pragma unroll
+            for (int i = 0; i < kTopkPerLane; ++i) nxt = (c[i] < m && c[i] > nxt) ? c[i] : nxt;
+            mine = nxt;
+        }
+    }
+}
+
+// kScores: src = scores [B][N] (+ n_offset); workgroup (x, b) takes the tiles x, x + gridDim.x, ... of sample b.  Tiles are
+// laid on the 16-byte grid of the sample's row (a = the row's misalignment in floats), so that a lane's four scores are
+// one 16-byte load wherever all four exist; the ragged ends go element by element.
+// !kScores: src = lists [N][B][K] (N lists per sample), every one sorted as a list is.
+// carry: the list starts as out[b][0..K) (merge into) instead of empty.  out: [gridDim.x][B][K].
+template <bool kScores>
+__global__ __launch_bounds__(kTopkThreads) void topk_kernel(const void* __restrict__ src, int B, long N, long n_offset, int K,
+                                                            key_t* __restrict__ out, bool carry)
+{
+    __shared__ key_t run[2][kTopkMaxK];  // the running list and the one being built
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, b = blockIdx.y;
+    key_t* dst = out + ((long)blockIdx.x * B + b) * K;
+    if (tid < K) run[0][tid] = carry ? dst[tid] : kKeyEmpty;
+    int cur = 0;
+    if constexpr (kScores) {
+        __shared__ key_t wl[4][kTopkMaxK];  // the four wave lists of a tile
+        const float* s = static_cast<const float*>(src) + (long)b * N;
+        const long a = (long)((reinterpret_cast<unsigned long long>(s) >> 2) & 3ull);
+        const long tiles = (N + a + kTopkTile - 1) / kTopkTile;
+        for (long t = blockIdx.x; t < tiles; t += gridDim.x) {
+            key_t c[kTopkPerLane];
+            const long n0 = t * kTopkTile + (long)tid * 4 - a;  // first of the lane's four scores
+            if (n0 >= 0 && n0 + 3 < N) {
+                const float4 q = *reinterpret_cast<const float4*>(s + n0);
+                c[0] = pack_key(q.x, (unsigned)(n_offset + n0));
+                c[1] = pack_key(q.y, (unsigned)(n_offset + n0 + 1));
+                c[2] = pack_key(q.z, (unsigned)(n_offset + n0 + 2));
+                c[3] = pack_key(q.w, (unsigned)(n_offset + n0 + 3));
+            } else {
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    const long n = n0 + e;
+                    c[e] = (n >= 0 && n < N) ? pack_key(s[n], (unsigned)(n_offset + n)) : kKeyEmpty;
+                }
+            }
+            wave_knock_out(c, K, wl[wave]);
+            __syncthreads();  // the four wave lists (and, first time round, run[0]) are in LDS
+            if (carry) {
+                if (wave == 0) merge_heads(lane < 4 ? wl[lane] : lane == 4 ? run[cur] : nullptr, K, run[cur ^ 1]);
+            } else {
+                // A fresh list: the five lists hold keys of different hypotheses, all distinct, so a key's place in the
+                // merged list is the number of keys above it -- counted by all 256 lanes at once instead of K more rounds.
+                if (tid < K) run[cur ^ 1][tid] = kKeyEmpty;
+                __syncthreads();
+                for (int e = tid; e < 5 * K; e += kTopkThreads) {
+                    const int l = e / K, j = e - l * K;
+                    const key_t k = l < 4 ? wl[l][j] : run[cur][j];
+                    if (k == kKeyEmpty) continue;
+                    int rank = 0;
+                    for (int i = 0; i < K; ++i)
+                        rank += (wl[0][i] > k) + (wl[1][i] > k) + (wl[2][i] > k) + (wl[3][i] > k) + (run[cur][i] > k);
+                    if (rank < K) run[cur ^ 1][rank] = k;
+                }
+            }
+            cur ^= 1;
+            __syncthreads();
+        }
+    } else {
+        __shared__ key_t ls[kTopkMaxParts * kTopkMaxK];  // up to 63 lists of a pass
+        const key_t* lists = static_cast<const key_t*>(src);
+        for (long g0 = 0; g0 < N; g0 += kTopkMaxParts) {
+            const int ng = (int)(N - g0 < kTopkMaxParts ? N - g0 : kTopkMaxParts);
+            for (int e = tid; e < ng * K; e += kTopkThreads) {
+                const int p = e / K;
+                ls[e] = lists[((g0 + p) * B + b) * K + (e - p * K)];
+            }
+            __syncthreads();
+            if (wave == 0) merge_heads(lane < ng ? ls + lane * K : lane == 63 ? run[cur] : nullptr, K, run[cur ^ 1]);
+            cur ^= 1;
+            __syncthreads();
+        }
+    }
+    __syncthreads();
+    if (tid < K) dst[tid] = run[cur][tid];
+}
+
+// decode + gather for a list, one thread per (b, k): the list counterpart of select_rotation_kernel
+__global__ __launch_bounds__(256) void select_topk_kernel(key_t* __restrict__ keys, int K, const float* __restrict__ R,
+                                                          long r_batch_stride, long n_offset, long N, int B,
+                                                          float* __restrict__ R_out, float* __restrict__ scores_out,
+                                                          long* __restrict__ idx_out, bool reset)
+{
+    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= (long)B * K) return;
+    const int b = (int)(i / K);
+    const key_t k = keys[i];
+    if (reset) keys[i] = kKeyEmpty;
+    const long gidx = (k == kKeyEmpty) ? -1l : key_index(k);
+    if (scores_out) scores_out[i] = (k == kKeyEmpty) ? -INFINITY : key_score(k);
+    if (idx_out) idx_out[i] = gidx;
+    if (R_out) {
+        const long loc = gidx - n_offset;
+        const bool mine = (k != kKeyEmpty) && loc >= 0 && loc < N;  // sharded: the owner rank holds the row, the others zeros
+        const float* r = R + (long)b * r_batch_stride + (mine ? loc : 0) * 9;
+#pragma unroll
+        for (int e = 0; e < 9; ++e) R_out[i * 9 + e] = mine ? r[e] : 0.0f;
+    }
+}
+
+// out[b][k * N2 + n] = R[idx_{b,k}] * D[n]: compose_rotations_kernel for K seeds (its expression, its in-bounds rule)
+__global__ __launch_bounds__(256) void compose_rotations_topk_kernel(const key_t* __restrict__ keys, int K,
+                                                                     const float* __restrict__ R, long r_batch_stride,
+                                                                     long n_offset, long N, const float* __restrict__ D,
+                                                                     long N2, int B, float* __restrict__ out)
+{
+    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= (long)B * K * N2) return;
+    const long bk = i / N2;  // b * K + k
+    const long n = i - bk * N2;
+    const int b = (int)(bk / K);
+    const key_t key = keys[bk];
+    long idx = key_index(key) - n_offset;
+    idx = (key == kKeyEmpty || idx < 0 || idx >= N) ? 0 : idx;  // empty slot / foreign shard: stay in bounds
+    const float* r = R + (long)b * r_batch_stride + idx * 9;
+    const float* d = D + n * 9;
+    float* o = out + i * 9;
+#pragma unroll
+    for (int a = 0; a < 3; ++a)
+#pragma unroll
+        for (int c = 0; c < 3; ++c) o[a * 3 + c] = r[a * 3] * d[c] + r[a * 3 + 1] * d[3 + c] + r[a * 3 + 2] * d[6 + c];
+}
+
+// ---------------------------------------------------------------------------------
 // Haar-uniform rotation hypotheses generated on the device (replaces the host call
 // pytorch3d.transforms.random_rotations(N), test_co3d.py:106 / modules/model.py:184; only the
 // distribution matters -- hypotheses are inputs of the hot path).  Counter-based: rotation n
@@ -769,6 +963,59 @@ hipError_t launch_argmax(const float* scores, int B, int64_t N, int64_t n_offset
     if (bx > cap) bx = cap;
     hipLaunchKernelGGL(argmax_kernel, dim3((unsigned)bx, (unsigned)B), dim3(256), 0, stream, scores, B, (long)N,
                        (long)n_offset, reinterpret_cast<key_t*>(best_key));
+    return hipGetLastError();
+}
+
+// partial lists per sample of a top-K launch over N scores: a pure function of N (the workspace is sized by it)
+int topk_parts(int64_t N)
+{
+    const int64_t tiles = (N + 3 + kTopkTile - 1) / kTopkTile;  // + 3: the row may start up to three floats past a 16-byte line
+    return (int)(tiles < kTopkMaxParts ? tiles : kTopkMaxParts);
+}
+
+hipError_t launch_topk_merge(const int64_t* lists, int P, int B, int K, int64_t* keys, bool carry, hipStream_t stream)
+{
+    hipLaunchKernelGGL(topk_kernel<false>, dim3(1, (unsigned)B), dim3(kTopkThreads), 0, stream,
+                       static_cast<const void*>(lists), B, (long)P, 0l, K, reinterpret_cast<key_t*>(keys), carry);
+    return hipGetLastError();
+}
+
+hipError_t launch_topk(const float* scores, int B, int64_t N, int64_t n_offset, int K, int64_t* keys, int64_t* workspace,
+                       bool carry, hipStream_t stream)
+{
+    const int parts = topk_parts(N);
+    if (parts <= 1) {  // one tile: straight into the caller's list
+        hipLaunchKernelGGL(topk_kernel<true>, dim3(1, (unsigned)B), dim3(kTopkThreads), 0, stream,
+                           static_cast<const void*>(scores), B, (long)N, (long)n_offset, K, reinterpret_cast<key_t*>(keys),
+                           carry);
+        return hipGetLastError();
+    }
+    hipLaunchKernelGGL(topk_kernel<true>, dim3((unsigned)parts, (unsigned)B), dim3(kTopkThreads), 0, stream,
+                       static_cast<const void*>(scores), B, (long)N, (long)n_offset, K,
+                       reinterpret_cast<key_t*>(workspace), false);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    return launch_topk_merge(workspace, parts, B, K, keys, carry, stream);
+}
+
+hipError_t launch_select_topk(int64_t* keys, int K, const float* R, int64_t r_batch_stride, int64_t n_offset, int64_t N,
+                              int B, float* R_out, float* scores_out, int64_t* idx_out, bool reset, hipStream_t stream)
+{
+    const long total = (long)B * K;
+    hipLaunchKernelGGL(select_topk_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream,
+                       reinterpret_cast<key_t*>(keys), K, R, (long)r_batch_stride, (long)n_offset, (long)N, B, R_out,
+                       scores_out, reinterpret_cast<long*>(idx_out), reset);
+    return hipGetLastError();
+}
+
+hipError_t launch_compose_rotations_topk(const int64_t* keys, int K, const float* R, int64_t r_batch_stride,
+                                         int64_t n_offset, int64_t N, const float* D, int64_t N2, int B, float* out,
+                                         hipStream_t stream)
+{
+    const long total = (long)B * K * N2;
+    hipLaunchKernelGGL(compose_rotations_topk_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream,
+                       reinterpret_cast<const key_t*>(keys), K, R, (long)r_batch_stride, (long)n_offset, (long)N, D,
+                       (long)N2, B, out);
     return hipGetLastError();
 }
 

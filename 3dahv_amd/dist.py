@@ -43,6 +43,26 @@ def all_reduce_best(key: torch.Tensor, group=None) -> torch.Tensor:
     return key
 
 
+def all_gather_topk(keys: torch.Tensor, group=None, merge_fn: Optional[Callable] = None, force: bool = False) -> torch.Tensor:
+    """Global K-best list from per-rank lists ``keys (B,K)`` (packed keys, descending, EMPTY-padded: ``ops.topk``): ONE
+    all-gather of ``8*B*K`` bytes per rank into ``(world,B,K)`` followed by ``ops.merge_topk`` -- the list counterpart of
+    ``all_reduce_best``.  The result is the same list on every rank and does not depend on how N was cut (the keys carry
+    global indices; a key met twice is kept once).  Under ``nccl`` (= RCCL) both the collective and the merge are
+    capturable.  ``merge_fn`` defaults to the HIP kernel; CPU tests inject their own.  With no process group (or a world
+    of one, unless ``force``) the list is returned as it is."""
+    inited = dist.is_available() and dist.is_initialized()
+    world = dist.get_world_size(group) if inited else 1
+    if not inited or (world == 1 and not force):
+        return keys
+    if merge_fn is None:
+        from . import ops
+        merge_fn = ops.merge_topk
+    lists = torch.empty((world,) + tuple(keys.shape), dtype=keys.dtype, device=keys.device)
+    # the concatenated form (world*B, K): what every backend accepts (gloo refuses the stacked shape)
+    dist.all_gather_into_tensor(lists.view((-1,) + tuple(keys.shape[1:])), keys.contiguous(), group=group)
+    return merge_fn(lists)
+
+
 # ---- host-side key codec (numpy): used by host logic and CPU tests ------------------
 
 def pack_keys_host(scores: np.ndarray, idx: np.ndarray) -> np.ndarray:

@@ -527,6 +527,145 @@ def compose_rotations(best_key: torch.Tensor, R: torch.Tensor, D: torch.Tensor, 
     return out
 
 
+# ---- K best hypotheses -------------------------------------------------------------------------------
+# A list is (B, K) int64 packed keys in descending order, distinct, padded with AHV_KEY_EMPTY: the first K entries of
+# torch.sort(scores, dim=1, descending=True, stable=True) -- NOT torch.topk's order, which leaves ties unspecified.
+
+# (device, B, N, K) -> workspace: static buffers, so that a captured graph replays on the same memory.  One buffer per shape,
+# shared by every caller: calls of one shape on DIFFERENT streams at the same time would race on it between the two launches
+# (issue them on one stream), and a buffer stays for every distinct N that was ever used (8 * min(N/1024, 63) * B * K bytes).
+_TOPK_WS = {}
+
+
+def _topk_k(k) -> int:
+    k = int(k)
+    if not 1 <= k <= _lib.AHV_TOPK_MAX_K:
+        raise RuntimeError("K = %d outside 1..%d" % (k, _lib.AHV_TOPK_MAX_K))
+    return k
+
+
+def _topk_list(keys: torch.Tensor, what: str = "keys"):
+    if keys.dim() != 2 or keys.dtype != torch.int64:
+        raise RuntimeError("%s must be a (B,K) int64 tensor" % what)
+    if not keys.is_cuda:
+        raise RuntimeError("3dahv_amd ops run on the GPU only (no CPU fallback); got a tensor on %s" % keys.device)
+    if not keys.is_contiguous():
+        raise RuntimeError("%s must be contiguous" % what)
+    return keys.shape[0], _topk_k(keys.shape[1])
+
+
+@torch.no_grad()
+def topk(scores: torch.Tensor, k: int, n_offset: int = 0, keys: torch.Tensor | None = None, reset: bool | None = None):
+    """The K best of ``scores (B,N)`` as packed keys ``(B,K)`` (``ahv_topk_f32``).  ``keys`` given: merge into that list
+    (chunked N, shards with their ``n_offset``) unless ``reset``; else a fresh list is returned.  ``keys[:, 0]`` is the
+    arg-max key.  Decode with ``select_topk``."""
+    if scores.dim() != 2:
+        raise RuntimeError("scores must be (B,N)")
+    k = _topk_k(k)
+    dev = _need_gpu(scores)
+    B, N = scores.shape
+    if keys is None:
+        keys = torch.empty((B, k), dtype=torch.int64, device=dev)
+        reset = True
+    elif _topk_list(keys) != (B, k) or keys.device != dev:
+        raise RuntimeError("keys must be a (B,K) = %s int64 tensor on %s" % ((B, k), dev))
+    s = scores.detach().contiguous()
+    nbytes = _lib.load().ahv_topk_workspace_bytes(B, N, k)
+    ws = None
+    if nbytes:
+        ws = _TOPK_WS.get((dev, B, N, k))
+        if ws is None:
+            ws = _TOPK_WS[(dev, B, N, k)] = torch.empty((nbytes // 8,), dtype=torch.int64, device=dev)
+    _call(dev, "ahv_topk_f32", s.data_ptr(), B, N, n_offset, k, keys.data_ptr(), ws.data_ptr() if ws is not None else None,
+          nbytes, _lib.AHV_TOPK_RESET_LIST if reset else 0)
+    return keys
+
+
+@torch.no_grad()
+def merge_topk(lists: torch.Tensor, keys: torch.Tensor | None = None, reset: bool | None = None):
+    """``lists (P,B,K)`` -> one list ``(B,K)`` (``ahv_topk_merge_keys``): what follows an all-gather of per-rank lists.
+    Duplicate keys are kept once, so a list merged twice changes nothing.  ``keys`` given: merge into it unless ``reset``."""
+    if lists.dim() != 3 or lists.dtype != torch.int64:
+        raise RuntimeError("lists must be a (P,B,K) int64 tensor")
+    if not lists.is_cuda:
+        raise RuntimeError("3dahv_amd ops run on the GPU only (no CPU fallback); got a tensor on %s" % lists.device)
+    P, B, k = lists.shape
+    k = _topk_k(k)
+    if keys is None:
+        keys = torch.empty((B, k), dtype=torch.int64, device=lists.device)
+        reset = True
+    elif _topk_list(keys) != (B, k) or keys.device != lists.device:
+        raise RuntimeError("keys must be a (B,K) = %s int64 tensor on %s" % ((B, k), lists.device))
+    ls = lists.contiguous()
+    _call(ls.device, "ahv_topk_merge_keys", ls.data_ptr(), P, B, k, keys.data_ptr(), _lib.AHV_TOPK_RESET_LIST if reset else 0)
+    return keys
+
+
+@torch.no_grad()
+def select_topk(keys: torch.Tensor, R: torch.Tensor, n_offset: int = 0, reset_keys: bool = False):
+    """``(scores (B,K), idx (B,K) global int64, R (B,K,3,3))`` of a list in ONE launch (``ahv_select_topk_f32``); an empty
+    slot gives -inf, -1 and a zero row; so does (for the row) a slot owned by another shard.  ``reset_keys``: hand the
+    list back empty."""
+    B, k = _topk_list(keys)
+    _need_gpu(R)
+    if R.device != keys.device:
+        raise RuntimeError("Expected all tensors to be on the same device, found %s and %s" % (keys.device, R.device))
+    N, rstride = _rot_layout(R, B)
+    Rc = R.detach().contiguous()
+    dev = Rc.device
+    score = torch.empty((B, k), dtype=torch.float32, device=dev)
+    idx = torch.empty((B, k), dtype=torch.int64, device=dev)
+    R_out = torch.empty((B, k, 3, 3), dtype=torch.float32, device=dev)
+    _call(dev, "ahv_select_topk_f32", keys.data_ptr(), k, Rc.data_ptr(), rstride, n_offset, N, B, R_out.data_ptr(),
+          score.data_ptr(), idx.data_ptr(), _lib.AHV_SELECT_RESET_KEY if reset_keys else 0)
+    return score, idx, R_out
+
+
+@torch.no_grad()
+def compose_rotations_topk(keys: torch.Tensor, R: torch.Tensor, D: torch.Tensor, n_offset: int = 0,
+                           out: torch.Tensor | None = None) -> torch.Tensor:
+    """Refinement hypotheses around K seeds: ``out[b, k * N2 + n] = R[idx_{b,k}] @ D[n]`` -> (B, K*N2, 3, 3)
+    (``ahv_compose_rotations_topk_f32``); at K = 1 it is ``compose_rotations`` bit for bit."""
+    B, k = _topk_list(keys)
+    _need_gpu(R, D)
+    if R.device != keys.device:
+        raise RuntimeError("Expected all tensors to be on the same device, found %s and %s" % (keys.device, R.device))
+    N, rstride = _rot_layout(R, B)
+    if D.dim() != 3 or tuple(D.shape[1:]) != (3, 3):
+        raise RuntimeError("D must be (N2,3,3)")
+    N2 = D.shape[0]
+    Rc, Dc = R.detach().contiguous(), D.detach().contiguous()
+    if out is None:
+        out = torch.empty((B, k * N2, 3, 3), dtype=torch.float32, device=Rc.device)
+    elif tuple(out.shape) != (B, k * N2, 3, 3) or not out.is_contiguous():
+        raise RuntimeError("out must be a contiguous (B, K*N2, 3, 3) tensor")
+    _call(out.device, "ahv_compose_rotations_topk_f32", keys.data_ptr(), k, Rc.data_ptr(), rstride, n_offset, N,
+          Dc.data_ptr(), N2, B, out.data_ptr())
+    return out
+
+
+def score_hypotheses_topk(vol_src: torch.Tensor, feat_tgt: torch.Tensor, R: torch.Tensor, W1: torch.Tensor, W2: torch.Tensor,
+                          b2: torch.Tensor, k: int, n_offset: int = 0, keys: torch.Tensor | None = None,
+                          reset: bool | None = None, **kw):
+    """``score_hypotheses`` with the scores kept, followed by ``topk`` on them: returns
+    ``(scores (B,N), best_key (B,), keys (B,K))``; ``best_key`` is the fused launch's arg-max key and equals ``keys[:, 0]``
+    for a fresh list.  ``keys`` / ``reset`` as in ``topk``; other keywords go to ``score_hypotheses``."""
+    k = _topk_k(k)
+    scores, best_key = score_hypotheses(vol_src, feat_tgt, R, W1, W2, b2, n_offset=n_offset, want_scores=True, **kw)
+    return scores, best_key, topk(scores, k, n_offset=n_offset, keys=keys, reset=reset)
+
+
+def verify_pair_topk(vol_src: torch.Tensor, vol_tgt: torch.Tensor, R: torch.Tensor, W1: torch.Tensor, W2: torch.Tensor,
+                     b2: torch.Tensor, k: int, n_offset: int = 0, keys: torch.Tensor | None = None,
+                     reset: bool | None = None, want_feat_tgt: bool = False, **kw):
+    """``verify_pair`` with the scores kept, followed by ``topk`` on them: returns ``(scores (B,N), best_key (B,),
+    keys (B,K))`` and, with ``want_feat_tgt``, the target features as fourth element."""
+    k = _topk_k(k)
+    r = verify_pair(vol_src, vol_tgt, R, W1, W2, b2, n_offset=n_offset, want_scores=True, want_feat_tgt=want_feat_tgt, **kw)
+    out = (r[0], r[1], topk(r[0], k, n_offset=n_offset, keys=keys, reset=reset))
+    return out + (r[2],) if want_feat_tgt else out
+
+
 class CoarseToFineState:
     """Scratch of ``coarse_to_fine`` for B samples on one device: the two packed keys (EMPTY between steps), the meeting
     point's counters (zero between steps) and the launch's error word.  One per caller and stream; reusing it keeps the

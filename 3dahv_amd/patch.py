@@ -88,13 +88,16 @@ def _hip_forward_2d3d(self, img_feat_src, img_feat_tgt, random_mask=True, mask_r
     return hip_forward_2d3d(self, img_feat_src, img_feat_tgt)   # runs under no_grad; fresh tensors, no graph
 
 
-def verify_hypotheses(self, img_feat_src, img_feat_tgt, proposals, want_scores=False, **kw):
+def verify_hypotheses(self, img_feat_src, img_feat_tgt, proposals, want_scores=False, topk=None, **kw):
     """INTEGRATION.md option B as a method of the (reference or mirror) ``Feature_Aligner`` -- ``install()`` adds it to the
     reference's class: lines 137-145 of test_co3d.py as ONE launch (``ops.verify_pair`` with this module's head weights).
     Returns ``(scores | None, packed keys)``; ``ops.select_rotation(keys, proposals)`` decodes them (lines 145-146).
     An inference call by the same rule as the patched callables (``_inference_call``: no_grad, or the module in eval mode --
     the reference scripts never enter no_grad, and ``ops.verify_pair`` on weights that require grad is refused because the
-    fused launch has no autograd edge).  A module in training mode with autograd recording is refused loudly here too."""
+    fused launch has no autograd edge).  A module in training mode with autograd recording is refused loudly here too.
+    ``topk=K``: additionally the K best hypotheses as a list of packed keys ``(B,K)`` (``ops.verify_pair_topk``; decode with
+    ``ops.select_topk(klist, proposals)``) -- the return value is then ``(scores | None, packed keys, klist)``; ``None``
+    (the default) returns what it always returned."""
     import torch
     c1, c2 = self.feature_embedding_2d[0], self.feature_embedding_2d[2]
     if not _inference_call(self):
@@ -102,6 +105,10 @@ def verify_hypotheses(self, img_feat_src, img_feat_tgt, proposals, want_scores=F
                            "training mode with autograd recording -- use rotate_volume / forward_3d2d (differentiable) or "
                            "ops.score_hypotheses_autograd for the loss")
     with torch.no_grad():
+        if topk is not None:
+            scores, key, klist = ops.verify_pair_topk(img_feat_src.detach(), img_feat_tgt.detach(), proposals, c1.weight,
+                                                      c2.weight, c2.bias, topk, **kw)[:3]
+            return (scores if want_scores else None), key, klist
         return ops.verify_pair(img_feat_src.detach(), img_feat_tgt.detach(), proposals, c1.weight, c2.weight, c2.bias,
                                want_scores=want_scores, **kw)[:2]
 

@@ -26,7 +26,7 @@ import torch
 import torch.distributed as dist
 
 from . import ops
-from .dist import KEY_EMPTY, shard_range
+from .dist import KEY_EMPTY, all_gather_topk, shard_range
 from .rotations import refine_rotations
 
 
@@ -46,6 +46,16 @@ class CoarseToFine:
     Scores do not depend on how the hypothesis sets are split over ranks, bit for bit (a team's score is a lone wave's);
     ``no_teams`` is the scheduling knob of ``ops.score_hypotheses``.  ``check()`` (host sync) raises if a one-launch step
     had to give its meeting point up -- such a step's outputs are poisoned (NaN, -1), never plausible.
+    ``seeds=K > 1`` (multi-seed refinement): stage 2 refines around the K best coarse hypotheses instead of the winner alone,
+    so a coarse winner in the wrong basin no longer decides the step.  The coarse stage keeps its scores, ``topk`` builds this
+    rank's K-list, ``dist.all_gather_topk`` (an all-gather of 8*B*K bytes per rank + ``merge_topk``) takes the place of the
+    coarse key all-reduce, every rank composes all K*N2 refinements (``compose_rotations_topk``) and scores its contiguous
+    slice of that axis; the fine key all-reduce and ``select_rotation`` are today's.  Still two collectives per step.  The
+    fine index lies in ``[0, K*N2)``: seed ``idx // N2`` (rank in the coarse list), refinement ``idx % N2``; the coarse
+    score / index returned are the list's first entry (the arg-max) and ``self.last["coarse_topk"] = (scores, idx)``, both
+    (B,K).  Seed 0's refinements are the single-seed step's, score for score, so the fine score never falls below it.
+    ``seeds=1`` is the step described above, unchanged.  The one-launch kernel is not extended: ``fused`` with
+    ``seeds > 1`` raises.
     ``use_graph``: None = captured when the step carries collectives, eager otherwise (see __init__); ``run_many`` replays
     several steps from one graph."""
 
@@ -53,7 +63,7 @@ class CoarseToFine:
                  D: Optional[torch.Tensor] = None, n_fine: int = 1000, max_angle_deg: float = 10.0,
                  batch: int = 1, use_graph: Optional[bool] = None, group=None, seed: int = 0, backend=None,
                  want_scores: bool = False, force_collectives: bool = False, no_teams: bool = False,
-                 fused: Optional[bool] = None):
+                 fused: Optional[bool] = None, seeds: int = 1):
         dev = R_coarse.device
         self.ops = ops if backend is None else backend
         self.W1, self.W2, self.b2 = W1, W2, b2
@@ -71,8 +81,16 @@ class CoarseToFine:
         self.rank = dist.get_rank(group) if inited else 0
         # a 1-rank RCCL group with force_collectives exercises "collectives inside the captured graph" on one GPU
         self.collectives = self.world > 1 or (force_collectives and inited)
+        self.seeds = int(seeds)
+        if not 1 <= self.seeds <= 64:
+            raise RuntimeError("seeds = %d outside 1..64" % self.seeds)
+        if self.seeds > self.R_coarse.shape[-3]:
+            raise RuntimeError("seeds = %d exceeds the %d coarse hypotheses" % (self.seeds, self.R_coarse.shape[-3]))
+        if self.seeds > 1 and fused:
+            raise RuntimeError("the one-launch step (fused=True) refines around ONE seed; seeds = %d needs fused=False"
+                               % self.seeds)
         self.c_lo, self.c_hi = shard_range(self.R_coarse.shape[0], self.rank, self.world)
-        self.f_lo, self.f_hi = shard_range(self.D.shape[0], self.rank, self.world)
+        self.f_lo, self.f_hi = shard_range(self.seeds * self.D.shape[0], self.rank, self.world)
         capturable = (not self.collectives) or (inited and dist.get_backend(group) == "nccl")
         # Default (use_graph=None), from the kernel-trace timelines of profiles/r06_graph_timeline.txt: a hipGraphLaunch idles
         # the device ~9 us between two replays, plain launches none -- so WITHOUT collectives a single step is issued eagerly
@@ -84,7 +102,8 @@ class CoarseToFine:
         self.use_graph = bool(use_graph and dev.type == "cuda" and capturable)
         # the two keys live with the object: every step's select hands them back empty
         self._keys = [torch.full((batch,), KEY_EMPTY, dtype=torch.int64, device=dev) for _ in range(2)]
-        self._R_fine = torch.empty((batch, self.D.shape[0], 3, 3), dtype=torch.float32, device=dev)
+        self._R_fine = torch.empty((batch, self.seeds * self.D.shape[0], 3, 3), dtype=torch.float32, device=dev)
+        self._klist = (torch.full((batch, self.seeds), KEY_EMPTY, dtype=torch.int64, device=dev) if self.seeds > 1 else None)
         self._graph = None
         self._static = None
         can_fuse = backend is None and not self.collectives and self.world == 1 and dev.type == "cuda"
@@ -119,6 +138,8 @@ class CoarseToFine:
             # (the refinement set is never materialised here: R_fine stays None)
             self.last = {"coarse_scores": r.get("coarse_scores"), "fine_scores": r.get("fine_scores"), "R_fine": None}
             return r["fine_score"], r["fine_idx"], r["R_pred"], r["coarse_score"], r["coarse_idx"]
+        if self.seeds > 1:
+            return self._step_seeds(vol_src, vol_tgt)
         key1, key2 = self._keys
         kw = {"no_teams": True} if self.no_teams else {}
         Rc = self.R_coarse[self.c_lo:self.c_hi]
@@ -139,6 +160,30 @@ class CoarseToFine:
         # this rank's slices of the two score sets and of the refinement set (None unless want_scores)
         self.last = {"coarse_scores": s1, "fine_scores": s2, "R_fine": R_fine if self.want_scores else None}
         return score, idx, R_pred, coarse_score, coarse_idx
+
+    def _step_seeds(self, vol_src, vol_tgt):
+        """The step with ``seeds = K > 1``: stage 2 scores the K*N2 refinements of the K best coarse hypotheses."""
+        o = self.ops
+        key2 = self._keys[1]
+        kw = {"no_teams": True} if self.no_teams else {}
+        Rc = self.R_coarse[self.c_lo:self.c_hi]
+        # the coarse scores are kept: the K-list is selected from them (the scorer's own arg-max key is its first entry)
+        s1, _, f_tgt = o.verify_pair(vol_src, vol_tgt, Rc, self.W1, self.W2, self.b2, n_offset=self.c_lo, want_scores=True,
+                                     want_feat_tgt=True, **kw)
+        klist = o.topk(s1, self.seeds, n_offset=self.c_lo, keys=self._klist, reset=True)
+        if self.collectives:  # 8*B*K bytes per rank, then the merge: the same list on every rank, however N1 was cut
+            klist = all_gather_topk(klist, group=self.group, merge_fn=o.merge_topk, force=True)
+        # every rank holds the whole coarse set and D: all K*N2 refinements are composed locally, a slice of them scored
+        R_fine_all = o.compose_rotations_topk(klist, self.R_coarse, self.D, out=self._R_fine)
+        R_fine = R_fine_all if self.world == 1 else R_fine_all[:, self.f_lo:self.f_hi]
+        s2, _ = o.score_hypotheses(vol_src, f_tgt, R_fine, self.W1, self.W2, self.b2, n_offset=self.f_lo,
+                                   want_scores=self.want_scores, best_key=key2, reset_best=False, **kw)
+        self._merge(key2)
+        score, idx, R_pred = o.select_rotation(key2, R_fine_all, n_offset=0, reset_key=True)
+        top_scores, top_idx, _ = o.select_topk(klist, self.R_coarse, n_offset=0)
+        self.last = {"coarse_scores": s1 if self.want_scores else None, "fine_scores": s2,
+                     "R_fine": R_fine if self.want_scores else None, "coarse_topk": (top_scores, top_idx)}
+        return score, idx, R_pred, top_scores[:, 0], top_idx[:, 0]
 
     def check(self):
         """Host sync.  Raises if a one-launch step abandoned its device-wide meeting point (another kernel held compute units
