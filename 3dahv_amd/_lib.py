@@ -22,6 +22,7 @@ AHV_SELECT_RESET_KEY = 1
 AHV_KEY_EMPTY = -(1 << 63)
 AHV_TOPK_MAX_K = 64
 AHV_TOPK_RESET_LIST = 1
+AHV_SO3_MAX_LADDER = 8
 
 _vp = ctypes.c_void_p
 _i64 = ctypes.c_int64
@@ -81,6 +82,11 @@ SIGNATURES["ahv_topk_f32"] = (_int, [_vp, _int, _i64, _i64, _int, _vp, _vp, ctyp
 SIGNATURES["ahv_topk_merge_keys"] = (_int, [_vp, _int, _int, _int, _vp, _u32, _vp])
 SIGNATURES["ahv_select_topk_f32"] = (_int, [_vp, _int, _vp, _i64, _i64, _i64, _int, _vp, _vp, _vp, _u32, _vp])
 SIGNATURES["ahv_compose_rotations_topk_f32"] = (_int, [_vp, _int, _vp, _i64, _i64, _i64, _vp, _i64, _int, _vp, _vp])
+SIGNATURES["ahv_score_rotation_grad_workspace_bytes"] = (ctypes.c_size_t, [_int, _i64])
+SIGNATURES["ahv_score_rotation_grad_f32"] = (_int, [_vp, _vp, _vp, _i64, _vp, _vp, _vp, _int, _i64, _vp, _vp, ctypes.c_size_t,
+                                                    _vp, _vp])
+SIGNATURES["ahv_so3_ascent_candidates_f32"] = (_int, [_vp, _vp, _vp, _vp, _int, _int, _int, _vp, _vp])
+SIGNATURES["ahv_so3_ascent_select_f32"] = (_int, [_vp, _vp, _vp, _int, _int, _int, _vp, _vp, _vp, _vp])
 
 # measurement / developer entry points (include/ahv_diag.h): not part of the drop-in boundary
 DIAG_SIGNATURES = {

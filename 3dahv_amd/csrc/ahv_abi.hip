@@ -38,6 +38,12 @@ hipError_t launch_score_backward(const float*, const float*, const float*, int64
                                  const float*, int, int64_t, const float*, float*, float*, float*, float*, float*,
                                  float*, float*, int, hipStream_t, bool);
 hipError_t launch_zero_fill(void* const* ptrs, const size_t* bytes, int count, hipStream_t stream);
+hipError_t launch_score_rotation_grad(const float*, const float*, const float*, int64_t, const float*, const float*,
+                                      const float*, int, int64_t, const float*, float*, float*, int, hipStream_t);
+hipError_t launch_so3_ascent_candidates(const float*, const float*, const float*, const float*, int, int, int, float*,
+                                        hipStream_t);
+hipError_t launch_so3_ascent_select(const float*, const float*, const float*, int, int, int, float*, float*, float*,
+                                    hipStream_t);
 size_t transformer_workspace_floats(int B);
 int transformer_blocks(const ahv_block_weights*, int, float*, float*, int, float*, hipStream_t, const char**);
 size_t forward_2d3d_workspace_floats(int B);
@@ -611,6 +617,71 @@ int ahv_compose_rotations_topk_f32(const int64_t* keys, int K, const float* R, i
     hipError_t e = ahv::launch_compose_rotations_topk(keys, K, R, r_batch_stride, n_offset, N, D, N2, B, out,
                                                       static_cast<hipStream_t>(stream));
     if (e != hipSuccess) return hip_fail("compose_rotations_topk: launch", e);
+    return AHV_OK;
+}
+
+// ---- rotation gradient of the score, SO(3) ascent step -------------------------------------------------
+size_t ahv_score_rotation_grad_workspace_bytes(int B, int64_t N)
+{
+    if (B <= 0 || N <= 0) return 0;
+    return sizeof(float) * 2048 * (size_t)B * (size_t)N;   // dL/du of every hypothesis
+}
+
+int ahv_score_rotation_grad_f32(const float* vol_src, const float* feat_tgt, const float* R, int64_t r_batch_stride,
+                                const float* W1, const float* W2, const float* b2, int B, int64_t N,
+                                const float* grad_scores, void* workspace, size_t workspace_bytes, float* grad_R,
+                                void* stream)
+{
+    if (B < 0 || N < 0) return fail(AHV_EINVAL, "score_rotation_grad: negative size (B=%d, N=%lld)", B, (long long)N);
+    if (B == 0 || N == 0) return AHV_OK;
+    if (!vol_src || !feat_tgt || !R || !W1 || !W2 || !b2 || !grad_R || !workspace)
+        return fail(AHV_EINVAL, "score_rotation_grad: null pointer");
+    if (r_batch_stride != 0 && r_batch_stride != N * 9)
+        return fail(AHV_EINVAL, "score_rotation_grad: r_batch_stride %lld must be 0 or N*9", (long long)r_batch_stride);
+    if (workspace_bytes < ahv_score_rotation_grad_workspace_bytes(B, N))
+        return fail(AHV_EINVAL, "score_rotation_grad: workspace of %zu bytes, need %zu (ahv_score_rotation_grad_workspace_bytes)",
+                    workspace_bytes, ahv_score_rotation_grad_workspace_bytes(B, N));
+    if (reinterpret_cast<uintptr_t>(workspace) & 15)
+        return fail(AHV_EINVAL, "score_rotation_grad: workspace must be 16-byte aligned");
+    const int cu = cu_count();
+    if (cu <= 0) return fail(AHV_EDEVICE, "score_rotation_grad: no usable HIP device");
+    hipError_t e = ahv::launch_score_rotation_grad(vol_src, feat_tgt, R, r_batch_stride, W1, W2, b2, B, N, grad_scores,
+                                                   static_cast<float*>(workspace), grad_R, cu, static_cast<hipStream_t>(stream));
+    if (e != hipSuccess) return hip_fail("score_rotation_grad: launch", e);
+    return AHV_OK;
+}
+
+static int so3_ascent_sizes(const char* who, int L, int B, int K)
+{
+    if (L < 1 || L > AHV_SO3_MAX_LADDER) return fail(AHV_EINVAL, "%s: L = %d outside 1..%d", who, L, AHV_SO3_MAX_LADDER);
+    if (bad_k(K)) return fail(AHV_EINVAL, "%s: K = %d outside 1..%d", who, K, AHV_TOPK_MAX_K);
+    if (B < 0) return fail(AHV_EINVAL, "%s: negative size", who);
+    if (B > 65535) return fail(AHV_EINVAL, "%s: B > 65535", who);   // B * K stays far inside an int
+    return AHV_OK;
+}
+
+int ahv_so3_ascent_candidates_f32(const float* R_cur, const float* grad_R, const float* theta, const float* ladder, int L,
+                                  int B, int K, float* R_cand, void* stream)
+{
+    if (int rc = so3_ascent_sizes("so3_ascent_candidates", L, B, K)) return rc;
+    if (B == 0) return AHV_OK;
+    if (!R_cur || !grad_R || !theta || !ladder || !R_cand) return fail(AHV_EINVAL, "so3_ascent_candidates: null pointer");
+    hipError_t e = ahv::launch_so3_ascent_candidates(R_cur, grad_R, theta, ladder, L, B, K, R_cand,
+                                                     static_cast<hipStream_t>(stream));
+    if (e != hipSuccess) return hip_fail("so3_ascent_candidates: launch", e);
+    return AHV_OK;
+}
+
+int ahv_so3_ascent_select_f32(const float* R_cand, const float* cand_scores, const float* ladder, int L, int B, int K,
+                              float* R_cur, float* score_cur, float* theta, void* stream)
+{
+    if (int rc = so3_ascent_sizes("so3_ascent_select", L, B, K)) return rc;
+    if (B == 0) return AHV_OK;
+    if (!R_cand || !cand_scores || !ladder || !R_cur || !score_cur || !theta)
+        return fail(AHV_EINVAL, "so3_ascent_select: null pointer");
+    hipError_t e = ahv::launch_so3_ascent_select(R_cand, cand_scores, ladder, L, B, K, R_cur, score_cur, theta,
+                                                 static_cast<hipStream_t>(stream));
+    if (e != hipSuccess) return hip_fail("so3_ascent_select: launch", e);
     return AHV_OK;
 }
 

@@ -1,6 +1,7 @@
 // ahv_backward.hip -- backward of the fused scorer (what Estimator.infoNCE_loss,
 // modules/model_co3d.py:41-61, needs from autograd): given dL/dscore[b][n], the gradients w.r.t. the source
-// volume, the target feature and the head weights.  No gradient flows to the rotations (they are sampled).
+// volume, the target feature and the head weights -- and, as a pass of its own at the end of this file
+// (score_rotation_grad_kernel), w.r.t. the rotations: d score / d R per hypothesis, bitwise reproducible.
 //
 //   scores[b][n] = 1/64 sum_pos <normalize(W2 relu(W1 slabs(rot(V_b, R_n))) + b2)[:, pos], tg_b[:, pos]>
 //
@@ -51,6 +52,10 @@ __device__ __forceinline__ void global_add(float* p, float v)
 // ---------------------------------------------------------------------------------------------------
 // Kernel 1: forward recompute + backward through score / normalise / GEMM2 / ReLU.
 // ---------------------------------------------------------------------------------------------------
+// ACCUM = false (the rotation gradient, ahv_score_rotation_grad_f32): the pass that only leaves du in the workspace -- nothing
+// is summed across hypotheses, no float atomics, so du (and all that follows from it) is a function of the hypothesis alone,
+// bit for bit; grad_scores may then be null (= all ones) and the three gradient pointers are not touched.
+template <bool ACCUM>
 __global__ __launch_bounds__(kBwdThreads, 1) void score_backward_head_kernel(
     const float* __restrict__ vol_src, const float* __restrict__ feat_tgt, const float* __restrict__ R,
     long r_batch_stride, const float* __restrict__ W1, const float* __restrict__ W2, const float* __restrict__ b2,
@@ -137,7 +142,7 @@ __global__ __launch_bounds__(kBwdThreads, 1) void score_backward_head_kernel(
 
             // score = 1/64 sum_pos <v / max(|v|, eps), tg>; F.normalize's clamp passes no gradient to the norm
             // when it is below eps
-            const float g = grad_scores[(long)b * N + h] * (1.0f / 64.0f);
+            const float g = ((!ACCUM && !grad_scores) ? 1.0f : grad_scores[(long)b * N + h]) * (1.0f / 64.0f);
             f32x4 dv[2][4];
 #pragma unroll
             for (int t = 0; t < 4; ++t) {
@@ -160,13 +165,15 @@ __global__ __launch_bounds__(kBwdThreads, 1) void score_backward_head_kernel(
 #pragma unroll
                     for (int r = 0; r < 4; ++r) {
                         dv[m2][t][r] = g * (tg[t][m2][r] * inv - c3 * v[m2][t][r]);
-                        dtg[t][m2][r] += g * inv * v[m2][t][r];
+                        if (ACCUM) dtg[t][m2][r] += g * inv * v[m2][t][r];
                     }
             }
+            if (ACCUM) {
 #pragma unroll
-            for (int m2 = 0; m2 < 2; ++m2)
+                for (int m2 = 0; m2 < 2; ++m2)
 #pragma unroll
-                for (int r = 0; r < 4; ++r) db2p[m2][r] += dv[m2][0][r] + dv[m2][1][r] + dv[m2][2][r] + dv[m2][3][r];
+                    for (int r = 0; r < 4; ++r) db2p[m2][r] += dv[m2][0][r] + dv[m2][1][r] + dv[m2][2][r] + dv[m2][3][r];
+            }
 
             // dr = W2^T dv (accumulator registers of dv are the B operand), du = dr where u > 0
             f32x4 du[2][4];
@@ -191,6 +198,7 @@ __global__ __launch_bounds__(kBwdThreads, 1) void score_backward_head_kernel(
 #pragma unroll
                     for (int r = 0; r < 4; ++r) dst[((t * 2 + m) * 64 + lane) * 4 + r] = acc[m][t][r] > 0.0f ? du[m][t][r] : 0.0f;
 
+            if (!ACCUM) continue;
             // dW2 += dv relu(u)^T: the contraction runs over positions, so both operands go through the
             // wave's LDS image once (dv as A, relu(u) as B).
 #pragma unroll
@@ -223,6 +231,7 @@ __global__ __launch_bounds__(kBwdThreads, 1) void score_backward_head_kernel(
                 }
             wave_lds_fence();
         }
+        if (!ACCUM) continue;
         float* gft = grad_feat_tgt + (long)b * (32 * 64);
 #pragma unroll
         for (int t = 0; t < 4; ++t)
@@ -231,6 +240,7 @@ __global__ __launch_bounds__(kBwdThreads, 1) void score_backward_head_kernel(
 #pragma unroll
                 for (int r = 0; r < 4; ++r) global_add(gft + (16 * m2 + 4 * kq + r) * 64 + 16 * t + n, dtg[t][m2][r]);
     }
+    if (!ACCUM) return;
 #pragma unroll
     for (int mt = 0; mt < 2; ++mt)
 #pragma unroll
@@ -1219,7 +1229,7 @@ hipError_t launch_score_backward(const float* vol_src, const float* feat_tgt, co
                            (long)N, grad_scores, du_ws, grad_feat_tgt, grad_W2, grad_b2);
     }
     else
-        hipLaunchKernelGGL(score_backward_head_kernel, grid, dim3(kBwdThreads), 0, stream, vol_src, feat_tgt, R,
+        hipLaunchKernelGGL(score_backward_head_kernel<true>, grid, dim3(kBwdThreads), 0, stream, vol_src, feat_tgt, R,
                            (long)r_batch_stride, W1, W2, b2, B, (long)N, grad_scores, du_ws, grad_feat_tgt, grad_W2, grad_b2);
     if ((e = hipGetLastError()) != hipSuccess) return e;
     hipLaunchKernelGGL(score_backward_w1_kernel, grid, dim3(kW1Threads), 0, stream, vol_src, R, (long)r_batch_stride,
@@ -1235,6 +1245,203 @@ hipError_t launch_score_backward(const float* vol_src, const float* feat_tgt, co
         if (gxv < 1) gxv = 1;
         hipLaunchKernelGGL(score_backward_volume_rmw_kernel, dim3(gxv, gy), dim3(kRmwThreads), 0, stream, R, (long)r_batch_stride,
                            W1, B, (long)N, du_ws, grad_vol);
+    }
+    return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------------------------------
+// d score / d R (ahv_score_rotation_grad_f32): kernel 2b with its hard part removed.  The head pass (ACCUM = false) leaves du
+// of every hypothesis in the workspace; here a TEAM of four waves -- one workgroup, wave m = channels 4 m .. 4 m + 3, the
+// split and the W1^T fragments of kernel 2b -- forms dX = W1^T du half a volume at a time (rmw_dx_half: 192 fp32 MFMAs per
+// wave and hypothesis) and, instead of scattering it, READS the eight corners of every rotated voxel from the channel-last
+// source image in LDS:
+//   s_corner = <dX[4 m .., p], V[4 m .., corner]>,   t_a(p) = sum_corners s_corner * d w_corner / d i_a,
+//   d score / d R[a][b] = sum_p t_a(p) * 4 p_b        (i_a = 4 q_a + 3.5, q = R p: d i_a / d R[a][b] = 4 p_b)
+// with grid_sampler_3d_backward's conventions: floor(i) is the cell (at an integer coordinate the derivative is
+// V[i + 1] - V[i]) and a corner outside [0, 7]^3 contributes neither value nor derivative.
+// One workgroup per hypothesis at a time, always: the nine sums of a hypothesis are formed by the same four waves in the
+// same order whatever B, N, the grid or the cut into calls are -- lane sums over its 8 voxels (half 0 then half 1, plane
+// order), a xor butterfly inside the wave, (w0 + w1) + (w2 + w3) across the team -- so grad_R is bitwise reproducible,
+// and a launch of a single hypothesis still has four waves (and B * N workgroups spread over the chip).
+// A sample whose volume, or a launch whose head weights, hold a NaN / inf reports NaN for its hypotheses (the project's
+// rule for non-finite inputs, ahv_exact.h), found while the volume is staged; a hypothesis whose R holds one reports NaN too.
+// ---------------------------------------------------------------------------------------------------
+constexpr int kRotGradThreads = 256;
+
+struct RgAxis {
+    float w0, w1;   // value weights of rows j, j + 1 (0 where the row is outside the volume)
+    float d0, d1;   // their derivatives w.r.t. the sample coordinate (-1 / +1, 0 where outside)
+    int o0, o1;     // clamped row index * stride (floats)
+};
+
+__device__ __forceinline__ void rg_axis(float i, int stride, RgAxis& a)
+{
+    i = fminf(fmaxf(i, -2.0f), 9.0f);   // keeps the conversion defined for any R; all corners are outside there anyway
+    const float fl = floorf(i), t = i - fl;
+    const int i0 = (int)fl, i1 = i0 + 1;
+    const bool in0 = (unsigned)i0 < 8u, in1 = (unsigned)i1 < 8u;
+    a.w0 = in0 ? 1.0f - t : 0.0f;
+    a.w1 = in1 ? t : 0.0f;
+    a.d0 = in0 ? -1.0f : 0.0f;
+    a.d1 = in1 ? 1.0f : 0.0f;
+    a.o0 = min(max(i0, 0), 7) * stride;
+    a.o1 = min(max(i1, 0), 7) * stride;
+}
+
+// the lane's four voxels of half volume H: plane al = 0..3 (depth 2 H + (al & 1) + 4 (al >> 1)), y = lane >> 3, x = lane & 7
+template <int H>
+__device__ __forceinline__ void rg_gather_half(float (&sum)[9], const float* xbuf, const float* src_ch, const float* Rm, int lane)
+{
+    const int yb = lane >> 3, xe = lane & 7;
+    const float x4 = (float)xe - 3.5f, y4 = (float)yb - 3.5f;   // 4 * voxel-centre coordinate
+#pragma unroll
+    for (int al = 0; al < 4; ++al) {
+        const float z4 = (float)(2 * H + (al & 1) + 4 * (al >> 1)) - 3.5f;
+        const float* xp = xbuf + al * kXPlane + yb * kXRow + xe * 4;   // 8-byte aligned
+        const f32x2 dlo = *reinterpret_cast<const f32x2*>(xp), dhi = *reinterpret_cast<const f32x2*>(xp + 2);
+        RgAxis ax, ay, az;
+        rg_axis(fmaf(Rm[0], x4, fmaf(Rm[1], y4, fmaf(Rm[2], z4, 3.5f))), kSrcStride, ax);
+        rg_axis(fmaf(Rm[3], x4, fmaf(Rm[4], y4, fmaf(Rm[5], z4, 3.5f))), kSrcRowsY * kSrcStride, ay);
+        rg_axis(fmaf(Rm[6], x4, fmaf(Rm[7], y4, fmaf(Rm[8], z4, 3.5f))), kSrcPlaneRows * kSrcStride, az);
+        float tx = 0.0f, ty = 0.0f, tz = 0.0f;
+#pragma unroll
+        for (int c = 0; c < 8; ++c) {   // corner (dz, dy, dx) = bits (4, 2, 1)
+            const float wx = (c & 1) ? ax.w1 : ax.w0, gx = (c & 1) ? ax.d1 : ax.d0;
+            const float wy = (c & 2) ? ay.w1 : ay.w0, gy = (c & 2) ? ay.d1 : ay.d0;
+            const float wz = (c & 4) ? az.w1 : az.w0, gz = (c & 4) ? az.d1 : az.d0;
+            const int off = ((c & 1) ? ax.o1 : ax.o0) + ((c & 2) ? ay.o1 : ay.o0) + ((c & 4) ? az.o1 : az.o0);
+            const f32x4 v = *reinterpret_cast<const f32x4*>(src_ch + off);
+            float s = fmaf(dhi[1], v[3], fmaf(dhi[0], v[2], fmaf(dlo[1], v[1], dlo[0] * v[0])));
+            s = (gx != 0.0f && gy != 0.0f && gz != 0.0f) ? s : 0.0f;   // outside: the clamped row is not this corner's
+            tx = fmaf(s, gx * (wy * wz), tx);
+            ty = fmaf(s, gy * (wx * wz), ty);
+            tz = fmaf(s, gz * (wx * wy), tz);
+        }
+        sum[0] = fmaf(tx, x4, sum[0]); sum[1] = fmaf(tx, y4, sum[1]); sum[2] = fmaf(tx, z4, sum[2]);
+        sum[3] = fmaf(ty, x4, sum[3]); sum[4] = fmaf(ty, y4, sum[4]); sum[5] = fmaf(ty, z4, sum[5]);
+        sum[6] = fmaf(tz, x4, sum[6]); sum[7] = fmaf(tz, y4, sum[7]); sum[8] = fmaf(tz, z4, sum[8]);
+    }
+}
+
+__global__ __launch_bounds__(kRotGradThreads) void score_rotation_grad_kernel(
+    const float* __restrict__ vol_src, const float* __restrict__ R, long r_batch_stride, const float* __restrict__ W1,
+    const float* __restrict__ W2, const float* __restrict__ b2, int B, long N, const float* __restrict__ du_ws,
+    float* __restrict__ grad_R)
+{
+    __shared__ __attribute__((aligned(16))) float lds_src[kSrcFloats];
+    __shared__ __attribute__((aligned(16))) float lds_x[4 * kXbufWords];   // per wave: dX of its 4 channels, half a volume
+    __shared__ float lds_red[4 * 12];
+    __shared__ unsigned lds_bad[2];   // [0]: a head weight is non-finite, [1]: the staged volume is
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int m = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int kq = lane >> 4, row = lane & 15;
+    float* xbuf = lds_x + m * kXbufWords;
+    const float* src_ch = lds_src + 4 * m;
+    if (tid < 2) lds_bad[tid] = 0u;
+    __syncthreads();
+    {
+        bool bad = false;
+        for (int i = tid; i < 32 * 384; i += kRotGradThreads) bad = bad || __builtin_amdgcn_classf(W1[i], 0x207);
+        for (int i = tid; i < 32 * 32; i += kRotGradThreads) bad = bad || __builtin_amdgcn_classf(W2[i], 0x207);
+        if (tid < 32) bad = bad || __builtin_amdgcn_classf(b2[tid], 0x207);
+        if (bad) lds_bad[0] = 1u;
+    }
+    // W1^T fragments of channels 4 m .. 4 m + 3: see score_backward_volume_rmw_kernel
+    float wx[2][8], wy[2][8], wz[2][8];
+#pragma unroll
+    for (int sp = 0; sp < 8; ++sp) {
+        const float* w = W1 + (4 * sp + kq) * 384;
+#pragma unroll
+        for (int kt = 0; kt < 2; ++kt) {
+            wx[kt][sp] = w[32 * m + 16 * kt + row];
+            wy[kt][sp] = w[128 + 32 * m + 16 * kt + row];
+        }
+#pragma unroll
+        for (int H = 0; H < 2; ++H) wz[H][sp] = w[256 + (4 * m + (row & 3)) * 8 + 2 * H + ((row >> 2) & 1) + 4 * (row >> 3)];
+    }
+    for (int b = blockIdx.y; b < B; b += gridDim.y) {
+        __syncthreads();
+        if (tid == 0) lds_bad[1] = 0u;
+        __syncthreads();
+        {
+            bool bad = false;
+            const float* vol = vol_src + (long)b * (16 * 512);
+            for (int i = tid; i < 16 * 512; i += kRotGradThreads) {
+                const int c = i >> 9, v = i & 511;
+                const float x = vol[i];
+                bad = bad || __builtin_amdgcn_classf(x, 0x207);   // sNaN | qNaN | -inf | +inf
+                lds_src[((v >> 6) * kSrcPlaneRows + ((v >> 3) & 7) * kSrcRowsY + (v & 7)) * kSrcStride + c] = x;
+            }
+            if (bad) lds_bad[1] = 1u;
+        }
+        __syncthreads();
+        const bool poisoned = (lds_bad[0] | lds_bad[1]) != 0u;
+        const float* Rb = R + (long)b * r_batch_stride;
+        for (long h = blockIdx.x; h < N; h += gridDim.x) {
+            float Rm[9];
+#pragma unroll
+            for (int i = 0; i < 9; ++i) Rm[i] = Rb[h * 9 + i];
+            bool bad_r = false;   // a NaN / inf entry of R: autograd's gradient is NaN, the clamp in rg_axis would hide it
+#pragma unroll
+            for (int i = 0; i < 9; ++i) bad_r = bad_r || __builtin_amdgcn_classf(Rm[i], 0x207);
+            DuRegs du;
+            load_du_regs(du, du_ws + ((long)b * N + h) * 2048, lane);
+            float sum[9];
+#pragma unroll
+            for (int i = 0; i < 9; ++i) sum[i] = 0.0f;
+            rmw_dx_half<0>(wx, wy, wz, du, xbuf, lane);
+            wave_lds_fence();
+            rg_gather_half<0>(sum, xbuf, src_ch, Rm, lane);
+            wave_lds_fence();
+            rmw_dx_half<1>(wx, wy, wz, du, xbuf, lane);
+            wave_lds_fence();
+            rg_gather_half<1>(sum, xbuf, src_ch, Rm, lane);
+            wave_lds_fence();
+#pragma unroll
+            for (int i = 0; i < 9; ++i) {
+                float x = sum[i];
+#pragma unroll
+                for (int s = 32; s >= 1; s >>= 1) x += __shfl_xor(x, s, 64);
+                sum[i] = x;
+            }
+            if (lane < 9) {
+                float x = sum[0];
+#pragma unroll
+                for (int i = 1; i < 9; ++i) x = lane == i ? sum[i] : x;
+                lds_red[m * 12 + lane] = x;
+            }
+            __syncthreads();
+            if (tid < 9) {
+                const float x = (lds_red[tid] + lds_red[12 + tid]) + (lds_red[24 + tid] + lds_red[36 + tid]);
+                grad_R[((long)b * N + h) * 9 + tid] = (poisoned || bad_r) ? __builtin_nanf("") : x;
+            }
+            __syncthreads();
+        }
+    }
+}
+
+hipError_t launch_score_rotation_grad(const float* vol_src, const float* feat_tgt, const float* R, int64_t r_batch_stride,
+                                      const float* W1, const float* W2, const float* b2, int B, int64_t N,
+                                      const float* grad_scores, float* du_ws, float* grad_R, int num_cu, hipStream_t stream)
+{
+    if (B == 0 || N == 0) return hipSuccess;
+    const int gy = B < num_cu ? B : num_cu;
+    {   // head pass: one wave per hypothesis; a short list is spread one hypothesis per workgroup over the chip
+        int64_t gx = num_cu / gy;
+        if (gx > N) gx = N;
+        if (gx < 1) gx = 1;
+        hipLaunchKernelGGL(score_backward_head_kernel<false>, dim3((unsigned)gx, gy), dim3(kBwdThreads), 0, stream, vol_src,
+                           feat_tgt, R, (long)r_batch_stride, W1, W2, b2, B, (long)N, grad_scores, du_ws,
+                           (float*)nullptr, (float*)nullptr, (float*)nullptr);
+        hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return e;
+    }
+    {   // a team (= workgroup) per hypothesis, two workgroups fit a CU
+        int64_t gx = (2 * (int64_t)num_cu + gy - 1) / gy;
+        if (gx > N) gx = N;
+        if (gx < 1) gx = 1;
+        hipLaunchKernelGGL(score_rotation_grad_kernel, dim3((unsigned)gx, gy), dim3(kRotGradThreads), 0, stream, vol_src, R,
+                           (long)r_batch_stride, W1, W2, b2, B, (long)N, du_ws, grad_R);
     }
     return hipGetLastError();
 }

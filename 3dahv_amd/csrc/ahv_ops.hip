@@ -1077,4 +1077,103 @@ hipError_t launch_zero_fill(void* const* ptrs, const size_t* bytes, int count, h
     return hipGetLastError();
 }
 
+// ---- SO(3) ascent step (ahv_so3_ascent_candidates_f32 / ahv_so3_ascent_select_f32) ----------------------
+// One thread per seed (b, k); rotations.so3_ascent_candidates / so3_ascent_select state the same rules in torch.
+// Direction: the Riemannian gradient in the body frame, w = vee(1/2 (R^T G - G^T R)); candidate slot 0 is R_cur bit for bit,
+// slot l >= 1 is R_cur exp(ladder[l-1] theta [w / |w|]x) (Rodrigues, 1 - cos a as 2 sin^2(a / 2)); |w| = 0 or a non-finite w:
+// every slot is R_cur.
+__global__ __launch_bounds__(256) void so3_ascent_candidates_kernel(const float* __restrict__ R_cur, const float* __restrict__ grad_R,
+                                                                    const float* __restrict__ theta, const float* __restrict__ ladder,
+                                                                    int L, int seeds, float* __restrict__ R_cand)
+{
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= seeds) return;
+    float R[9], G[9];
+#pragma unroll
+    for (int j = 0; j < 9; ++j) {
+        R[j] = R_cur[(long)i * 9 + j];
+        G[j] = grad_R[(long)i * 9 + j];
+    }
+    float A[9];   // R^T G
+#pragma unroll
+    for (int r = 0; r < 3; ++r)
+#pragma unroll
+        for (int c = 0; c < 3; ++c) A[3 * r + c] = R[r] * G[c] + R[3 + r] * G[3 + c] + R[6 + r] * G[6 + c];
+    const float wx = 0.5f * (A[7] - A[5]), wy = 0.5f * (A[2] - A[6]), wz = 0.5f * (A[3] - A[1]);
+    const float nrm = sqrtf(wx * wx + wy * wy + wz * wz);
+    const bool move = nrm > 0.0f && nrm < __builtin_inff();   // false for NaN
+    const float inv = move ? 1.0f / nrm : 0.0f;
+    const float nx = wx * inv, ny = wy * inv, nz = wz * inv;
+    const float th = theta[i];
+    float* out = R_cand + (long)i * (L + 1) * 9;
+#pragma unroll
+    for (int j = 0; j < 9; ++j) out[j] = R[j];
+    for (int l = 1; l <= L; ++l) {
+        float* o = out + l * 9;
+        if (!move) {
+#pragma unroll
+            for (int j = 0; j < 9; ++j) o[j] = R[j];
+            continue;
+        }
+        const float a = ladder[l - 1] * th;
+        const float sn = sinf(a), sh = sinf(0.5f * a), c1 = 2.0f * sh * sh;
+        // E = I + sin a K + (1 - cos a) (n n^T - I), K = [n]x
+        const float E[9] = {1.0f + c1 * (nx * nx - 1.0f), c1 * nx * ny - sn * nz, c1 * nx * nz + sn * ny,
+                            c1 * nx * ny + sn * nz, 1.0f + c1 * (ny * ny - 1.0f), c1 * ny * nz - sn * nx,
+                            c1 * nx * nz - sn * ny, c1 * ny * nz + sn * nx, 1.0f + c1 * (nz * nz - 1.0f)};
+#pragma unroll
+        for (int r = 0; r < 3; ++r)
+#pragma unroll
+            for (int c = 0; c < 3; ++c) o[3 * r + c] = R[3 * r] * E[c] + R[3 * r + 1] * E[3 + c] + R[3 * r + 2] * E[6 + c];
+    }
+}
+
+// A candidate replaces the incumbent only if its score is strictly greater (false for NaN), slots scanned in order: a seed's
+// score never decreases, slot 0 (R_cur itself) wins a tie.  theta <- ladder[l-1] theta for the accepted slot, theta min(ladder)
+// when slot 0 stayed.
+__global__ __launch_bounds__(256) void so3_ascent_select_kernel(const float* __restrict__ R_cand, const float* __restrict__ cand_scores,
+                                                                const float* __restrict__ ladder, int L, int seeds,
+                                                                float* __restrict__ R_cur, float* __restrict__ score_cur,
+                                                                float* __restrict__ theta)
+{
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= seeds) return;
+    const float* sc = cand_scores + (long)i * (L + 1);
+    float best = sc[0], lmin = ladder[0];
+    int slot = 0;
+    for (int l = 1; l <= L; ++l) {
+        const float s = sc[l];
+        if (s > best) {
+            best = s;
+            slot = l;
+        }
+        lmin = fminf(lmin, ladder[l - 1]);
+    }
+    const float* src = R_cand + ((long)i * (L + 1) + slot) * 9;
+#pragma unroll
+    for (int j = 0; j < 9; ++j) R_cur[(long)i * 9 + j] = src[j];
+    score_cur[i] = best;
+    theta[i] = theta[i] * (slot ? ladder[slot - 1] : lmin);
+}
+
+hipError_t launch_so3_ascent_candidates(const float* R_cur, const float* grad_R, const float* theta, const float* ladder, int L,
+                                        int B, int K, float* R_cand, hipStream_t stream)
+{
+    const int seeds = B * K;
+    if (seeds == 0) return hipSuccess;
+    hipLaunchKernelGGL(so3_ascent_candidates_kernel, dim3((seeds + 255) / 256), dim3(256), 0, stream, R_cur, grad_R, theta,
+                       ladder, L, seeds, R_cand);
+    return hipGetLastError();
+}
+
+hipError_t launch_so3_ascent_select(const float* R_cand, const float* cand_scores, const float* ladder, int L, int B, int K,
+                                    float* R_cur, float* score_cur, float* theta, hipStream_t stream)
+{
+    const int seeds = B * K;
+    if (seeds == 0) return hipSuccess;
+    hipLaunchKernelGGL(so3_ascent_select_kernel, dim3((seeds + 255) / 256), dim3(256), 0, stream, R_cand, cand_scores, ladder,
+                       L, seeds, R_cur, score_cur, theta);
+    return hipGetLastError();
+}
+
 }  // namespace ahv

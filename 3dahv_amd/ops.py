@@ -16,6 +16,7 @@ to torch's current stream.  The plain ops carry no autograd graph; the ``*_autog
 from __future__ import annotations
 
 import contextvars
+import math
 
 import torch
 
@@ -96,12 +97,14 @@ def rotate_volume(volume: torch.Tensor, rotation_matrix: torch.Tensor, padding_m
     reference passes): it is read once, never materialised.  Differentiable w.r.t. ``volume`` like the
     reference's (utils.py:113-131; infoNCE_loss back-propagates through it, modules/model_co3d.py:49-54): when
     autograd is recording and ``volume`` requires grad the call goes through ``_RotateVolumeFn`` (HIP forward, HIP
-    adjoint).  A rotation matrix that requires grad is refused loudly (the reference samples its rotations).
+    adjoint).  A rotation matrix that requires grad is refused loudly: the rotation gradient exists on the fused path
+    (``score_hypotheses`` / ``score_rotation_grad``), not for the materialised volumes of this op.
     """
     if torch.is_grad_enabled():
         if rotation_matrix.requires_grad:
-            raise NotImplementedError("rotate_volume: no gradient w.r.t. rotation_matrix is implemented (the "
-                                      "reference samples its rotations); detach it")
+            raise NotImplementedError("rotate_volume: no gradient w.r.t. rotation_matrix is implemented for the op-level "
+                                      "rotation (32 KB materialised per hypothesis); detach it, or score with "
+                                      "score_hypotheses, whose autograd edge carries d score / d R")
         if volume.requires_grad:
             return _RotateVolumeFn.apply(volume, rotation_matrix)
     return _rotate_volume_nograd(volume, rotation_matrix, padding_mode)
@@ -217,7 +220,7 @@ def score_hypotheses(vol_src: torch.Tensor, feat_tgt: torch.Tensor, R: torch.Ten
     ``score_hypotheses_autograd`` (HIP backward) -- like the reference's op sequence, nothing is silently detached.
     """
     if (want_scores and clock_stamps is None and torch.is_grad_enabled()
-            and any(t.requires_grad for t in (vol_src, feat_tgt, W1, W2, b2))):
+            and any(t.requires_grad for t in (vol_src, feat_tgt, R, W1, W2, b2))):
         return _ScoreFn.apply(vol_src, feat_tgt, R, W1, W2, b2, n_offset, best_key, reset_best, split_f16)
     with torch.no_grad():
         return _score_hypotheses_nograd(vol_src, feat_tgt, R, W1, W2, b2, n_offset, want_scores, best_key, reset_best,
@@ -249,7 +252,7 @@ def verify_pair(vol_src: torch.Tensor, vol_tgt: torch.Tensor, R: torch.Tensor, W
     Inference only (no autograd edge): with autograd recording and an input that requires grad it REFUSES (the check runs
     before the no_grad block -- as a decorator the block hid the recording state from the check, round 4) -- use
     ``forward_3d2d`` + ``score_hypotheses``, which carry the HIP backward."""
-    _refuse_grad("verify_pair", vol_src, vol_tgt, W1, W2, b2)
+    _refuse_grad("verify_pair", vol_src, vol_tgt, R, W1, W2, b2)
     if vol_tgt.dim() != 5 or tuple(vol_tgt.shape) != tuple(vol_src.shape):
         raise RuntimeError("vol_tgt must have vol_src's shape (B,16,8,8,8), got %s" % (tuple(vol_tgt.shape),))
     split = bool(_SPLIT_F16.get() if split_f16 is None else split_f16)
@@ -341,7 +344,8 @@ def score_hypotheses_train(vol_src: torch.Tensor, feat_tgt: torch.Tensor, R: tor
 def score_hypotheses_backward(vol_src: torch.Tensor, feat_tgt: torch.Tensor, R: torch.Tensor, W1: torch.Tensor,
                               W2: torch.Tensor, b2: torch.Tensor, grad_scores: torch.Tensor, workspace: torch.Tensor | None = None):
     """Gradients of ``score_hypotheses`` w.r.t. ``(vol_src, feat_tgt, W1, W2, b2)`` given ``dL/dscores (B,N)``
-    (three launches; what ``infoNCE_loss`` back-propagates, modules/model_co3d.py:41-61).  R gets no gradient.
+    (three launches; what ``infoNCE_loss`` back-propagates, modules/model_co3d.py:41-61).  R's gradient is
+    ``score_rotation_grad``'s.
     ``workspace``: what ``score_hypotheses_train`` returned for the SAME inputs -- the first kernel then reads the saved
     pre-activations instead of recomputing the forward (and consumes them: one backward per workspace)."""
     if vol_src.dim() != 5 or tuple(vol_src.shape[1:]) != _VOL:
@@ -411,12 +415,16 @@ class _RotateVolumeFn(torch.autograd.Function):
 
 
 class _ScoreFn(torch.autograd.Function):
-    """Differentiable fused scorer: forward = one fused launch, backward = ``score_hypotheses_backward``."""
+    """Differentiable fused scorer: forward = one fused launch, backward = ``score_hypotheses_backward`` for the volume, the
+    target features and the head weights and ``score_rotation_grad`` for R (a shared (N,3,3) set receives the sum over the
+    batch).  Each runs only when one of its inputs needs a gradient."""
 
     @staticmethod
     def forward(ctx, vol_src, feat_tgt, R, W1, W2, b2, n_offset=0, best_key=None, reset_best=None, split_f16=None, need_key=True):
         ctx.ws = None
         plain = n_offset == 0 and best_key is None and not split_f16 and (split_f16 is not None or not _SPLIT_F16.get())
+        # the saved pre-activations serve the volume / feature / weight gradients; R's gradient brings its own workspace
+        plain = plain and any(ctx.needs_input_grad[i] for i in (0, 1, 3, 4, 5))
         if plain:
             # the training forward: the same scores, and the pre-activations kept for the backward (no recompute there);
             # the arg-max key of the inference launch is not produced -- callers of the differentiable form use the scores
@@ -436,14 +444,22 @@ class _ScoreFn(torch.autograd.Function):
     def backward(ctx, grad_scores, _grad_key):
         vol_src, feat_tgt, R, W1, W2, b2 = ctx.saved_tensors
         ws, ctx.ws = ctx.ws, None   # one backward per workspace: a second one (retain_graph) recomputes the forward
-        g_vol, g_ft, g_W1, g_W2, g_b2 = score_hypotheses_backward(vol_src, feat_tgt, R, W1, W2, b2,
-                                                                  grad_scores.contiguous(), workspace=ws)
-        return (g_vol, g_ft, None, g_W1.reshape(W1.shape), g_W2.reshape(W2.shape), g_b2.reshape(b2.shape),
+        gs = grad_scores.contiguous()
+        need = ctx.needs_input_grad
+        g_R = None
+        if need[2]:   # before the other backward: that one consumes the saved workspace, this one brings its own
+            g_R = score_rotation_grad(vol_src, feat_tgt, R, W1, W2, b2, gs)
+            if R.dim() == 3:
+                g_R = g_R.sum(dim=0)
+        if not (need[0] or need[1] or need[3] or need[4] or need[5]):
+            return (None, None, g_R) + (None,) * 8
+        g_vol, g_ft, g_W1, g_W2, g_b2 = score_hypotheses_backward(vol_src, feat_tgt, R, W1, W2, b2, gs, workspace=ws)
+        return (g_vol, g_ft, g_R, g_W1.reshape(W1.shape), g_W2.reshape(W2.shape), g_b2.reshape(b2.shape),
                 None, None, None, None, None)
 
 
 def score_hypotheses_autograd(vol_src, feat_tgt, R, W1, W2, b2) -> torch.Tensor:
-    """``scores (B,N)`` with autograd support for vol_src, feat_tgt and the head weights (training path)."""
+    """``scores (B,N)`` with autograd support for vol_src, feat_tgt, the head weights (training path) and R."""
     return _ScoreFn.apply(vol_src, feat_tgt, R, W1, W2, b2, 0, None, None, None, False)[0]
 
 
@@ -664,6 +680,193 @@ def verify_pair_topk(vol_src: torch.Tensor, vol_tgt: torch.Tensor, R: torch.Tens
     r = verify_pair(vol_src, vol_tgt, R, W1, W2, b2, n_offset=n_offset, want_scores=True, want_feat_tgt=want_feat_tgt, **kw)
     out = (r[0], r[1], topk(r[0], k, n_offset=n_offset, keys=keys, reset=reset))
     return out + (r[2],) if want_feat_tgt else out
+
+
+# ---- rotation gradient of the score, gradient-based pose polishing ------------------------------------------
+
+@torch.no_grad()
+def score_rotation_grad(vol_src: torch.Tensor, feat_tgt: torch.Tensor, R: torch.Tensor, W1: torch.Tensor, W2: torch.Tensor,
+                        b2: torch.Tensor, grad_scores: torch.Tensor | None = None, out: torch.Tensor | None = None,
+                        workspace: torch.Tensor | None = None) -> torch.Tensor:
+    """``grad_R (B,N,3,3) = grad_scores[b,n] * d score[b,n] / d R[b,n]`` (``ahv_score_rotation_grad_f32``): the Euclidean
+    gradient torch.autograd returns for ``rotation_matrix`` through utils.rotate_volume -> forward_3d2d -> the mean cosine.
+    R (N,3,3) shared by the batch or (B,N,3,3); a shared set still gives one gradient per sample and hypothesis.
+    ``grad_scores`` None = ones.  Bitwise reproducible: ``grad_R[b,n]`` does not depend on N, on how a set is cut into
+    calls or on whether the set is shared.  ``out`` / ``workspace`` (float32, ``2048*B*N`` elements): caller's buffers, so
+    that a captured graph replays on the same memory."""
+    if vol_src.dim() != 5 or tuple(vol_src.shape[1:]) != _VOL:
+        raise RuntimeError("vol_src must be (B,16,8,8,8), got %s" % (tuple(vol_src.shape),))
+    B = vol_src.shape[0]
+    if tuple(feat_tgt.shape) != (B, 32, 64):
+        raise RuntimeError("feat_tgt must be (B,32,64), got %s" % (tuple(feat_tgt.shape),))
+    N, rstride = _rot_layout(R, B)
+    tensors = (vol_src, feat_tgt, R, W1, W2, b2) + (() if grad_scores is None else (grad_scores,))
+    dev = _need_gpu(*tensors)
+    if grad_scores is not None and tuple(grad_scores.shape) != (B, N):
+        raise RuntimeError("grad_scores must be (B,N) = %s, got %s" % ((B, N), tuple(grad_scores.shape)))
+    W1c, W2c, b2c = _head(W1, W2, b2)
+    vs, ft, Rc = (t.detach().contiguous() for t in (vol_src, feat_tgt, R))
+    gs = None if grad_scores is None else grad_scores.detach().contiguous()
+    nbytes = _lib.load().ahv_score_rotation_grad_workspace_bytes(B, N)
+    if workspace is None:
+        workspace = torch.empty((max(nbytes, 16) // 4,), dtype=torch.float32, device=dev)
+    elif workspace.device != dev or workspace.dtype != torch.float32 or workspace.numel() * 4 < nbytes:
+        raise RuntimeError("workspace must be a float32 tensor of at least %d elements on %s" % (nbytes // 4, dev))
+    if out is None:
+        out = torch.empty((B, N, 3, 3), dtype=torch.float32, device=dev)
+    elif tuple(out.shape) != (B, N, 3, 3) or not out.is_contiguous() or out.device != dev or out.dtype != torch.float32:
+        raise RuntimeError("out must be a contiguous float32 (B,N,3,3) tensor on %s" % dev)
+    _call(dev, "ahv_score_rotation_grad_f32", vs.data_ptr(), ft.data_ptr(), Rc.data_ptr(), rstride, W1c.data_ptr(),
+          W2c.data_ptr(), b2c.data_ptr(), B, N, gs.data_ptr() if gs is not None else None, workspace.data_ptr(),
+          workspace.numel() * 4, out.data_ptr())
+    return out
+
+
+def _ladder(ladder, dev) -> torch.Tensor:
+    if isinstance(ladder, torch.Tensor):
+        t = ladder.to(device=dev, dtype=torch.float32).reshape(-1).contiguous()
+    else:
+        t = torch.tensor([float(x) for x in ladder], dtype=torch.float32, device=dev)
+    if not 1 <= t.numel() <= _lib.AHV_SO3_MAX_LADDER:
+        raise RuntimeError("the ladder must hold 1..%d factors" % _lib.AHV_SO3_MAX_LADDER)
+    return t
+
+
+def _seeds(R_cur: torch.Tensor):
+    if R_cur.dim() != 4 or tuple(R_cur.shape[2:]) != (3, 3):
+        raise RuntimeError("the seeds must be (B,K,3,3), got %s" % (tuple(R_cur.shape),))
+    return R_cur.shape[0], _topk_k(R_cur.shape[1])
+
+
+@torch.no_grad()
+def so3_ascent_candidates(R_cur: torch.Tensor, grad_R: torch.Tensor, theta: torch.Tensor, ladder,
+                          out: torch.Tensor | None = None) -> torch.Tensor:
+    """``ahv_so3_ascent_candidates_f32``: ``R_cur, grad_R (B,K,3,3)``, ``theta (B,K)`` -> candidates ``(B, K*(L+1), 3, 3)``
+    (``rotations.so3_ascent_candidates`` states the rule)."""
+    B, K = _seeds(R_cur)
+    dev = _need_gpu(R_cur, grad_R, theta)
+    lad = _ladder(ladder, dev)
+    L = lad.numel()
+    if tuple(grad_R.shape) != (B, K, 3, 3) or tuple(theta.shape) != (B, K):
+        raise RuntimeError("grad_R must be (B,K,3,3) and theta (B,K)")
+    if out is None:
+        out = torch.empty((B, K * (L + 1), 3, 3), dtype=torch.float32, device=dev)
+    elif tuple(out.shape) != (B, K * (L + 1), 3, 3) or not out.is_contiguous():
+        raise RuntimeError("out must be a contiguous (B, K*(L+1), 3, 3) tensor")
+    _call(dev, "ahv_so3_ascent_candidates_f32", R_cur.detach().contiguous().data_ptr(), grad_R.detach().contiguous().data_ptr(),
+          theta.detach().contiguous().data_ptr(), lad.data_ptr(), L, B, K, out.data_ptr())
+    return out
+
+
+@torch.no_grad()
+def so3_ascent_select(R_cand: torch.Tensor, cand_scores: torch.Tensor, ladder, R_cur: torch.Tensor, score_cur: torch.Tensor,
+                      theta: torch.Tensor):
+    """``ahv_so3_ascent_select_f32``: picks each seed's slot and UPDATES ``R_cur (B,K,3,3)``, ``score_cur (B,K)`` and
+    ``theta (B,K)`` in place (``rotations.so3_ascent_select`` states the rule); returns the three."""
+    B, K = _seeds(R_cur)
+    dev = _need_gpu(R_cand, cand_scores, R_cur, score_cur, theta)
+    lad = _ladder(ladder, dev)
+    L = lad.numel()
+    if (tuple(R_cand.shape) != (B, K * (L + 1), 3, 3) or tuple(cand_scores.shape) != (B, K * (L + 1))
+            or tuple(score_cur.shape) != (B, K) or tuple(theta.shape) != (B, K)):
+        raise RuntimeError("expected R_cand (B,K*(L+1),3,3), cand_scores (B,K*(L+1)), score_cur and theta (B,K)")
+    for t in (R_cand, cand_scores, R_cur, score_cur, theta):
+        if not t.is_contiguous():
+            raise RuntimeError("so3_ascent_select works in place: its tensors must be contiguous")
+    _call(dev, "ahv_so3_ascent_select_f32", R_cand.data_ptr(), cand_scores.data_ptr(), lad.data_ptr(), L, B, K,
+          R_cur.data_ptr(), score_cur.data_ptr(), theta.data_ptr())
+    return R_cur, score_cur, theta
+
+
+def _score_into(vs, ft, Rc, W1c, W2c, b2c, scores, key) -> None:
+    """The fused scorer on prepared tensors into the caller's buffers (no allocation)."""
+    B, N = scores.shape
+    dev = scores.device
+    lib = _lib.load()
+    with torch.cuda.device(dev):
+        _lib.check(lib.ahv_score_hypotheses_f32(vs.data_ptr(), ft.data_ptr(), Rc.data_ptr(), N * 9, 0, W1c.data_ptr(),
+                                                W2c.data_ptr(), b2c.data_ptr(), B, N, scores.data_ptr(), key.data_ptr(),
+                                                _lib.AHV_SCORE_RESET_BEST, _stream(dev)), "ahv_score_hypotheses_f32")
+
+
+def polish_rotations(vol_src: torch.Tensor, feat_tgt: torch.Tensor, R0: torch.Tensor, W1: torch.Tensor, W2: torch.Tensor,
+                     b2: torch.Tensor, iters: int = 8, init_angle_deg: float = 2.0, ladder=(0.25, 0.5, 1.0, 2.0),
+                     out: dict | None = None):
+    """A few ascent steps on SO(3) from the seeds ``R0 (B,K,3,3)``: returns ``(R (B,K,3,3), scores (B,K), theta (B,K))``.
+    Per iteration: ``score_rotation_grad`` at the seeds, ``so3_ascent_candidates`` (each seed itself + L trial angles along
+    its Riemannian gradient), ONE fused-scorer launch over the ``K*(L+1)`` candidates of every sample, ``so3_ascent_select``.
+    Every score compared or returned is the fused scorer's: ``scores`` equals ``score_hypotheses`` at ``R`` bit for bit, and a
+    seed's score never decreases.  ``iters=0`` returns ``R0`` and its scores.  Fixed iteration count, no host
+    synchronisation; with ``out`` (a dict from an earlier call of the same shapes) nothing is allocated, so the call
+    replays from a hipGraph.  ``theta`` is each seed's final trust angle in radians.  Inference only."""
+    _refuse_grad("polish_rotations", vol_src, feat_tgt, R0, W1, W2, b2)
+    with torch.no_grad():
+        if vol_src.dim() != 5 or tuple(vol_src.shape[1:]) != _VOL:
+            raise RuntimeError("vol_src must be (B,16,8,8,8), got %s" % (tuple(vol_src.shape),))
+        B, K = _seeds(R0)
+        if vol_src.shape[0] != B or tuple(feat_tgt.shape) != (B, 32, 64):
+            raise RuntimeError("expected vol_src (B,16,8,8,8), feat_tgt (B,32,64) and R0 (B,K,3,3) with one B")
+        iters = int(iters)
+        if iters < 0:
+            raise RuntimeError("iters must be >= 0")
+        dev = _need_gpu(vol_src, feat_tgt, R0, W1, W2, b2)
+        W1c, W2c, b2c = _head(W1, W2, b2)
+        vs, ft = vol_src.detach().contiguous(), feat_tgt.detach().contiguous()
+        o = out if out is not None else {}
+        # a ladder given as a device tensor is taken as it is (identified by its storage: no host read, and no host-to-
+        # device copy when the first call with these buffers happens under graph capture); a sequence is copied once
+        if isinstance(ladder, torch.Tensor):
+            L, lad_id = ladder.numel(), ("tensor", ladder.data_ptr(), str(ladder.device), ladder.dtype)
+        else:
+            L, lad_id = len(ladder), tuple(float(x) for x in ladder)
+        sig = (B, K, L, lad_id, float(init_angle_deg), str(dev))
+        if o.get("sig") != sig:
+            o.clear()
+            o["sig"] = sig
+            o["ladder"] = _ladder(ladder, dev)
+            new = lambda *shape, dtype=torch.float32: torch.empty(shape, dtype=dtype, device=dev)
+            o["R"], o["scores"], o["theta"] = new(B, K, 3, 3), new(B, K), new(B, K)
+            o["theta0"] = torch.full((B, K), math.radians(float(init_angle_deg)), dtype=torch.float32, device=dev)
+            o["grad"], o["cand"], o["cand_scores"] = new(B, K, 3, 3), new(B, K * (L + 1), 3, 3), new(B, K * (L + 1))
+            o["ws"] = new(max(_lib.load().ahv_score_rotation_grad_workspace_bytes(B, K), 16) // 4)
+            o["key"] = new(B, dtype=torch.int64)
+        R, scores, theta = o["R"], o["scores"], o["theta"]
+        R.copy_(R0)
+        theta.copy_(o["theta0"])
+        if iters == 0:
+            _score_into(vs, ft, R, W1c, W2c, b2c, scores, o["key"])
+        for _ in range(iters):
+            score_rotation_grad(vs, ft, R, W1c, W2c, b2c, out=o["grad"], workspace=o["ws"])
+            so3_ascent_candidates(R, o["grad"], theta, o["ladder"], out=o["cand"])
+            _score_into(vs, ft, o["cand"], W1c, W2c, b2c, o["cand_scores"], o["key"])
+            so3_ascent_select(o["cand"], o["cand_scores"], o["ladder"], R, scores, theta)
+        return R, scores, theta
+
+
+def verify_pair_polished(vol_src: torch.Tensor, vol_tgt: torch.Tensor, R: torch.Tensor, W1: torch.Tensor, W2: torch.Tensor,
+                         b2: torch.Tensor, K: int = 8, iters: int = 8, init_angle_deg: float = 2.0,
+                         ladder=(0.25, 0.5, 1.0, 2.0), **kw):
+    """The verify step followed by polishing: ``verify_pair`` with the scores kept -> ``topk`` -> ``select_topk`` ->
+    ``polish_rotations`` on the K best hypotheses -> the best of the K polished (first maximal).  Returns
+    ``(score (B,), R_pred (B,3,3), seed_idx (B,), info)``: ``seed_idx`` is the global index of the hypothesis the winner started
+    from; ``info`` holds the K-list ``topk_scores, topk_idx (B,K)`` (entry 0 is the unpolished arg-max), the list's ``keys``,
+    the polished ``polished_scores (B,K)`` / ``polished_R (B,K,3,3)`` / ``theta`` and ``seed_rank (B,)``.  Other keywords go to
+    ``verify_pair``, except ``split_f16``: the polishing loop scores with the fp32 scorer, and a K-list from the split-f16
+    scorer beside it would break "never below the arg-max's score" -- refused (also inside ``split_f16_scorer``).  Inference
+    only."""
+    k = _topk_k(K)
+    if kw.get("split_f16") or (kw.get("split_f16") is None and _SPLIT_F16.get()):
+        raise RuntimeError("verify_pair_polished scores with the fp32 scorer throughout: split_f16 is not supported")
+    scores, _key, keys, f_tgt = verify_pair_topk(vol_src, vol_tgt, R, W1, W2, b2, k, want_feat_tgt=True, **kw)
+    with torch.no_grad():
+        top_scores, top_idx, R_seed = select_topk(keys, R)
+        Rp, sp, theta = polish_rotations(vol_src, f_tgt, R_seed, W1, W2, b2, iters=iters, init_angle_deg=init_angle_deg,
+                                         ladder=ladder)
+        best, rank = argmax(sp)   # first maximal (the list is in descending order of the seeds' scores)
+        rows = torch.arange(sp.shape[0], device=sp.device)
+        info = {"topk_scores": top_scores, "topk_idx": top_idx, "keys": keys, "polished_scores": sp, "polished_R": Rp,
+                "theta": theta, "seed_rank": rank}
+        return best, Rp[rows, rank], top_idx[rows, rank], info
 
 
 class CoarseToFineState:

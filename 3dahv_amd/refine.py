@@ -56,6 +56,13 @@ class CoarseToFine:
     (B,K).  Seed 0's refinements are the single-seed step's, score for score, so the fine score never falls below it.
     ``seeds=1`` is the step described above, unchanged.  The one-launch kernel is not extended: ``fused`` with
     ``seeds > 1`` raises.
+    ``polish_iters > 0`` (gradient-based polishing, ``ops.polish_rotations``): after the fine stage the fine winner takes
+    ``polish_iters`` ascent steps on SO(3) along the rotation gradient of the score.  The fine score and ``R_pred`` returned are
+    the polished ones (never below the fine winner's: an ascent step keeps the incumbent unless a candidate scores strictly
+    higher), the fine index stays that of the seed, and ``self.last["polish"]`` holds ``score_before, R_before, score_after,
+    R_after, theta``.  Multi-rank: after the second key all-reduce every rank holds the same winner and the whole volumes, and
+    the rotation gradient is a function of the hypothesis alone bit for bit, so every rank computes the same bits -- still
+    two collectives per step.  ``polish_iters=0`` is the step described above, unchanged; ``fused`` with polishing raises.
     ``use_graph``: None = captured when the step carries collectives, eager otherwise (see __init__); ``run_many`` replays
     several steps from one graph."""
 
@@ -63,7 +70,8 @@ class CoarseToFine:
                  D: Optional[torch.Tensor] = None, n_fine: int = 1000, max_angle_deg: float = 10.0,
                  batch: int = 1, use_graph: Optional[bool] = None, group=None, seed: int = 0, backend=None,
                  want_scores: bool = False, force_collectives: bool = False, no_teams: bool = False,
-                 fused: Optional[bool] = None, seeds: int = 1):
+                 fused: Optional[bool] = None, seeds: int = 1, polish_iters: int = 0, polish_angle_deg: float = 2.0,
+                 polish_ladder=(0.25, 0.5, 1.0, 2.0)):
         dev = R_coarse.device
         self.ops = ops if backend is None else backend
         self.W1, self.W2, self.b2 = W1, W2, b2
@@ -89,6 +97,18 @@ class CoarseToFine:
         if self.seeds > 1 and fused:
             raise RuntimeError("the one-launch step (fused=True) refines around ONE seed; seeds = %d needs fused=False"
                                % self.seeds)
+        self.polish_iters = int(polish_iters)
+        if self.polish_iters < 0:
+            raise RuntimeError("polish_iters must be >= 0")
+        if self.polish_iters > 0 and fused:
+            raise RuntimeError("the one-launch step (fused=True) does not polish; polish_iters = %d needs fused=False"
+                               % self.polish_iters)
+        self.polish_angle_deg, self.polish_ladder = float(polish_angle_deg), tuple(float(x) for x in polish_ladder)
+        self._polish_out = {}
+        if self.polish_iters > 0 and backend is None and dev.type == "cuda":
+            # the ladder lives on the device from here on: the first polish of a slot may happen under graph capture
+            # (run_many), where a host-to-device copy is not allowed
+            self.polish_ladder = torch.tensor(self.polish_ladder, dtype=torch.float32, device=dev)
         self.c_lo, self.c_hi = shard_range(self.R_coarse.shape[0], self.rank, self.world)
         self.f_lo, self.f_hi = shard_range(self.seeds * self.D.shape[0], self.rank, self.world)
         capturable = (not self.collectives) or (inited and dist.get_backend(group) == "nccl")
@@ -139,7 +159,7 @@ class CoarseToFine:
             self.last = {"coarse_scores": r.get("coarse_scores"), "fine_scores": r.get("fine_scores"), "R_fine": None}
             return r["fine_score"], r["fine_idx"], r["R_pred"], r["coarse_score"], r["coarse_idx"]
         if self.seeds > 1:
-            return self._step_seeds(vol_src, vol_tgt)
+            return self._step_seeds(vol_src, vol_tgt, slot)
         key1, key2 = self._keys
         kw = {"no_teams": True} if self.no_teams else {}
         Rc = self.R_coarse[self.c_lo:self.c_hi]
@@ -159,9 +179,21 @@ class CoarseToFine:
         coarse_score, coarse_idx, _ = o.select_rotation(key1, self.R_coarse, n_offset=0, reset_key=True)
         # this rank's slices of the two score sets and of the refinement set (None unless want_scores)
         self.last = {"coarse_scores": s1, "fine_scores": s2, "R_fine": R_fine if self.want_scores else None}
+        score, R_pred = self._polish(vol_src, f_tgt, score, R_pred, slot)
         return score, idx, R_pred, coarse_score, coarse_idx
 
-    def _step_seeds(self, vol_src, vol_tgt):
+    def _polish(self, vol_src, f_tgt, score, R_pred, slot: int = 0):
+        """The fine winner after ``polish_iters`` ascent steps (every rank on its own: same inputs, same bits)."""
+        if self.polish_iters == 0:
+            return score, R_pred
+        R, s, theta = self.ops.polish_rotations(vol_src, f_tgt, R_pred[:, None], self.W1, self.W2, self.b2,
+                                                iters=self.polish_iters, init_angle_deg=self.polish_angle_deg,
+                                                ladder=self.polish_ladder, out=self._polish_out.setdefault(slot, {}))
+        self.last["polish"] = {"score_before": score, "R_before": R_pred, "score_after": s[:, 0], "R_after": R[:, 0],
+                               "theta": theta[:, 0]}
+        return s[:, 0], R[:, 0]
+
+    def _step_seeds(self, vol_src, vol_tgt, slot: int = 0):
         """The step with ``seeds = K > 1``: stage 2 scores the K*N2 refinements of the K best coarse hypotheses."""
         o = self.ops
         key2 = self._keys[1]
@@ -183,6 +215,7 @@ class CoarseToFine:
         top_scores, top_idx, _ = o.select_topk(klist, self.R_coarse, n_offset=0)
         self.last = {"coarse_scores": s1 if self.want_scores else None, "fine_scores": s2,
                      "R_fine": R_fine if self.want_scores else None, "coarse_topk": (top_scores, top_idx)}
+        score, R_pred = self._polish(vol_src, f_tgt, score, R_pred, slot)
         return score, idx, R_pred, top_scores[:, 0], top_idx[:, 0]
 
     def check(self):
@@ -270,7 +303,7 @@ class CoarseToFine:
             s = torch.cuda.Stream()
             s.wait_stream(torch.cuda.current_stream())
             with torch.cuda.stream(s):  # warm-up outside capture
-                for k in range(min(2, steps)):
+                for k in range(steps if self.polish_iters > 0 else min(2, steps)):   # (polishing builds a slot's buffers on first use)
                     self._step(static[0][k], static[1][k], slot=k)
             torch.cuda.current_stream().wait_stream(s)
             torch.cuda.synchronize()

@@ -137,3 +137,61 @@ def geodesic_deg(R_pred: torch.Tensor, R_gt: torch.Tensor) -> torch.Tensor:
     modules/model.py:199-200, test_linemod.py:66-67): arccos(((sum(Rp*Rg)).clamp(-1,3)-1)/2)*180/pi."""
     sim = (torch.sum(R_pred.reshape(-1, 9) * R_gt.reshape(-1, 9), dim=-1).clamp(-1, 3) - 1) / 2
     return torch.arccos(sim) * 180.0 / math.pi
+
+
+# ---- SO(3) ascent step: the host statement of ahv_so3_ascent_candidates_f32 / ahv_so3_ascent_select_f32 ----------------
+# (what the CPU tests execute and the GPU tests compare the kernels with; ``ops`` never falls back to it)
+
+def so3_tangent(R: torch.Tensor, G: torch.Tensor) -> torch.Tensor:
+    """The skew part ``1/2 (R^T G - G^T R)`` of ``R^T G`` (..., 3, 3): the Riemannian gradient of a function with Euclidean
+    gradient ``G`` at ``R``, in the body frame -- d/de f(R exp(e [w]x)) = 2 <vee(.), w>."""
+    A = R.transpose(-1, -2) @ G
+    return 0.5 * (A - A.transpose(-1, -2))
+
+
+def so3_ascent_candidates(R_cur: torch.Tensor, grad_R: torch.Tensor, theta: torch.Tensor, ladder) -> torch.Tensor:
+    """``R_cur, grad_R (B,K,3,3)``, ``theta (B,K)`` radians, ``ladder`` L factors -> ``(B, K*(L+1), 3, 3)``: slot 0 of a seed is
+    ``R_cur`` itself, slot ``l >= 1`` is ``R_cur exp(ladder[l-1] theta [w/|w|]x)`` with ``w = vee(so3_tangent(R_cur, grad_R))``;
+    ``|w| = 0`` or a non-finite ``w``: every slot is ``R_cur``."""
+    B, K = R_cur.shape[:2]
+    ladder = torch.as_tensor(ladder, dtype=R_cur.dtype, device=R_cur.device).reshape(-1)
+    L = ladder.numel()
+    S = so3_tangent(R_cur, grad_R)
+    w = torch.stack([S[..., 2, 1], S[..., 0, 2], S[..., 1, 0]], dim=-1)
+    nrm = (w * w).sum(-1).sqrt()
+    move = (nrm > 0) & torch.isfinite(nrm)
+    n = torch.where(move[..., None], w / torch.where(move, nrm, torch.ones_like(nrm))[..., None], torch.zeros_like(w))
+    a = theta[..., None] * ladder                                   # (B,K,L)
+    sn, c1 = torch.sin(a)[..., None, None], (2 * torch.sin(0.5 * a) ** 2)[..., None, None]
+    Kx = torch.zeros_like(R_cur)
+    Kx[..., 0, 1], Kx[..., 0, 2] = -n[..., 2], n[..., 1]
+    Kx[..., 1, 0], Kx[..., 1, 2] = n[..., 2], -n[..., 0]
+    Kx[..., 2, 0], Kx[..., 2, 1] = -n[..., 1], n[..., 0]
+    eye = torch.eye(3, dtype=R_cur.dtype, device=R_cur.device)
+    nnT = n[..., :, None] * n[..., None, :]
+    E = eye + sn * Kx[:, :, None] + c1 * (nnT - eye)[:, :, None]   # (B,K,L,3,3)
+    moved = R_cur[:, :, None] @ E
+    stay = R_cur[:, :, None].expand(B, K, L, 3, 3)
+    cand = torch.where(move[..., None, None, None], moved, stay)
+    return torch.cat([R_cur[:, :, None], cand], dim=2).reshape(B, K * (L + 1), 3, 3)
+
+
+def so3_ascent_select(R_cand: torch.Tensor, cand_scores: torch.Tensor, theta: torch.Tensor, ladder):
+    """``R_cand (B, K*(L+1), 3, 3)``, its scores ``(B, K*(L+1))`` -> ``(R_cur (B,K,3,3), score_cur (B,K), theta (B,K))``.  Slots
+    are scanned in order and a candidate replaces the incumbent only if its score is strictly greater (false for NaN): a
+    seed's score never decreases, slot 0 wins ties.  ``theta <- ladder[l-1] theta`` for the accepted slot, ``theta min(ladder)``
+    when slot 0 stayed."""
+    B, K = theta.shape
+    ladder = torch.as_tensor(ladder, dtype=theta.dtype, device=theta.device).reshape(-1)
+    L = ladder.numel()
+    sc = cand_scores.reshape(B, K, L + 1)
+    best = sc[..., 0].clone()
+    slot = torch.zeros((B, K), dtype=torch.int64, device=sc.device)
+    for l in range(1, L + 1):
+        better = sc[..., l] > best
+        best = torch.where(better, sc[..., l], best)
+        slot = torch.where(better, torch.full_like(slot, l), slot)
+    Rc = R_cand.reshape(B, K, L + 1, 3, 3)
+    R_new = torch.gather(Rc, 2, slot[..., None, None, None].expand(B, K, 1, 3, 3))[:, :, 0]
+    factor = torch.cat([ladder.min().reshape(1), ladder])[slot]
+    return R_new, best, theta * factor

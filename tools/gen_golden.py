@@ -300,6 +300,38 @@ def gen_infonce(rotate_volume, fa, vol_src3, vol_tgt3):
     np.savez(os.path.join(OUT, "infonce_grad.npz"), W1=W1, W2=W2, b2=b2, acc_thr=np.int64(ACC_THR), **out)
 
 
+def gen_rotation_grad(rotate_volume, fa, vol_src, vol_tgt):
+    """G12 `rotation_grad`: d score / d rotation_matrix of the reference's own differentiable callables under torch autograd
+    -- `utils.rotate_volume` (utils.py:113-131: F.affine_grid + F.grid_sample carry the gradient to rotation_matrix) and
+    `Feature_Aligner.forward_3d2d` (modules/modules.py:112-124) execute as shipped, the score line is test_co3d.py:143.
+    Inputs of G1 `score_n128`; hypotheses: its first 32 rotations and the G3 `edge_rotations` set.  Stored: the rotations
+    (with the edge names), grad_R of the reference run as shipped (fp32) and of the same modules cast to fp64, and the
+    scores of both runs."""
+    import copy
+    g1 = np.load(os.path.join(OUT, "score_n128.npz"))
+    g3 = np.load(os.path.join(OUT, "edge_rotations.npz"))
+    W1, W2, b2 = head_weights(fa)
+    assert np.array_equal(g1["vol_src"], vol_src.numpy()) and np.array_equal(g1["vol_tgt"], vol_tgt.numpy())
+    assert np.array_equal(g1["W1"], W1) and np.array_equal(g1["W2"], W2) and np.array_equal(g1["b2"], b2)
+    R = np.concatenate([g1["R"][:32], g3["R"]]).astype(np.float32)
+    names = np.array(["haar%02d" % i for i in range(32)] + [str(n) for n in g3["names"]])
+    out = {}
+    for tag, dtype in (("", torch.float32), ("_f64", torch.float64)):
+        f = copy.deepcopy(fa).to(dtype).eval()
+        Rl = torch.from_numpy(R).to(dtype).requires_grad_(True)
+        n = Rl.shape[0]
+        warped = rotate_volume(vol_src.to(dtype).expand(n, -1, -1, -1, -1), Rl)
+        f_src = f.forward_3d2d(warped)
+        with torch.no_grad():
+            f_tgt = f.forward_3d2d(vol_tgt.to(dtype))
+        sim = (f_src * f_tgt).sum(dim=1).mean(dim=-1)      # test_co3d.py:143 for one pair
+        (g,) = torch.autograd.grad(sim.sum(), Rl)
+        out["grad_R" + tag], out["scores" + tag] = g.numpy(), sim.detach().numpy()
+    err = np.abs(out["grad_R"] - out["grad_R_f64"]).reshape(n, 9).max(1) / np.abs(out["grad_R_f64"]).reshape(n, 9).max(1).clip(1e-30)
+    print("G12 rotation_grad: %d hypotheses, |grad| max %.3e, fp32 run against fp64 run: max %.2e" % (n, np.abs(out["grad_R_f64"]).max(), err.max()))
+    np.savez(os.path.join(OUT, "rotation_grad.npz"), R=R, names=names, **out)
+
+
 def main():
     os.makedirs(OUT, exist_ok=True)
     torch.set_num_threads(8)
@@ -313,6 +345,9 @@ def main():
     fa, vol_src3, vol_tgt3 = seeded_pair(Feature_Aligner)
     W1, W2, b2 = head_weights(fa)
     vol_src, vol_tgt = vol_src3[:1], vol_tgt3[:1]
+    if "--only-g12" in sys.argv:    # the rotation gradient alone (needs score_n128.npz and edge_rotations.npz in place)
+        gen_rotation_grad(rotate_volume, fa, vol_src, vol_tgt)
+        return
     if "--only-g11" in sys.argv:    # round 6 addition alone
         gen_infonce(rotate_volume, fa, vol_src3, vol_tgt3)
         return
@@ -421,6 +456,7 @@ def main():
     gen_batched32(rotate_volume, Feature_Aligner, fa)
     gen_nonfinite(rotate_volume, fa, vol_src, vol_tgt)
     gen_infonce(rotate_volume, fa, vol_src3, vol_tgt3)
+    gen_rotation_grad(rotate_volume, fa, vol_src, vol_tgt)
     gen_encoder_full(Feature_Aligner)
 
     total = sum(os.path.getsize(os.path.join(OUT, f)) for f in os.listdir(OUT))
