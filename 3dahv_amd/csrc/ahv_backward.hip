@@ -888,6 +888,7 @@ __device__ __forceinline__ void rmw_wait(unsigned* ctr, unsigned target)
 
 // |R^T R - I| <= 0.04 entrywise: the eigenvalues of R^T R are then >= 0.88, two lattice points 4 apart map >= 3.75 apart and
 // >= 2.16 apart along some axis -- their footprints cannot share a row.  NaN compares false: not a rotation.
+// (tests/test_rmw_footprints_cpu.py reads the constant below and checks the claim on a model of rmw_scatter_half's lane map.)
 __device__ __forceinline__ bool rmw_rotation_like(const float* Rm)
 {
     bool ok = true;

@@ -14,6 +14,7 @@ import numpy as np
 import pytest
 import torch
 
+from . import rotation_families as fam
 from .conftest import load_golden
 
 pytestmark = pytest.mark.gpu
@@ -73,34 +74,54 @@ def ref_scores_masked(vs, ft, R, W1, W2, b2, flips=None):
     return torch.stack(out), us
 
 
-def kink_aware_errors(got, vs, ft, R, W1, W2, b2, gs):
-    """max relative error of every gradient against the best assignment of the ambiguous ReLU sub-gradients."""
-    def grads(flips):
+class KinkReference:
+    """The fp64 gradients of one case, the list of its ambiguous ReLU sub-gradients and (lazily, once) the change of the
+    gradients when each of them flips: several kernel results of the same case share one reference.
+    A pre-activation of EXACTLY 0 is not ambiguous (tests/test_gpu_rotation_grad.py says the same): a rank-deficient R
+    produces them, F.relu's sub-gradient there is 0 and so is the kernel's ``u > 0`` mask -- the fp64 reference and the
+    kernel cannot take different sides."""
+
+    def __init__(self, vs, ft, R, W1, W2, b2, gs):
+        self.args = (vs, ft, R, W1, W2, b2, gs)
+        self.base, self.us = self.grads(None)
+        self.amb = [(b, idx) for b, u in enumerate(self.us) for idx in torch.nonzero((u.abs() < KINK_TAU) & (u != 0)).tolist()]
+        self.deltas = None
+
+    def grads(self, flips):
+        vs, ft, R, W1, W2, b2, gs = self.args
         leaves = [x.double().requires_grad_(True) for x in (vs, ft, W1, W2, b2)]
         s, us = ref_scores_masked(leaves[0], leaves[1], R.double(), leaves[2], leaves[3], leaves[4], flips)
         return torch.autograd.grad(s, leaves, grad_outputs=gs.double()), us
-    base, us = grads(None)
-    amb = [(b, idx) for b, u in enumerate(us) for idx in torch.nonzero(u.abs() < KINK_TAU).tolist()]
-    errs0 = [relerr(a, r.reshape(a.shape)) for a, r in zip(got, base)]
-    if not amb or max(errs0) < GRAD_RTOL:
-        return errs0, len(amb), 0
-    assert len(amb) <= KINK_MAX, "too many near-kink pre-activations: %d" % len(amb)
-    deltas = []
-    for b, idx in amb:  # gradient change when this one sub-gradient flips
-        flips = [torch.zeros_like(u, dtype=torch.bool) for u in us]
-        flips[b][tuple(idx)] = True
-        g, _ = grads(flips)
-        deltas.append([x - y for x, y in zip(g, base)])
-    # the gradient is affine in the flip bits: least squares for the bits, rounded to {0, 1}
-    flat = lambda ts: torch.cat([t.reshape(-1).double() for t in ts])
-    A = torch.stack([flat(d) for d in deltas], dim=1)
-    rhs = flat([a.double() - r.reshape(a.shape) for a, r in zip(got, base)])
-    bits = (torch.linalg.lstsq(A, rhs[:, None]).solution[:, 0] > 0.5)
-    ref = [x.clone() for x in base]
-    for i in torch.nonzero(bits).flatten().tolist():
-        ref = [x + d for x, d in zip(ref, deltas[i])]
-    errs = [relerr(a, r.reshape(a.shape)) for a, r in zip(got, ref)]
-    return errs, len(amb), int(bits.sum())
+
+    def errors(self, got):
+        base, us, amb = self.base, self.us, self.amb
+        errs0 = [relerr(a, r.reshape(a.shape)) for a, r in zip(got, base)]
+        if not amb or max(errs0) < GRAD_RTOL:
+            return errs0, len(amb), 0
+        assert len(amb) <= KINK_MAX, "too many near-kink pre-activations: %d" % len(amb)
+        if self.deltas is None:
+            self.deltas = []
+            for b, idx in amb:  # gradient change when this one sub-gradient flips
+                flips = [torch.zeros_like(u, dtype=torch.bool) for u in us]
+                flips[b][tuple(idx)] = True
+                g, _ = self.grads(flips)
+                self.deltas.append([x - y for x, y in zip(g, base)])
+        deltas = self.deltas
+        # the gradient is affine in the flip bits: least squares for the bits, rounded to {0, 1}
+        flat = lambda ts: torch.cat([t.reshape(-1).double() for t in ts])
+        A = torch.stack([flat(d) for d in deltas], dim=1)
+        rhs = flat([a.double() - r.reshape(a.shape) for a, r in zip(got, base)])
+        bits = (torch.linalg.lstsq(A, rhs[:, None]).solution[:, 0] > 0.5)
+        ref = [x.clone() for x in base]
+        for i in torch.nonzero(bits).flatten().tolist():
+            ref = [x + d for x, d in zip(ref, deltas[i])]
+        errs = [relerr(a, r.reshape(a.shape)) for a, r in zip(got, ref)]
+        return errs, len(amb), int(bits.sum())
+
+
+def kink_aware_errors(got, vs, ft, R, W1, W2, b2, gs):
+    """max relative error of every gradient against the best assignment of the ambiguous ReLU sub-gradients."""
+    return KinkReference(vs, ft, R, W1, W2, b2, gs).errors(got)
 
 
 def make_case(ahv, dev, B, N, per_sample, seed):
@@ -247,6 +268,109 @@ def test_backward_edge_cases(ops, ahv, dev):
     a = ops.score_hypotheses_backward(vs, ft, R, W1, W2, b2, gs)
     b = ops.score_hypotheses_backward(vs, ft, R, W1, W2, b2, gs)
     assert all(relerr(x, y.double()) < 1e-5 for x, y in zip(a, b))
+
+
+# ---- the dV scatter's two paths (tests/rotation_families.py; the lane-map model is tests/test_rmw_footprints_cpu.py) ----------
+GRAD_NAMES = ("vol_src", "feat_tgt", "W1", "W2", "b2")
+SAVED_RTOL = 5e-6       # saved against recomputing backward: the bar of test_saved_preactivations_backward_equals_the_recomputing_one
+TWO_CALLS_RTOL = 1e-5   # "two calls agree to rounding": the bar of test_backward_edge_cases
+
+
+def family_sets(which):
+    """name -> (B, R as a numpy array (N,3,3) shared or (B,N,3,3) per sample) for one family case."""
+    if which == "singles":        # B = 1, N = 1: the first matrix of every sub-family, and the zero matrix
+        out = {}
+        for R, names in (fam.inside(), fam.outside()):
+            seen = set()
+            for k, s in enumerate(names):
+                if fam.family(s) not in seen:
+                    seen.add(fam.family(s))
+                    out[s] = (1, R[k:k + 1])
+        return out
+    if which == "shared_mixed":   # B = 2, one set of 200: both kinds in flight in a workgroup
+        return {which: (2, fam.mixed(200)[0])}
+    if which == "per_sample":     # B = 3 x 96: one sample all accepted, one all rejected, one mixed
+        return {which: (3, np.stack([fam.inside(96)[0], fam.outside(96)[0], fam.mixed(96)[0]]))}
+    if which == "many_samples":   # B = 300 x 2: more samples than CUs, one accepted and one rejected matrix per sample
+        return {which: (300, np.stack([fam.inside(300, 8)[0], fam.outside(300, 8)[0]], axis=1))}
+    if which == "large_mixed":    # B = 1 x 2000: several hypotheses per slot and workgroup (reference cost of the (2, 1100) case)
+        return {which: (1, fam.mixed(2000)[0])}
+    raise KeyError(which)
+
+
+def family_case(ahv, dev, B, R_np, seed):
+    """make_case inputs with R replaced."""
+    vs, ft, _, W1, W2, b2, _ = make_case(ahv, dev, B, 1, False, seed)
+    R = torch.from_numpy(np.ascontiguousarray(R_np)).to(dev)
+    gs = torch.from_numpy(np.random.RandomState(seed + 7).standard_normal((B, R.shape[-3])).astype(np.float32)).to(dev)
+    return vs, ft, R, W1, W2, b2, gs
+
+
+def both_backwards(ops, vs, ft, R, W1, W2, b2, gs):
+    """(recomputing gradients, saved-pre-activation gradients); the training forward's scores must be the inference ones."""
+    want = ops.score_hypotheses_backward(vs, ft, R, W1, W2, b2, gs)
+    scores, ws = ops.score_hypotheses_train(vs, ft, R, W1, W2, b2)
+    plain, _ = ops.score_hypotheses(vs, ft, R, W1, W2, b2)
+    assert torch.equal(scores, plain)
+    saved = ops.score_hypotheses_backward(vs, ft, R, W1, W2, b2, gs, workspace=ws)
+    return want, saved
+
+
+@pytest.mark.parametrize("which", ["singles", "shared_mixed", "per_sample", "many_samples", "large_mixed"])
+def test_backward_of_near_and_non_rotations_matches_fp64_autograd(ops, ahv, dev, which):
+    """Matrices at the edge of what rmw_rotation_like accepts (8 voxels per scatter instruction) and matrices it rejects
+    (one voxel per instruction), alone, side by side in a workgroup and many per slot: the five gradients of the recomputing
+    AND of the saved-pre-activation backward against the kink-aware fp64 reference, unchanged GRAD_RTOL; the training forward
+    gives the inference scores bit for bit, and the two backwards agree to SAVED_RTOL."""
+    for k, (name, (B, R_np)) in enumerate(family_sets(which).items()):
+        case = family_case(ahv, dev, B, R_np, 400 + 10 * k + B)
+        want, saved = both_backwards(ops, *case)
+        ref = KinkReference(*case)
+        for tag, got in (("recomputing", want), ("saved", saved)):
+            errs, n_amb, combo = ref.errors(got)
+            print(name, tag, tuple(case[2].shape), {k_: "%.1e" % v for k_, v in zip(GRAD_NAMES, errs)}, "near-kink pre-activations:", n_amb,
+                  "flipped:", combo)
+            assert all(torch.isfinite(g).all().item() for g in got)
+            assert max(errs) < GRAD_RTOL, (name, tag, errs, n_amb)
+        between = [relerr(a, b.double()) for a, b in zip(saved, want)]
+        print(name, "saved against recomputing:", ["%.1e" % e for e in between])
+        assert max(between) < SAVED_RTOL, (name, between)
+
+
+@pytest.mark.parametrize("saved", [False, True])
+def test_backward_is_additive_over_single_hypothesis_calls(ops, ahv, dev, saved):
+    """The five gradients of the mixed set equal the sum of N calls with ONE hypothesis each, added up in fp64 on the host.  A
+    single-hypothesis call has one busy slot in one workgroup per sample, so no two hypotheses share an instruction stream or
+    an image there: a race between the lanes of a scatter instruction, or between the two slots, shows as a difference --
+    without any kink fitting, the arithmetic per hypothesis being the same in both arrangements."""
+    R_np = fam.mixed(200)[0]
+    vs, ft, R, W1, W2, b2, gs = family_case(ahv, dev, 2, R_np, 431)
+
+    def run(r, g):
+        r, g = r.contiguous(), g.contiguous()
+        if not saved:
+            return ops.score_hypotheses_backward(vs, ft, r, W1, W2, b2, g)
+        _, ws = ops.score_hypotheses_train(vs, ft, r, W1, W2, b2)
+        return ops.score_hypotheses_backward(vs, ft, r, W1, W2, b2, g, workspace=ws)
+    full = run(R, gs)
+    total = [torch.zeros(t.shape, dtype=torch.float64) for t in full]
+    for n in range(R.shape[0]):
+        for acc, part in zip(total, run(R[n:n + 1], gs[:, n:n + 1])):
+            acc += part.cpu().double()
+    errs = [relerr(f.cpu(), t) for f, t in zip(full, total)]
+    print("additivity, saved =", saved, {k: "%.1e" % v for k, v in zip(GRAD_NAMES, errs)})
+    assert max(errs) < TWO_CALLS_RTOL, dict(zip(GRAD_NAMES, errs))
+
+
+def test_backward_of_rejected_matrices_is_reproducible(ops, ahv, dev):
+    """Two calls on ``outside`` (footprints that do overlap, 46 % of them by the model) agree to rounding, both backwards."""
+    case = family_case(ahv, dev, 2, fam.outside()[0], 433)
+    a, sa = both_backwards(ops, *case)
+    b, sb = both_backwards(ops, *case)
+    for tag, x, y in (("recomputing", a, b), ("saved", sa, sb)):
+        errs = [relerr(p, q.double()) for p, q in zip(x, y)]
+        print("run to run,", tag, ["%.1e" % e for e in errs])
+        assert max(errs) < TWO_CALLS_RTOL, (tag, errs)
 
 
 def tiny_cfg(n):
