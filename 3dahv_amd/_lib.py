@@ -82,6 +82,8 @@ SIGNATURES["ahv_topk_f32"] = (_int, [_vp, _int, _i64, _i64, _int, _vp, _vp, ctyp
 SIGNATURES["ahv_topk_merge_keys"] = (_int, [_vp, _int, _int, _int, _vp, _u32, _vp])
 SIGNATURES["ahv_select_topk_f32"] = (_int, [_vp, _int, _vp, _i64, _i64, _i64, _int, _vp, _vp, _vp, _u32, _vp])
 SIGNATURES["ahv_compose_rotations_topk_f32"] = (_int, [_vp, _int, _vp, _i64, _i64, _i64, _vp, _i64, _int, _vp, _vp])
+SIGNATURES["ahv_topk_modes_workspace_bytes"] = (ctypes.c_size_t, [_int, _i64, _int])
+SIGNATURES["ahv_topk_modes_f32"] = (_int, [_vp, _vp, _i64, _int, _i64, _i64, _int, ctypes.c_float, _vp, _vp, ctypes.c_size_t, _vp])
 SIGNATURES["ahv_score_rotation_grad_workspace_bytes"] = (ctypes.c_size_t, [_int, _i64])
 SIGNATURES["ahv_score_rotation_grad_f32"] = (_int, [_vp, _vp, _vp, _i64, _vp, _vp, _vp, _int, _i64, _vp, _vp, ctypes.c_size_t,
                                                     _vp, _vp])

@@ -32,6 +32,9 @@ hipError_t launch_select_topk(int64_t*, int, const float*, int64_t, int64_t, int
                               hipStream_t);
 hipError_t launch_compose_rotations_topk(const int64_t*, int, const float*, int64_t, int64_t, int64_t, const float*, int64_t,
                                          int, float*, hipStream_t);
+int64_t topk_modes_state_stride(int64_t N);
+hipError_t launch_topk_modes(const float*, const float*, int64_t, int, int64_t, int64_t, int, float, int64_t*, int64_t*,
+                             hipStream_t);
 hipError_t launch_random_rotations(uint64_t, uint64_t, int64_t, float*, hipStream_t);
 hipError_t launch_so3_grid(int64_t, int64_t, int64_t, float*, hipStream_t);
 hipError_t launch_score_backward(const float*, const float*, const float*, int64_t, const float*, const float*,
@@ -617,6 +620,43 @@ int ahv_compose_rotations_topk_f32(const int64_t* keys, int K, const float* R, i
     hipError_t e = ahv::launch_compose_rotations_topk(keys, K, R, r_batch_stride, n_offset, N, D, N2, B, out,
                                                       static_cast<hipStream_t>(stream));
     if (e != hipSuccess) return hip_fail("compose_rotations_topk: launch", e);
+    return AHV_OK;
+}
+
+// ---- distinct pose modes ---------------------------------------------------------------------------------
+size_t ahv_topk_modes_workspace_bytes(int B, int64_t N, int K)
+{
+    if (B <= 0 || N <= 0 || bad_k(K)) return 0;
+    return sizeof(int64_t) * (size_t)B * (size_t)ahv::topk_modes_state_stride(N);   // the alive state: one key per hypothesis
+}
+
+int ahv_topk_modes_f32(const float* scores, const float* R, int64_t r_batch_stride, int B, int64_t N, int64_t n_offset, int K,
+                       float min_trace, int64_t* keys, void* workspace, size_t workspace_bytes, void* stream)
+{
+    if (bad_k(K)) return fail(AHV_EINVAL, "topk_modes: K = %d outside 1..%d", K, AHV_TOPK_MAX_K);
+    if (B < 0 || N < 0) return fail(AHV_EINVAL, "topk_modes: negative size");
+    if (B > 65535) return fail(AHV_EINVAL, "topk_modes: B > 65535");
+    if (n_offset < 0 || n_offset + N > 4294967296ll) return fail(AHV_EINVAL, "topk_modes: n_offset + N must fit in 32 bits");
+    if (!(min_trace > -1.0f && min_trace < 3.0f))   // false for a NaN
+        return fail(AHV_EINVAL, "topk_modes: min_trace = %g outside (-1, 3) (1 + 2 cos theta, 0 < theta < 180 degrees)",
+                    (double)min_trace);
+    if (r_batch_stride != 0 && r_batch_stride != N * 9)
+        return fail(AHV_EINVAL, "topk_modes: r_batch_stride %lld must be 0 or N*9", (long long)r_batch_stride);
+    if (B == 0) return AHV_OK;
+    if (!keys || (N > 0 && (!scores || !R))) return fail(AHV_EINVAL, "topk_modes: null pointer");
+    const size_t need = ahv_topk_modes_workspace_bytes(B, N, K);
+    if (need && (!workspace || workspace_bytes < need || (reinterpret_cast<uintptr_t>(workspace) & 15)))
+        return fail(AHV_EINVAL, "topk_modes: needs a 16-byte aligned workspace of %zu bytes (ahv_topk_modes_workspace_bytes), "
+                    "got %zu", need, workspace_bytes);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (N == 0) {
+        hipError_t e = ahv::launch_fill_keys(keys, B * K, s);
+        if (e != hipSuccess) return hip_fail("topk_modes: list fill", e);
+        return AHV_OK;
+    }
+    hipError_t e = ahv::launch_topk_modes(scores, R, r_batch_stride, B, N, n_offset, K, min_trace, keys,
+                                          static_cast<int64_t*>(workspace), s);
+    if (e != hipSuccess) return hip_fail("topk_modes: launch", e);
     return AHV_OK;
 }
 

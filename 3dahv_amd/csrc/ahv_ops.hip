@@ -779,6 +779,131 @@ __global__ __launch_bounds__(256) void compose_rotations_topk_kernel(const key_t
 }
 
 // ---------------------------------------------------------------------------------
+// Distinct pose modes (ahv_topk_modes_f32): greedy suppression by geodesic distance over the WHOLE scored set.  Entry j of
+// the list is the largest key still alive; the winner then kills itself (by index, unconditionally) and every alive
+// hypothesis i with t(i, w) = sum_ab R_i[a][b] R_w[a][b] >= tau (tau = 1 + 2 cos theta: for rotations "within theta of
+// the winner").  A NaN t kills nothing.  K + 1 dependent launches: the list is filled EMPTY, round 0 packs the keys into the
+// alive state, round j >= 1 applies winner j - 1 and reduces the largest survivor.  The KERNEL BOUNDARY is the hand-over of
+// keys[j - 1]: no workgroup waits on another one.
+// Alive state: the packed keys themselves, state[b][Ns] (Ns = N rounded up to 4) in the caller's workspace, kKeyEmpty =
+// dead -- 8 bytes per hypothesis, read every round, written only where a hypothesis dies; the survivor's key needs no
+// re-packing.  Grid rule of the top-K kernels: tiles of kTopkTile hypotheses, 256 threads, four consecutive hypotheses per
+// lane; tile t starts at hypothesis t * kTopkTile.  A lane's four matrices are 144 contiguous bytes: nine 16-byte loads
+// when THAT ADDRESS is 16-byte aligned (a per-sample R row with N % 4 != 0 starts mid-vector, so the tile index says
+// nothing), element by element otherwise and at the ragged end.  A lane whose four hypotheses are all dead reads no
+// matrix; a wave of such lanes issues no load.
+// ---------------------------------------------------------------------------------
+typedef long long i64x2 __attribute__((ext_vector_type(2)));
+
+// the workgroup's largest key -> one atomicMax into *dst (skipped when nothing survives: *dst was filled kKeyEmpty)
+__device__ __forceinline__ void modes_publish(key_t best, key_t* wl, key_t* dst)
+{
+    const key_t m = wave_max_key_dpp(best);
+    if ((threadIdx.x & 63) == 0) wl[threadIdx.x >> 6] = m;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        key_t r = wl[0];
+#pragma unroll
+        for (int w = 1; w < kTopkThreads / 64; ++w) r = wl[w] > r ? wl[w] : r;
+        if (r != kKeyEmpty) atomicMax(dst, r);
+    }
+}
+
+// kFirst: round 0 -- state = pack_key(scores), keys[b][0] = the arg-max key.  !kFirst: round j.
+template <bool kFirst>
+__global__ __launch_bounds__(kTopkThreads) void topk_modes_kernel(const float* __restrict__ scores, const float* __restrict__ R,
+                                                                  long r_batch_stride, long N, long Ns, long n_offset, int K,
+                                                                  int j, float tau, key_t* __restrict__ state,
+                                                                  key_t* __restrict__ keys)
+{
+    __shared__ key_t wl[kTopkThreads / 64];
+    const int tid = threadIdx.x, b = blockIdx.y;
+    key_t* st = state + (long)b * Ns;
+    key_t* list = keys + (long)b * K;
+    const long tiles = (N + kTopkTile - 1) / kTopkTile;
+    key_t best = kKeyEmpty;
+    if constexpr (kFirst) {
+        const float* s = scores + (long)b * N;
+        for (long t = blockIdx.x; t < tiles; t += gridDim.x) {
+            const long n0 = t * kTopkTile + (long)tid * 4;
+            if (n0 >= N) continue;
+            key_t c[4];
+            if (n0 + 3 < N && (reinterpret_cast<unsigned long long>(s + n0) & 15ull) == 0) {
+                const float4 q = *reinterpret_cast<const float4*>(s + n0);
+                c[0] = pack_key(q.x, (unsigned)(n_offset + n0));
+                c[1] = pack_key(q.y, (unsigned)(n_offset + n0 + 1));
+                c[2] = pack_key(q.z, (unsigned)(n_offset + n0 + 2));
+                c[3] = pack_key(q.w, (unsigned)(n_offset + n0 + 3));
+            } else {
+#pragma unroll
+                for (int e = 0; e < 4; ++e) c[e] = n0 + e < N ? pack_key(s[n0 + e], (unsigned)(n_offset + n0 + e)) : kKeyEmpty;
+            }
+            // (the row is padded to Ns: all four slots exist; the padding is written dead)
+            *reinterpret_cast<i64x2*>(st + n0) = i64x2{c[0], c[1]};
+            *reinterpret_cast<i64x2*>(st + n0 + 2) = i64x2{c[2], c[3]};
+#pragma unroll
+            for (int e = 0; e < 4; ++e) best = c[e] > best ? c[e] : best;
+        }
+        modes_publish(best, wl, list);
+    } else {
+        const key_t prev = list[j - 1];
+        if (prev == kKeyEmpty) return;  // the alive set ran out: keys[j..K) stay EMPTY (uniform over the grid)
+        const long widx = key_index(prev) - n_offset;
+        if (widx < 0 || widx >= N) return;  // (cannot happen for a list this call built: stay in bounds regardless)
+        const float* Rb = R + (long)b * r_batch_stride;
+        float w[9];
+#pragma unroll
+        for (int i = 0; i < 9; ++i) w[i] = Rb[widx * 9 + i];
+        for (long t = blockIdx.x; t < tiles; t += gridDim.x) {
+            const long n0 = t * kTopkTile + (long)tid * 4;
+            if (n0 >= N) continue;
+            const i64x2 c01 = *reinterpret_cast<const i64x2*>(st + n0), c23 = *reinterpret_cast<const i64x2*>(st + n0 + 2);
+            key_t c[4] = {c01.x, c01.y, c23.x, c23.y};
+            if (c[0] == kKeyEmpty && c[1] == kKeyEmpty && c[2] == kKeyEmpty && c[3] == kKeyEmpty) continue;
+            const float* r = Rb + n0 * 9;
+            float tr[4];
+            if (n0 + 3 < N && (reinterpret_cast<unsigned long long>(r) & 15ull) == 0) {
+                float4 q[9];
+#pragma unroll
+                for (int v = 0; v < 9; ++v) q[v] = reinterpret_cast<const float4*>(r)[v];
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    float acc = 0.0f;
+#pragma unroll
+                    for (int i = 0; i < 9; ++i) {
+                        const int f = e * 9 + i;
+                        const float4 v = q[f >> 2];
+                        const float x = (f & 3) == 0 ? v.x : (f & 3) == 1 ? v.y : (f & 3) == 2 ? v.z : v.w;
+                        acc = fmaf(x, w[i], acc);
+                    }
+                    tr[e] = acc;
+                }
+            } else {
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    float acc = 0.0f;
+                    if (n0 + e < N && c[e] != kKeyEmpty) {
+#pragma unroll
+                        for (int i = 0; i < 9; ++i) acc = fmaf(r[e * 9 + i], w[i], acc);
+                    }
+                    tr[e] = acc;
+                }
+            }
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                if (c[e] == kKeyEmpty) continue;
+                if (tr[e] >= tau || n0 + e == widx) {  // false for a NaN trace; the winner goes by its index
+                    st[n0 + e] = kKeyEmpty;
+                    continue;
+                }
+                best = c[e] > best ? c[e] : best;
+            }
+        }
+        modes_publish(best, wl, list + j);
+    }
+}
+
+// ---------------------------------------------------------------------------------
 // Haar-uniform rotation hypotheses generated on the device (replaces the host call
 // pytorch3d.transforms.random_rotations(N), test_co3d.py:106 / modules/model.py:184; only the
 // distribution matters -- hypotheses are inputs of the hot path).  Counter-based: rotation n
@@ -1029,6 +1154,27 @@ __global__ void fill_keys_kernel(key_t* __restrict__ k, int B)
 hipError_t launch_fill_keys(int64_t* best_key, int B, hipStream_t stream)
 {
     hipLaunchKernelGGL(fill_keys_kernel, dim3((B + 255) / 256), dim3(256), 0, stream, reinterpret_cast<key_t*>(best_key), B);
+    return hipGetLastError();
+}
+
+// hypotheses per sample of the alive state of ahv_topk_modes_f32: N rounded up to a lane's four
+int64_t topk_modes_state_stride(int64_t N) { return (N + 3) & ~(int64_t)3; }
+
+// K + 1 launches: the list filled EMPTY, round 0, rounds 1 .. K - 1 (each reads the entry the one before reduced)
+hipError_t launch_topk_modes(const float* scores, const float* R, int64_t r_batch_stride, int B, int64_t N, int64_t n_offset,
+                             int K, float tau, int64_t* keys, int64_t* state, hipStream_t stream)
+{
+    hipError_t e = launch_fill_keys(keys, B * K, stream);
+    if (e != hipSuccess) return e;
+    const int64_t tiles = (N + kTopkTile - 1) / kTopkTile;
+    const dim3 grid((unsigned)(tiles < 1024 ? tiles : 1024), (unsigned)B);
+    const long Ns = (long)topk_modes_state_stride(N);
+    hipLaunchKernelGGL(topk_modes_kernel<true>, grid, dim3(kTopkThreads), 0, stream, scores, R, (long)r_batch_stride, (long)N,
+                       Ns, (long)n_offset, K, 0, tau, reinterpret_cast<key_t*>(state), reinterpret_cast<key_t*>(keys));
+    for (int j = 1; j < K; ++j)
+        hipLaunchKernelGGL(topk_modes_kernel<false>, grid, dim3(kTopkThreads), 0, stream, scores, R, (long)r_batch_stride,
+                           (long)N, Ns, (long)n_offset, K, j, tau, reinterpret_cast<key_t*>(state),
+                           reinterpret_cast<key_t*>(keys));
     return hipGetLastError();
 }
 

@@ -63,6 +63,43 @@ def all_gather_topk(keys: torch.Tensor, group=None, merge_fn: Optional[Callable]
     return merge_fn(lists)
 
 
+def all_gather_scores(scores_local: torch.Tensor, n_total: int, group=None, force: bool = False,
+                      out: Optional[torch.Tensor] = None, staging: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The full score row ``(B, n_total)`` from this rank's slice ``(B, hi - lo)`` of ``shard_range(n_total, rank, world)``:
+    ONE all-gather of ``4*B*ceil(n_total / world)`` bytes per rank.  What a selection that does not compose across shards
+    needs (``ops.topk_modes``: a shard's local winner can suppress a hypothesis the global selection keeps): every rank then
+    selects over the whole row and gets the same list bit for bit, however N was cut.  ``shard_range`` cuts unevenly, so the
+    slices are padded to the largest shard and the padding is stripped.  ``out (B, n_total)`` and ``staging
+    (world + 1, B, ceil(n_total / world))`` given: no allocation (capture).  With no process group (or a world of one,
+    unless ``force``) the slice is returned as it is."""
+    inited = dist.is_available() and dist.is_initialized()
+    world = dist.get_world_size(group) if inited else 1
+    if not inited or (world == 1 and not force):
+        if scores_local.shape[1] != n_total:
+            raise ValueError("local scores hold %d hypotheses, expected %d" % (scores_local.shape[1], n_total))
+        return scores_local
+    rank = dist.get_rank(group)
+    lo, hi = shard_range(n_total, rank, world)
+    B = scores_local.shape[0]
+    if scores_local.shape[1] != hi - lo:
+        raise ValueError("local scores hold %d hypotheses, shard expects %d" % (scores_local.shape[1], hi - lo))
+    width = -(-n_total // world)
+    if staging is None:
+        staging = torch.empty((world + 1, B, width), dtype=scores_local.dtype, device=scores_local.device)
+    if out is None:
+        out = torch.empty((B, n_total), dtype=scores_local.dtype, device=scores_local.device)
+    mine = staging[world]
+    mine[:, :hi - lo].copy_(scores_local)
+    if hi - lo < width:
+        mine[:, hi - lo:].zero_()
+    # the concatenated form (world*B, width): what every backend accepts (gloo refuses the stacked shape)
+    dist.all_gather_into_tensor(staging[:world].view(world * B, width), mine, group=group)
+    for r in range(world):
+        a, b = shard_range(n_total, r, world)
+        out[:, a:b].copy_(staging[r, :, :b - a])
+    return out
+
+
 # ---- host-side key codec (numpy): used by host logic and CPU tests ------------------
 
 def pack_keys_host(scores: np.ndarray, idx: np.ndarray) -> np.ndarray:

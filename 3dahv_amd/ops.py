@@ -682,6 +682,77 @@ def verify_pair_topk(vol_src: torch.Tensor, vol_tgt: torch.Tensor, R: torch.Tens
     return out + (r[2],) if want_feat_tgt else out
 
 
+# ---- distinct pose modes --------------------------------------------------------------------------------------
+# (device, B, N) -> alive-state workspace of topk_modes: static like _TOPK_WS, and under the same rule (one stream per shape)
+_MODES_WS = {}
+
+
+def min_trace(min_angle_deg) -> float:
+    """``tau = 1 + 2 cos(theta)`` in double precision, rounded to fp32: what ``ahv_topk_modes_f32`` takes as ``min_trace``."""
+    theta = float(min_angle_deg)
+    if not 0.0 < theta < 180.0:
+        raise RuntimeError("min_angle_deg = %r outside (0, 180)" % (min_angle_deg,))
+    tau = float(torch.tensor(1.0 + 2.0 * math.cos(math.radians(theta)), dtype=torch.float64).to(torch.float32))
+    if not -1.0 < tau < 3.0:
+        raise RuntimeError("min_angle_deg = %r: 1 + 2 cos(theta) rounds to %r in fp32, outside (-1, 3)" % (min_angle_deg, tau))
+    return tau
+
+
+def topk_modes_workspace(B: int, N: int, k: int, device) -> torch.Tensor | None:
+    """A workspace for ``topk_modes`` on (B, N, k): allocate it once, pass it to every call (no allocation under capture)."""
+    nbytes = _lib.load().ahv_topk_modes_workspace_bytes(B, N, _topk_k(k))
+    return torch.empty((nbytes // 8,), dtype=torch.int64, device=device) if nbytes else None
+
+
+@torch.no_grad()
+def topk_modes(scores: torch.Tensor, R: torch.Tensor, k: int, min_angle_deg: float, n_offset: int = 0,
+               keys: torch.Tensor | None = None, workspace: torch.Tensor | None = None):
+    """Up to K distinct pose modes of ``scores (B,N)`` over the hypotheses ``R (N,3,3)`` / ``(B,N,3,3)`` as packed keys
+    ``(B,K)`` (``ahv_topk_modes_f32``): the K-best order with every hypothesis within ``min_angle_deg`` of an earlier entry
+    left out, padded with AHV_KEY_EMPTY when the set holds fewer modes.  ``keys`` is OVERWRITTEN (modes do not merge: select
+    once over the whole set -- ``dist.all_gather_scores`` for shards); ``workspace``: an int64 tensor of
+    ``ahv_topk_modes_workspace_bytes`` bytes (``topk_modes_workspace``), else a static one per shape.  With both given the call
+    allocates nothing.  Decode with ``select_topk``."""
+    if scores.dim() != 2:
+        raise RuntimeError("scores must be (B,N)")
+    k = _topk_k(k)
+    tau = min_trace(min_angle_deg)
+    dev = _need_gpu(scores, R)
+    B, N = scores.shape
+    n_rot, rstride = _rot_layout(R, B)
+    if n_rot != N:
+        raise RuntimeError("R holds %d hypotheses, scores %d" % (n_rot, N))
+    if keys is None:
+        keys = torch.empty((B, k), dtype=torch.int64, device=dev)
+    elif _topk_list(keys) != (B, k) or keys.device != dev:
+        raise RuntimeError("keys must be a (B,K) = %s int64 tensor on %s" % ((B, k), dev))
+    s, Rc = scores.detach().contiguous(), R.detach().contiguous()
+    nbytes = _lib.load().ahv_topk_modes_workspace_bytes(B, N, k)
+    if workspace is None and nbytes:
+        workspace = _MODES_WS.get((dev, B, N))
+        if workspace is None:
+            workspace = _MODES_WS[(dev, B, N)] = torch.empty((nbytes // 8,), dtype=torch.int64, device=dev)
+    have = 0
+    if workspace is not None:
+        if workspace.device != dev or not workspace.is_contiguous():
+            raise RuntimeError("workspace must be a contiguous tensor on %s" % dev)
+        have = workspace.numel() * workspace.element_size()
+    _call(dev, "ahv_topk_modes_f32", s.data_ptr(), Rc.data_ptr(), rstride, B, N, n_offset, k, tau, keys.data_ptr(),
+          workspace.data_ptr() if workspace is not None else None, have)
+    return keys
+
+
+def verify_pair_modes(vol_src: torch.Tensor, vol_tgt: torch.Tensor, R: torch.Tensor, W1: torch.Tensor, W2: torch.Tensor,
+                      b2: torch.Tensor, k: int, min_angle_deg: float, keys: torch.Tensor | None = None,
+                      workspace: torch.Tensor | None = None, **kw):
+    """The verify step with distinct modes: ``verify_pair`` with the scores kept -> ``topk_modes`` -> ``select_topk``.
+    Returns ``(mode_scores (B,K), mode_idx (B,K), R_modes (B,K,3,3))``; a slot past the last mode holds -inf, -1 and a zero
+    matrix.  Other keywords go to ``verify_pair``."""
+    k = _topk_k(k)
+    scores = verify_pair(vol_src, vol_tgt, R, W1, W2, b2, want_scores=True, **kw)[0]
+    return select_topk(topk_modes(scores, R, k, min_angle_deg, keys=keys, workspace=workspace), R)
+
+
 # ---- rotation gradient of the score, gradient-based pose polishing ------------------------------------------
 
 @torch.no_grad()

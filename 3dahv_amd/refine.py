@@ -26,7 +26,7 @@ import torch
 import torch.distributed as dist
 
 from . import ops
-from .dist import KEY_EMPTY, all_gather_topk, shard_range
+from .dist import KEY_EMPTY, all_gather_scores, all_gather_topk, shard_range
 from .rotations import refine_rotations
 
 
@@ -56,6 +56,20 @@ class CoarseToFine:
     (B,K).  Seed 0's refinements are the single-seed step's, score for score, so the fine score never falls below it.
     ``seeds=1`` is the step described above, unchanged.  The one-launch kernel is not extended: ``fused`` with
     ``seeds > 1`` raises.
+    ``modes=K`` with ``mode_angle_deg=theta`` (mode-seeded refinement): the K seeds are the K best DISTINCT coarse poses --
+    ``ops.topk_modes``: the K-best order with every hypothesis within theta of an earlier seed left out -- instead of the K
+    largest scores, which neighbours of one peak fill.  The step is the multi-seed one with that selection in its place.
+    Modes do not compose across shards, so a multi-rank step gathers the coarse scores (``dist.all_gather_scores``,
+    4*B*N1/world bytes per rank, in place of the list all-gather) and every rank selects over the whole row: the same list
+    bit for bit however N1 was cut.  Fewer than K modes: the list ends in EMPTY slots; their refinement blocks are composed
+    around row 0 to stay in bounds and scored, but take no part in any result.  ``self.last["modes"] = (scores, idx, R)``,
+    (B,K), (B,K), (B,K,3,3): each mode's own best refinement, ``idx`` inside its N2-block (-inf, -1 and zeros for an EMPTY
+    mode) -- ``argmax`` / ``select_rotation`` on the (B*K, N2) view of the fine scores; multi-rank, the N2-blocks are cut
+    across ranks and the second all-reduce carries the (B,K) per-block keys instead of the (B,) key: still two collectives.
+    The fine winner returned is the best of those (fine index ``mode * N2 + idx``), ``self.last["coarse_topk"]`` the coarse
+    modes.  With ``polish_iters > 0`` all K per-mode poses are polished (``self.last["polish"]`` is (B,K)-shaped) and the
+    best polished one is returned.  ``modes=1`` gives the ``seeds=1`` step's outputs bit for bit.  Exclusive with
+    ``seeds > 1`` and with ``fused``: both raise.
     ``polish_iters > 0`` (gradient-based polishing, ``ops.polish_rotations``): after the fine stage the fine winner takes
     ``polish_iters`` ascent steps on SO(3) along the rotation gradient of the score.  The fine score and ``R_pred`` returned are
     the polished ones (never below the fine winner's: an ascent step keeps the incumbent unless a candidate scores strictly
@@ -71,7 +85,7 @@ class CoarseToFine:
                  batch: int = 1, use_graph: Optional[bool] = None, group=None, seed: int = 0, backend=None,
                  want_scores: bool = False, force_collectives: bool = False, no_teams: bool = False,
                  fused: Optional[bool] = None, seeds: int = 1, polish_iters: int = 0, polish_angle_deg: float = 2.0,
-                 polish_ladder=(0.25, 0.5, 1.0, 2.0)):
+                 polish_ladder=(0.25, 0.5, 1.0, 2.0), modes: int = 0, mode_angle_deg: float = 15.0):
         dev = R_coarse.device
         self.ops = ops if backend is None else backend
         self.W1, self.W2, self.b2 = W1, W2, b2
@@ -97,6 +111,19 @@ class CoarseToFine:
         if self.seeds > 1 and fused:
             raise RuntimeError("the one-launch step (fused=True) refines around ONE seed; seeds = %d needs fused=False"
                                % self.seeds)
+        self.modes = int(modes)
+        if self.modes:
+            if not 1 <= self.modes <= 64:
+                raise RuntimeError("modes = %d outside 1..64" % self.modes)
+            if self.seeds > 1:
+                raise RuntimeError("modes = %d and seeds = %d are two selections of the stage-2 seeds: pass one of them"
+                                   % (self.modes, self.seeds))
+            if fused:
+                raise RuntimeError("the one-launch step (fused=True) refines around ONE seed; modes = %d needs fused=False"
+                                   % self.modes)
+            self.mode_angle_deg = float(mode_angle_deg)
+            ops.min_trace(self.mode_angle_deg)   # raises outside (0, 180)
+            self.seeds = self.modes              # the stage-2 layout is the multi-seed one: K blocks of N2
         self.polish_iters = int(polish_iters)
         if self.polish_iters < 0:
             raise RuntimeError("polish_iters must be >= 0")
@@ -123,7 +150,17 @@ class CoarseToFine:
         # the two keys live with the object: every step's select hands them back empty
         self._keys = [torch.full((batch,), KEY_EMPTY, dtype=torch.int64, device=dev) for _ in range(2)]
         self._R_fine = torch.empty((batch, self.seeds * self.D.shape[0], 3, 3), dtype=torch.float32, device=dev)
-        self._klist = (torch.full((batch, self.seeds), KEY_EMPTY, dtype=torch.int64, device=dev) if self.seeds > 1 else None)
+        self._klist = (torch.full((batch, self.seeds), KEY_EMPTY, dtype=torch.int64, device=dev)
+                       if self.seeds > 1 or self.modes else None)
+        if self.modes:   # everything the mode selection and the per-mode results write to lives with the object
+            n1, K = self.R_coarse.shape[-3], self.modes
+            self._block_keys = torch.full((batch, K), KEY_EMPTY, dtype=torch.int64, device=dev)
+            self._block_off = (torch.arange(K, dtype=torch.int64, device=dev) * self.D.shape[0])[None]
+            self._modes_ws = (ops.topk_modes_workspace(batch, n1, K, dev) if backend is None and dev.type == "cuda" else None)
+            self._s_all = self._s_stage = None
+            if self.collectives:
+                self._s_all = torch.empty((batch, n1), dtype=torch.float32, device=dev)
+                self._s_stage = torch.empty((self.world + 1, batch, -(-n1 // self.world)), dtype=torch.float32, device=dev)
         self._graph = None
         self._static = None
         can_fuse = backend is None and not self.collectives and self.world == 1 and dev.type == "cuda"
@@ -158,6 +195,8 @@ class CoarseToFine:
             # (the refinement set is never materialised here: R_fine stays None)
             self.last = {"coarse_scores": r.get("coarse_scores"), "fine_scores": r.get("fine_scores"), "R_fine": None}
             return r["fine_score"], r["fine_idx"], r["R_pred"], r["coarse_score"], r["coarse_idx"]
+        if self.modes:
+            return self._step_modes(vol_src, vol_tgt, slot)
         if self.seeds > 1:
             return self._step_seeds(vol_src, vol_tgt, slot)
         key1, key2 = self._keys
@@ -216,6 +255,53 @@ class CoarseToFine:
         self.last = {"coarse_scores": s1 if self.want_scores else None, "fine_scores": s2,
                      "R_fine": R_fine if self.want_scores else None, "coarse_topk": (top_scores, top_idx)}
         score, R_pred = self._polish(vol_src, f_tgt, score, R_pred, slot)
+        return score, idx, R_pred, top_scores[:, 0], top_idx[:, 0]
+
+    def _step_modes(self, vol_src, vol_tgt, slot: int = 0):
+        """The step with ``modes = K``: ``_step_seeds`` with ``topk_modes`` over the whole coarse row in place of ``topk``."""
+        o = self.ops
+        K, N2, B = self.modes, self.D.shape[0], self.B
+        kw = {"no_teams": True} if self.no_teams else {}
+        Rc = self.R_coarse[self.c_lo:self.c_hi]
+        s1, _, f_tgt = o.verify_pair(vol_src, vol_tgt, Rc, self.W1, self.W2, self.b2, n_offset=self.c_lo, want_scores=True,
+                                     want_feat_tgt=True, **kw)
+        s_all = s1
+        if self.collectives:  # modes do not compose across shards: the whole row on every rank, then ONE selection
+            s_all = all_gather_scores(s1, self.R_coarse.shape[-3], group=self.group, force=True, out=self._s_all,
+                                      staging=self._s_stage)
+        klist = o.topk_modes(s_all, self.R_coarse, K, self.mode_angle_deg, keys=self._klist, workspace=self._modes_ws)
+        R_fine_all = o.compose_rotations_topk(klist, self.R_coarse, self.D, out=self._R_fine)
+        R_fine = R_fine_all if self.world == 1 else R_fine_all[:, self.f_lo:self.f_hi]
+        s2, _ = o.score_hypotheses(vol_src, f_tgt, R_fine, self.W1, self.W2, self.b2, n_offset=self.f_lo, want_scores=True, **kw)
+        # each mode's best refinement: the arg-max key of every N2-block (index inside the block) that this rank scored
+        bk = self._block_keys
+        if self.world == 1:
+            bk.copy_(o.argmax(s2.view(B * K, N2), return_key=True).view(B, K))
+        else:
+            bk.fill_(KEY_EMPTY)
+            for k in range(self.f_lo // N2, (self.f_hi - 1) // N2 + 1 if self.f_hi > self.f_lo else 0):
+                a, b = max(self.f_lo, k * N2), min(self.f_hi, (k + 1) * N2)
+                bk[:, k] = o.argmax(s2[:, a - self.f_lo:b - self.f_lo].contiguous(), n_offset=a - k * N2, return_key=True)
+        self._merge(bk)   # the second collective, (B,K) keys wide
+        bk = torch.where(klist == KEY_EMPTY, klist, bk)   # an EMPTY mode's block was composed around row 0: no result
+        m_score, m_idx, m_R = o.select_rotation(bk.view(B * K), R_fine_all.view(B * K, N2, 3, 3), n_offset=0)
+        m_score, m_idx, m_R = m_score.view(B, K), m_idx.view(B, K), m_R.view(B, K, 3, 3)
+        # the fine winner: the same keys with the index moved to mode * N2 + idx (the index word counts down: no borrow)
+        key2 = torch.where(bk == KEY_EMPTY, bk, bk - self._block_off).max(dim=1).values
+        score, idx, R_pred = o.select_rotation(key2, R_fine_all, n_offset=0)
+        top_scores, top_idx, _ = o.select_topk(klist, self.R_coarse, n_offset=0)
+        self.last = {"coarse_scores": s_all if self.want_scores else None, "fine_scores": s2,
+                     "R_fine": R_fine if self.want_scores else None, "coarse_topk": (top_scores, top_idx),
+                     "modes": (m_score, m_idx, m_R)}
+        if self.polish_iters > 0:
+            R, s, theta = o.polish_rotations(vol_src, f_tgt, m_R, self.W1, self.W2, self.b2, iters=self.polish_iters,
+                                             init_angle_deg=self.polish_angle_deg, ladder=self.polish_ladder,
+                                             out=self._polish_out.setdefault(slot, {}))
+            s = torch.where(bk == KEY_EMPTY, m_score, s)   # an EMPTY mode (a zero matrix went in) stays at -inf
+            self.last["polish"] = {"score_before": m_score, "R_before": m_R, "score_after": s, "R_after": R, "theta": theta}
+            score, best = s.max(dim=1)
+            R_pred = R[torch.arange(B, device=R.device), best]
+            idx = best * N2 + m_idx[torch.arange(B, device=R.device), best]
         return score, idx, R_pred, top_scores[:, 0], top_idx[:, 0]
 
     def check(self):
