@@ -23,6 +23,8 @@ AHV_KEY_EMPTY = -(1 << 63)
 AHV_TOPK_MAX_K = 64
 AHV_TOPK_RESET_LIST = 1
 AHV_SO3_MAX_LADDER = 8
+AHV_POSTERIOR_MAX_MODES = 16
+AHV_POSTERIOR_RESET_STATE = 1
 
 _vp = ctypes.c_void_p
 _i64 = ctypes.c_int64
@@ -89,6 +91,12 @@ SIGNATURES["ahv_score_rotation_grad_f32"] = (_int, [_vp, _vp, _vp, _i64, _vp, _v
                                                     _vp, _vp])
 SIGNATURES["ahv_so3_ascent_candidates_f32"] = (_int, [_vp, _vp, _vp, _vp, _int, _int, _int, _vp, _vp])
 SIGNATURES["ahv_so3_ascent_select_f32"] = (_int, [_vp, _vp, _vp, _int, _int, _int, _vp, _vp, _vp, _vp])
+SIGNATURES["ahv_pose_posterior_state_bytes"] = (ctypes.c_size_t, [_int, _int])
+SIGNATURES["ahv_pose_posterior_workspace_bytes"] = (ctypes.c_size_t, [_int, _i64, _int])
+SIGNATURES["ahv_pose_posterior_f32"] = (_int, [_vp, _vp, _i64, _int, _i64, _vp, _int, ctypes.c_float, ctypes.c_float, _vp, _vp,
+                                               ctypes.c_size_t, _u32, _vp])
+SIGNATURES["ahv_pose_posterior_merge"] = (_int, [_vp, _int, _int, _int, ctypes.c_float, _vp, _u32, _vp])
+SIGNATURES["ahv_pose_posterior_finish_f32"] = (_int, [_vp, _int, _int, ctypes.c_float] + [_vp] * 10 + [_vp])
 
 # measurement / developer entry points (include/ahv_diag.h): not part of the drop-in boundary
 DIAG_SIGNATURES = {

@@ -35,6 +35,13 @@ hipError_t launch_compose_rotations_topk(const int64_t*, int, const float*, int6
 int64_t topk_modes_state_stride(int64_t N);
 hipError_t launch_topk_modes(const float*, const float*, int64_t, int, int64_t, int64_t, int, float, int64_t*, int64_t*,
                              hipStream_t);
+size_t posterior_state_stride(int K);
+int posterior_parts(int64_t N);
+hipError_t launch_posterior(const float*, const float*, int64_t, int, int64_t, const float*, int, float, float, void*, void*, bool,
+                            hipStream_t);
+hipError_t launch_posterior_merge(const void*, int, int, int, float, void*, bool, hipStream_t);
+hipError_t launch_posterior_finish(const void*, int, int, float, float*, float*, float*, int64_t*, float*, float*, float*, float*,
+                                   float*, float*, hipStream_t);
 hipError_t launch_random_rotations(uint64_t, uint64_t, int64_t, float*, hipStream_t);
 hipError_t launch_so3_grid(int64_t, int64_t, int64_t, float*, hipStream_t);
 hipError_t launch_score_backward(const float*, const float*, const float*, int64_t, const float*, const float*,
@@ -657,6 +664,91 @@ int ahv_topk_modes_f32(const float* scores, const float* R, int64_t r_batch_stri
     hipError_t e = ahv::launch_topk_modes(scores, R, r_batch_stride, B, N, n_offset, K, min_trace, keys,
                                           static_cast<int64_t*>(workspace), s);
     if (e != hipSuccess) return hip_fail("topk_modes: launch", e);
+    return AHV_OK;
+}
+
+// ---- pose posterior ----------------------------------------------------------------------------------------
+static bool bad_modes(int K) { return K < 0 || K > AHV_POSTERIOR_MAX_MODES; }
+static bool bad_beta(float beta) { return !(beta > 0.0f && beta < __builtin_inff()); }   // false for a NaN
+
+size_t ahv_pose_posterior_state_bytes(int B, int K)
+{
+    if (B <= 0 || bad_modes(K)) return 0;
+    return (size_t)B * ahv::posterior_state_stride(K);
+}
+
+size_t ahv_pose_posterior_workspace_bytes(int B, int64_t N, int K)
+{
+    if (B <= 0 || N <= 0 || bad_modes(K)) return 0;
+    return (size_t)ahv::posterior_parts(N) * (size_t)B * ahv::posterior_state_stride(K);   // one partial state per workgroup
+}
+
+int ahv_pose_posterior_f32(const float* scores, const float* R, int64_t r_batch_stride, int B, int64_t N, const float* anchors,
+                           int K, float min_trace, float beta, void* state, void* workspace, size_t workspace_bytes,
+                           unsigned flags, void* stream)
+{
+    if (bad_modes(K)) return fail(AHV_EINVAL, "pose_posterior: K = %d outside 0..%d", K, AHV_POSTERIOR_MAX_MODES);
+    if (B < 0 || N < 0) return fail(AHV_EINVAL, "pose_posterior: negative size");
+    if (B > 65535) return fail(AHV_EINVAL, "pose_posterior: B > 65535");
+    if (bad_beta(beta)) return fail(AHV_EINVAL, "pose_posterior: beta = %g must be finite and > 0 (1 / temperature)", (double)beta);
+    if (!(min_trace > -1.0f && min_trace < 3.0f))   // false for a NaN
+        return fail(AHV_EINVAL, "pose_posterior: min_trace = %g outside (-1, 3) (1 + 2 cos theta, 0 < theta < 180 degrees)",
+                    (double)min_trace);
+    if (r_batch_stride != 0 && r_batch_stride != N * 9)
+        return fail(AHV_EINVAL, "pose_posterior: r_batch_stride %lld must be 0 or N*9", (long long)r_batch_stride);
+    if (flags & ~AHV_POSTERIOR_RESET_STATE) return fail(AHV_EINVAL, "pose_posterior: unknown flags 0x%x", flags);
+    if (B == 0) return AHV_OK;
+    if (!state || (N > 0 && (!scores || !R)) || (K > 0 && N > 0 && !anchors)) return fail(AHV_EINVAL, "pose_posterior: null pointer");
+    if (reinterpret_cast<uintptr_t>(state) & 15) return fail(AHV_EINVAL, "pose_posterior: state must be 16-byte aligned");
+    const size_t need = ahv_pose_posterior_workspace_bytes(B, N, K);
+    if (need && (!workspace || workspace_bytes < need || (reinterpret_cast<uintptr_t>(workspace) & 15)))
+        return fail(AHV_EINVAL, "pose_posterior: needs a 16-byte aligned workspace of %zu bytes (ahv_pose_posterior_workspace_bytes), "
+                    "got %zu", need, workspace_bytes);
+    const bool reset = (flags & AHV_POSTERIOR_RESET_STATE) != 0;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (N == 0) {
+        if (!reset) return AHV_OK;
+        hipError_t e = ahv::launch_posterior_merge(nullptr, 0, B, K, beta, state, false, s);   // an empty state
+        if (e != hipSuccess) return hip_fail("pose_posterior: state reset", e);
+        return AHV_OK;
+    }
+    hipError_t e = ahv::launch_posterior(scores, R, r_batch_stride, B, N, anchors, K, min_trace, beta, state, workspace, !reset, s);
+    if (e != hipSuccess) return hip_fail("pose_posterior: launch", e);
+    return AHV_OK;
+}
+
+int ahv_pose_posterior_merge(const void* states, int P, int B, int K, float beta, void* state, unsigned flags, void* stream)
+{
+    if (bad_modes(K)) return fail(AHV_EINVAL, "pose_posterior_merge: K = %d outside 0..%d", K, AHV_POSTERIOR_MAX_MODES);
+    if (B < 0 || P < 0) return fail(AHV_EINVAL, "pose_posterior_merge: negative size");
+    if (B > 65535) return fail(AHV_EINVAL, "pose_posterior_merge: B > 65535");
+    if (bad_beta(beta)) return fail(AHV_EINVAL, "pose_posterior_merge: beta = %g must be finite and > 0 (1 / temperature)", (double)beta);
+    if (flags & ~AHV_POSTERIOR_RESET_STATE) return fail(AHV_EINVAL, "pose_posterior_merge: unknown flags 0x%x", flags);
+    if (B == 0) return AHV_OK;
+    if (!state || (P > 0 && !states)) return fail(AHV_EINVAL, "pose_posterior_merge: null pointer");
+    if ((reinterpret_cast<uintptr_t>(state) & 15) || (reinterpret_cast<uintptr_t>(states) & 15))
+        return fail(AHV_EINVAL, "pose_posterior_merge: states must be 16-byte aligned");
+    const bool reset = (flags & AHV_POSTERIOR_RESET_STATE) != 0;
+    if (P == 0 && !reset) return AHV_OK;
+    hipError_t e = ahv::launch_posterior_merge(states, P, B, K, beta, state, !reset, static_cast<hipStream_t>(stream));
+    if (e != hipSuccess) return hip_fail("pose_posterior_merge: launch", e);
+    return AHV_OK;
+}
+
+int ahv_pose_posterior_finish_f32(const void* state, int B, int K, float beta, float* log_z, float* entropy, float* mean_score,
+                                  int64_t* n_excluded, float* mode_prob, float* rest_prob, float* mode_R_mean, float* R_mean,
+                                  float* mode_spread_deg, float* spread_deg, void* stream)
+{
+    if (bad_modes(K)) return fail(AHV_EINVAL, "pose_posterior_finish: K = %d outside 0..%d", K, AHV_POSTERIOR_MAX_MODES);
+    if (B < 0) return fail(AHV_EINVAL, "pose_posterior_finish: negative size");
+    if (B > 65535) return fail(AHV_EINVAL, "pose_posterior_finish: B > 65535");
+    if (bad_beta(beta)) return fail(AHV_EINVAL, "pose_posterior_finish: beta = %g must be finite and > 0 (1 / temperature)", (double)beta);
+    if (B == 0) return AHV_OK;
+    if (!state) return fail(AHV_EINVAL, "pose_posterior_finish: null state");
+    if (reinterpret_cast<uintptr_t>(state) & 15) return fail(AHV_EINVAL, "pose_posterior_finish: state must be 16-byte aligned");
+    hipError_t e = ahv::launch_posterior_finish(state, B, K, beta, log_z, entropy, mean_score, n_excluded, mode_prob, rest_prob,
+                                                mode_R_mean, R_mean, mode_spread_deg, spread_deg, static_cast<hipStream_t>(stream));
+    if (e != hipSuccess) return hip_fail("pose_posterior_finish: launch", e);
     return AHV_OK;
 }
 

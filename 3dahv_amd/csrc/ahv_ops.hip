@@ -904,6 +904,404 @@ __global__ __launch_bounds__(kTopkThreads) void topk_modes_kernel(const float* _
 }
 
 // ---------------------------------------------------------------------------------
+// Pose posterior (ahv_pose_posterior_f32 / _merge / _finish_f32): softmax statistics of the scored set at inverse temperature
+// beta, split over K anchor buckets (hypothesis i belongs to the FIRST anchor k with t(i, k) >= tau, else to the rest).  What is
+// kept per bucket and for the whole set is a RECORD of kPostRec doubles -- m (the largest score met, -inf when empty), and
+// relative to it mass = sum w, S = sum w s, M = sum w R (9), w = exp((s - m) beta) -- so that two records merge by the
+// online-softmax rule: m = max, each side rescaled by exp((m_side - m) beta).  A sample's STATE is a 16-byte header (int64
+// n_excluded, int64 reserved) and K + 2 records: buckets 0 .. K-1, the rest bucket, the whole set.
+//  - posterior_partial_kernel: ONE pass over scores and R on the grid rule of the top-K / modes kernels (tiles of kTopkTile,
+//    four consecutive hypotheses per lane, 16-byte loads where THAT ADDRESS is aligned).  The anchors sit in LDS.  A lane keeps
+//    online-softmax sums (fp32 weights, fp64 sums) for the whole set and the rest bucket; a mode bucket is hit rarely and is reduced wave-wide, only
+//    when a ballot says some lane hit it, into the wave's LDS row in program order.  Wave sums are DPP row operations in fp64,
+//    the four waves are combined in the order 0..3, one partial state per workgroup goes to the workspace.
+//  - posterior_merge_kernel: states [P][B] -> state [B] in the order p = 0 .. P-1 (into the state, or from empty): the second
+//    launch of a call and the merge after an all-gather.
+//  - posterior_finish_kernel: a state -> the outputs; the rotation nearest to M is the top eigenvector of Horn's 4 x 4
+//    quaternion matrix (the maximiser of sum R o M over SO(3) = U diag(1, 1, det(U V^T)) V^T), by cyclic Jacobi in fp64.
+// No floating-point atomics: for a given (B, N, K) every sum is taken in one fixed order, so results are bitwise reproducible.
+// ---------------------------------------------------------------------------------
+constexpr int kPostMaxModes = 16;
+constexpr int kPostRec = 12;      // doubles per record: m, mass, S, M[9]
+constexpr int kPostHeader = 16;   // bytes: int64 n_excluded, int64 reserved (0)
+
+__host__ __device__ constexpr size_t posterior_state_stride_dev(int K) { return (size_t)kPostHeader + (size_t)(K + 2) * kPostRec * sizeof(double); }
+size_t posterior_state_stride(int K) { return posterior_state_stride_dev(K); }
+
+int posterior_parts(int64_t N)
+{
+    const int64_t tiles = (N + kTopkTile - 1) / kTopkTile;
+    return (int)(tiles < kTopkMaxParts ? tiles : kTopkMaxParts);
+}
+
+struct PostAcc {  // one lane's online-softmax sums: the weights are fp32 (expf), the sums fp64 -- S / mass - m cancels, and an fp32
+    float m;      // S would put its own rounding (times beta) into the entropy of a peaked distribution
+    double mass, S, M[9];
+};
+
+__device__ __forceinline__ void post_clear(PostAcc& a)
+{
+    a.m = -INFINITY;
+    a.mass = 0.0;
+    a.S = 0.0;
+#pragma unroll
+    for (int i = 0; i < 9; ++i) a.M[i] = 0.0;
+}
+
+__device__ __forceinline__ void post_add(PostAcc& a, float s, const float* r, float beta)
+{
+    if (s > a.m) {  // a new maximum: rescale what is there (by 0 when nothing is: m = -inf)
+        const double f = (double)expf((a.m - s) * beta);
+        a.mass *= f;
+        a.S *= f;
+#pragma unroll
+        for (int i = 0; i < 9; ++i) a.M[i] *= f;
+        a.m = s;
+    }
+    const double w = (double)expf((s - a.m) * beta);
+    a.mass += w;
+    a.S = fma(w, (double)s, a.S);
+#pragma unroll
+    for (int i = 0; i < 9; ++i) a.M[i] = fma(w, (double)r[i], a.M[i]);
+}
+
+// dst <- dst merged with src (records of kPostRec doubles), dst's side first
+__device__ __forceinline__ void post_merge(double* dst, const double* src, double beta)
+{
+    const double ma = dst[0], mb = src[0];
+    const double m = mb > ma ? mb : ma;
+    if (m == -INFINITY) return;  // both empty
+    const double fa = ma == -INFINITY ? 0.0 : exp((ma - m) * beta), fb = mb == -INFINITY ? 0.0 : exp((mb - m) * beta);
+    dst[0] = m;
+#pragma unroll
+    for (int i = 1; i < kPostRec; ++i) dst[i] = dst[i] * fa + src[i] * fb;
+}
+
+template <int kCtrl, int kRows, int kBanks>
+__device__ __forceinline__ double sum_f64_dpp_step(double x)
+{
+    const unsigned long long u = __builtin_bit_cast(unsigned long long, x);
+    const unsigned lo = (unsigned)__builtin_amdgcn_update_dpp(0, (int)(unsigned)u, kCtrl, kRows, kBanks, true);
+    const unsigned hi = (unsigned)__builtin_amdgcn_update_dpp(0, (int)(unsigned)(u >> 32), kCtrl, kRows, kBanks, true);
+    return x + __builtin_bit_cast(double, ((unsigned long long)hi << 32) | lo);
+}
+
+// sum over the 64 lanes in the order of wave_sum_dpp, in fp64; valid in lane 63
+__device__ __forceinline__ double wave_sum_dpp_f64(double x)
+{
+    x = sum_f64_dpp_step<0x111, 0xF, 0xF>(x);  // row_shr:1
+    x = sum_f64_dpp_step<0x112, 0xF, 0xF>(x);  // row_shr:2
+    x = sum_f64_dpp_step<0x114, 0xF, 0xE>(x);  // row_shr:4
+    x = sum_f64_dpp_step<0x118, 0xF, 0xC>(x);  // row_shr:8
+    x = sum_f64_dpp_step<0x142, 0xA, 0xF>(x);  // row_bcast:15
+    x = sum_f64_dpp_step<0x143, 0xC, 0xF>(x);  // row_bcast:31
+    return x;
+}
+
+template <int kCtrl, int kRows>
+__device__ __forceinline__ float max_f32_dpp_step(float x)
+{
+    const int xi = __builtin_bit_cast(int, x);
+    const float o = __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(xi, xi, kCtrl, kRows, 0xF, false));
+    return o > x ? o : x;
+}
+
+// the wave's largest value (no NaN among the inputs: they are finite scores or -inf), in every lane
+__device__ __forceinline__ float wave_max_f32_dpp(float x)
+{
+    x = max_f32_dpp_step<0x111, 0xF>(x);
+    x = max_f32_dpp_step<0x112, 0xF>(x);
+    x = max_f32_dpp_step<0x114, 0xF>(x);
+    x = max_f32_dpp_step<0x118, 0xF>(x);
+    x = max_f32_dpp_step<0x142, 0xA>(x);
+    x = max_f32_dpp_step<0x143, 0xC>(x);
+    return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, x), 63));
+}
+
+// the 64 lanes' sums as one record, merged into row (LDS) by lane 63.  Called by whole waves only.
+__device__ __forceinline__ void post_wave_into(const PostAcc& a, double beta, double* row)
+{
+    const float mw = wave_max_f32_dpp(a.m);
+    const double f = a.m == -INFINITY ? 0.0 : exp(((double)a.m - (double)mw) * beta);
+    double rec[kPostRec];
+    rec[0] = (double)mw;
+    rec[1] = wave_sum_dpp_f64(f * a.mass);
+    rec[2] = wave_sum_dpp_f64(f * a.S);
+#pragma unroll
+    for (int i = 0; i < 9; ++i) rec[3 + i] = wave_sum_dpp_f64(f * a.M[i]);
+    if ((threadIdx.x & 63) == 63) post_merge(row, rec, beta);
+}
+
+__global__ __launch_bounds__(kTopkThreads) void posterior_partial_kernel(const float* __restrict__ scores, const float* __restrict__ R,
+                                                                         long r_batch_stride, int B, long N,
+                                                                         const float* __restrict__ anchors, int K, float tau,
+                                                                         float beta, char* __restrict__ partial)
+{
+    __shared__ double rows[kTopkThreads / 64][kPostMaxModes + 2][kPostRec];  // per wave: buckets, rest, whole
+    __shared__ float anc[kPostMaxModes][9];
+    __shared__ int used[kPostMaxModes];  // an all-zero anchor is an empty slot: skipped by this flag, not by its value
+    __shared__ int n_excl;
+    const int tid = threadIdx.x, wave = tid >> 6, b = blockIdx.y;
+    const double beta_d = (double)beta;
+    for (int e = tid; e < (kTopkThreads / 64) * (kPostMaxModes + 2) * kPostRec; e += kTopkThreads)
+        (&rows[0][0][0])[e] = (e % kPostRec) == 0 ? (double)-INFINITY : 0.0;
+    if (tid < K * 9) (&anc[0][0])[tid] = anchors[(long)b * K * 9 + tid];
+    if (tid == 0) n_excl = 0;
+    __syncthreads();
+    if (tid < K) {
+        bool any = false;
+#pragma unroll
+        for (int i = 0; i < 9; ++i) any = any || anc[tid][i] != 0.0f;  // true for a NaN entry: its t then matches nothing
+        used[tid] = any ? 1 : 0;
+    }
+    __syncthreads();
+
+    const float* s = scores + (long)b * N;
+    const float* Rb = R + (long)b * r_batch_stride;
+    const long tiles = (N + kTopkTile - 1) / kTopkTile;
+    PostAcc whole, rest;
+    post_clear(whole);
+    post_clear(rest);
+    int excluded = 0;
+    for (long t = blockIdx.x; t < tiles; t += gridDim.x) {  // (uniform over the workgroup: every lane takes every trip)
+        const long n0 = t * kTopkTile + (long)tid * 4;
+        float sc[4], r[4][9];
+        int bk[4];  // K: rest, k < K: bucket k, -1: no such hypothesis / not in the scored set
+        const bool full = n0 + 3 < N;
+        if (full && (reinterpret_cast<unsigned long long>(s + n0) & 15ull) == 0) {
+            const float4 q = *reinterpret_cast<const float4*>(s + n0);
+            sc[0] = q.x; sc[1] = q.y; sc[2] = q.z; sc[3] = q.w;
+        } else {
+#pragma unroll
+            for (int e = 0; e < 4; ++e) sc[e] = n0 + e < N ? s[n0 + e] : 0.0f;
+        }
+        const float* rp = Rb + n0 * 9;
+        if (full && (reinterpret_cast<unsigned long long>(rp) & 15ull) == 0) {
+            float4 q[9];
+#pragma unroll
+            for (int v = 0; v < 9; ++v) q[v] = reinterpret_cast<const float4*>(rp)[v];
+#pragma unroll
+            for (int e = 0; e < 4; ++e)
+#pragma unroll
+                for (int i = 0; i < 9; ++i) {
+                    const int f = e * 9 + i;
+                    const float4 v = q[f >> 2];
+                    r[e][i] = (f & 3) == 0 ? v.x : (f & 3) == 1 ? v.y : (f & 3) == 2 ? v.z : v.w;
+                }
+        } else {
+#pragma unroll
+            for (int e = 0; e < 4; ++e)
+#pragma unroll
+                for (int i = 0; i < 9; ++i) r[e][i] = n0 + e < N ? rp[e * 9 + i] : 0.0f;
+        }
+        bool hit = false;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            const bool exists = n0 + e < N;
+            const bool scored = exists && fabsf(sc[e]) < __builtin_inff();  // false for NaN and +-inf
+            excluded += (exists && !scored) ? 1 : 0;
+            bk[e] = scored ? K : -1;
+        }
+        for (int k = K - 1; k >= 0; --k) {  // descending: the FIRST matching anchor is the one left standing
+            if (!used[k]) continue;
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                float acc = 0.0f;
+#pragma unroll
+                for (int i = 0; i < 9; ++i) acc = fmaf(r[e][i], anc[k][i], acc);
+                bk[e] = (bk[e] >= 0 && acc >= tau) ? k : bk[e];  // false for a NaN t
+            }
+        }
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            if (bk[e] < 0) continue;
+            post_add(whole, sc[e], r[e], beta);
+            if (bk[e] == K) post_add(rest, sc[e], r[e], beta);
+            else hit = true;
+        }
+        if (__ballot(hit)) {  // rare (a 15-degree cap holds 0.1 % of SO(3)); wave-uniform from here on
+            for (int k = 0; k < K; ++k) {
+                const bool mine = bk[0] == k || bk[1] == k || bk[2] == k || bk[3] == k;
+                if (!__ballot(mine)) continue;
+                PostAcc a;
+                post_clear(a);
+#pragma unroll
+                for (int e = 0; e < 4; ++e)
+                    if (bk[e] == k) post_add(a, sc[e], r[e], beta);
+                post_wave_into(a, beta_d, rows[wave][k]);
+            }
+        }
+    }
+    post_wave_into(rest, beta_d, rows[wave][K]);
+    post_wave_into(whole, beta_d, rows[wave][K + 1]);
+    if (excluded) atomicAdd(&n_excl, excluded);  // an integer count: order does not matter
+    __syncthreads();
+    char* st = partial + ((size_t)blockIdx.x * B + b) * posterior_state_stride_dev(K);
+    if (tid < K + 2) {  // the four waves in the order 0..3
+        double rec[kPostRec];
+#pragma unroll
+        for (int i = 0; i < kPostRec; ++i) rec[i] = rows[0][tid][i];
+#pragma unroll
+        for (int w = 1; w < kTopkThreads / 64; ++w) post_merge(rec, rows[w][tid], beta_d);
+        double* dst = reinterpret_cast<double*>(st + kPostHeader) + tid * kPostRec;
+#pragma unroll
+        for (int i = 0; i < kPostRec; ++i) dst[i] = rec[i];
+    }
+    if (tid == 63) {
+        reinterpret_cast<long long*>(st)[0] = n_excl;
+        reinterpret_cast<long long*>(st)[1] = 0;
+    }
+}
+
+// states [P][B] -> state [B], in the order p = 0 .. P-1; carry: state's own content comes first
+__global__ __launch_bounds__(64) void posterior_merge_kernel(const char* __restrict__ states, int P, int B, int K, float beta,
+                                                             char* __restrict__ state, bool carry)
+{
+    const int b = blockIdx.x, j = threadIdx.x;
+    const size_t stride = posterior_state_stride_dev(K);
+    char* dst = state + (size_t)b * stride;
+    if (j < K + 2) {
+        double* d = reinterpret_cast<double*>(dst + kPostHeader) + j * kPostRec;
+        double rec[kPostRec];
+#pragma unroll
+        for (int i = 0; i < kPostRec; ++i) rec[i] = carry ? d[i] : (i == 0 ? (double)-INFINITY : 0.0);
+        for (int p = 0; p < P; ++p) {
+            const double* src = reinterpret_cast<const double*>(states + ((size_t)p * B + b) * stride + kPostHeader) + j * kPostRec;
+            double in[kPostRec];
+#pragma unroll
+            for (int i = 0; i < kPostRec; ++i) in[i] = src[i];
+            post_merge(rec, in, (double)beta);
+        }
+#pragma unroll
+        for (int i = 0; i < kPostRec; ++i) d[i] = rec[i];
+    }
+    if (j == 63) {
+        long long n = carry ? reinterpret_cast<const long long*>(dst)[0] : 0;
+        for (int p = 0; p < P; ++p) n += reinterpret_cast<const long long*>(states + ((size_t)p * B + b) * stride)[0];
+        reinterpret_cast<long long*>(dst)[0] = n;
+        reinterpret_cast<long long*>(dst)[1] = 0;
+    }
+}
+
+// one Jacobi rotation of the symmetric A (4 x 4) in the (P, Q) plane, accumulated into V
+template <int P, int Q>
+__device__ __forceinline__ void jacobi4_rotate(double (&A)[4][4], double (&V)[4][4])
+{
+    const double apq = A[P][Q];
+    if (apq == 0.0) return;
+    const double theta = (A[Q][Q] - A[P][P]) / (2.0 * apq);
+    const double t = (theta >= 0.0 ? 1.0 : -1.0) / (fabs(theta) + sqrt(theta * theta + 1.0));
+    const double c = 1.0 / sqrt(t * t + 1.0), s = t * c;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {  // A <- A J
+        const double akp = A[k][P], akq = A[k][Q];
+        A[k][P] = c * akp - s * akq;
+        A[k][Q] = s * akp + c * akq;
+    }
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {  // A <- J^T A
+        const double apk = A[P][k], aqk = A[Q][k];
+        A[P][k] = c * apk - s * aqk;
+        A[Q][k] = s * apk + c * aqk;
+    }
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const double vkp = V[k][P], vkq = V[k][Q];
+        V[k][P] = c * vkp - s * vkq;
+        V[k][Q] = s * vkp + c * vkq;
+    }
+}
+
+// Rm = the rotation nearest to M (Frobenius), spread = the angle whose cosine is (sum Rm o M - 1) / 2, in degrees.
+// M is a weighted mean of the matrices (already divided by the mass).
+__device__ __forceinline__ void post_project(const double* M, float* Rm, float* spread)
+{
+    double A[4][4] = {{M[0] + M[4] + M[8], M[7] - M[5], M[2] - M[6], M[3] - M[1]},
+                      {M[7] - M[5], M[0] - M[4] - M[8], M[1] + M[3], M[2] + M[6]},
+                      {M[2] - M[6], M[1] + M[3], -M[0] + M[4] - M[8], M[5] + M[7]},
+                      {M[3] - M[1], M[2] + M[6], M[5] + M[7], -M[0] - M[4] + M[8]}};
+    double V[4][4] = {{1, 0, 0, 0}, {0, 1, 0, 0}, {0, 0, 1, 0}, {0, 0, 0, 1}};
+#pragma unroll 1
+    for (int sweep = 0; sweep < 12; ++sweep) {  // cyclic Jacobi converges quadratically: 12 sweeps are far past fp64 for a 4 x 4
+        jacobi4_rotate<0, 1>(A, V);
+        jacobi4_rotate<0, 2>(A, V);
+        jacobi4_rotate<0, 3>(A, V);
+        jacobi4_rotate<1, 2>(A, V);
+        jacobi4_rotate<1, 3>(A, V);
+        jacobi4_rotate<2, 3>(A, V);
+    }
+    double best = A[0][0], q[4] = {V[0][0], V[1][0], V[2][0], V[3][0]};
+#pragma unroll
+    for (int c = 1; c < 4; ++c) {
+        const bool take = A[c][c] > best;
+        best = take ? A[c][c] : best;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) q[k] = take ? V[k][c] : q[k];
+    }
+    const double nn = 1.0 / sqrt(q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3]);
+    const double w = q[0] * nn, x = q[1] * nn, y = q[2] * nn, z = q[3] * nn;
+    const double Rd[9] = {1.0 - 2.0 * (y * y + z * z), 2.0 * (x * y - w * z), 2.0 * (x * z + w * y),
+                          2.0 * (x * y + w * z), 1.0 - 2.0 * (x * x + z * z), 2.0 * (y * z - w * x),
+                          2.0 * (x * z - w * y), 2.0 * (y * z + w * x), 1.0 - 2.0 * (x * x + y * y)};
+    double dot = 0.0;
+#pragma unroll
+    for (int i = 0; i < 9; ++i) dot += Rd[i] * M[i];
+    double cs = (dot - 1.0) * 0.5;
+    cs = cs < -1.0 ? -1.0 : cs > 1.0 ? 1.0 : cs;  // (a NaN stays a NaN)
+    if (Rm) {
+#pragma unroll
+        for (int i = 0; i < 9; ++i) Rm[i] = (float)Rd[i];
+    }
+    if (spread) *spread = (float)(acos(cs) * 57.295779513082320877);
+}
+
+// thread j of block b: bucket j < K, the rest bucket (j = K) or the whole set (j = K + 1)
+__global__ __launch_bounds__(64) void posterior_finish_kernel(const char* __restrict__ state, int B, int K, float beta,
+                                                              float* __restrict__ log_z, float* __restrict__ entropy,
+                                                              float* __restrict__ mean_score, long long* __restrict__ n_excluded,
+                                                              float* __restrict__ mode_prob, float* __restrict__ rest_prob,
+                                                              float* __restrict__ mode_R_mean, float* __restrict__ R_mean,
+                                                              float* __restrict__ mode_spread, float* __restrict__ spread)
+{
+    const int b = blockIdx.x, j = threadIdx.x;
+    if (j >= K + 2) return;
+    const char* st = state + (size_t)b * posterior_state_stride_dev(K);
+    const double* recs = reinterpret_cast<const double*>(st + kPostHeader);
+    const double* all = recs + (K + 1) * kPostRec;
+    const double* me = recs + j * kPostRec;
+    const double bd = (double)beta, m_all = all[0], Z = all[1];
+    const bool empty = !(me[1] > 0.0);  // an empty slot, a bucket without a member, an empty scored set
+    if (j == K + 1) {
+        if (n_excluded) n_excluded[b] = reinterpret_cast<const long long*>(st)[0];
+        if (log_z) log_z[b] = empty ? -INFINITY : (float)(m_all * bd + log(Z));
+        if (entropy) entropy[b] = empty ? __builtin_nanf("") : (float)(log(Z) - bd * (all[2] / Z - m_all));
+        if (mean_score) mean_score[b] = empty ? __builtin_nanf("") : (float)(all[2] / Z);
+    } else {
+        const float p = empty ? 0.0f : (float)(me[1] * exp((me[0] - m_all) * bd) / Z);
+        if (j == K) {
+            if (rest_prob) rest_prob[b] = p;
+            return;
+        }
+        if (mode_prob) mode_prob[(long)b * K + j] = p;
+    }
+    float* Rm = j <= K ? (mode_R_mean ? mode_R_mean + ((long)b * K + j) * 9 : nullptr) : (R_mean ? R_mean + (long)b * 9 : nullptr);
+    float* sp = j <= K ? (mode_spread ? mode_spread + (long)b * K + j : nullptr) : (spread ? spread + b : nullptr);
+    if (!Rm && !sp) return;
+    if (empty) {
+        if (Rm) {
+#pragma unroll
+            for (int i = 0; i < 9; ++i) Rm[i] = 0.0f;
+        }
+        if (sp) *sp = __builtin_nanf("");
+        return;
+    }
+    double M[9];
+#pragma unroll
+    for (int i = 0; i < 9; ++i) M[i] = me[3 + i] / me[1];
+    post_project(M, Rm, sp);
+}
+
+// ---------------------------------------------------------------------------------
 // Haar-uniform rotation hypotheses generated on the device (replaces the host call
 // pytorch3d.transforms.random_rotations(N), test_co3d.py:106 / modules/model.py:184; only the
 // distribution matters -- hypotheses are inputs of the hot path).  Counter-based: rotation n
@@ -1175,6 +1573,36 @@ hipError_t launch_topk_modes(const float* scores, const float* R, int64_t r_batc
         hipLaunchKernelGGL(topk_modes_kernel<false>, grid, dim3(kTopkThreads), 0, stream, scores, R, (long)r_batch_stride,
                            (long)N, Ns, (long)n_offset, K, j, tau, reinterpret_cast<key_t*>(state),
                            reinterpret_cast<key_t*>(keys));
+    return hipGetLastError();
+}
+
+// ---- pose posterior ---------------------------------------------------------------------------------------
+hipError_t launch_posterior_merge(const void* states, int P, int B, int K, float beta, void* state, bool carry, hipStream_t stream)
+{
+    hipLaunchKernelGGL(posterior_merge_kernel, dim3((unsigned)B), dim3(64), 0, stream, static_cast<const char*>(states), P, B, K,
+                       beta, static_cast<char*>(state), carry);
+    return hipGetLastError();
+}
+
+// two launches: one partial state per workgroup into the workspace, then their merge into (or over) the caller's state
+hipError_t launch_posterior(const float* scores, const float* R, int64_t r_batch_stride, int B, int64_t N, const float* anchors,
+                            int K, float tau, float beta, void* state, void* workspace, bool carry, hipStream_t stream)
+{
+    const int parts = posterior_parts(N);
+    hipLaunchKernelGGL(posterior_partial_kernel, dim3((unsigned)parts, (unsigned)B), dim3(kTopkThreads), 0, stream, scores, R,
+                       (long)r_batch_stride, B, (long)N, anchors, K, tau, beta, static_cast<char*>(workspace));
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    return launch_posterior_merge(workspace, parts, B, K, beta, state, carry, stream);
+}
+
+hipError_t launch_posterior_finish(const void* state, int B, int K, float beta, float* log_z, float* entropy, float* mean_score,
+                                   int64_t* n_excluded, float* mode_prob, float* rest_prob, float* mode_R_mean, float* R_mean,
+                                   float* mode_spread_deg, float* spread_deg, hipStream_t stream)
+{
+    hipLaunchKernelGGL(posterior_finish_kernel, dim3((unsigned)B), dim3(64), 0, stream, static_cast<const char*>(state), B, K, beta,
+                       log_z, entropy, mean_score, reinterpret_cast<long long*>(n_excluded), mode_prob, rest_prob, mode_R_mean,
+                       R_mean, mode_spread_deg, spread_deg);
     return hipGetLastError();
 }
 

@@ -63,6 +63,26 @@ def all_gather_topk(keys: torch.Tensor, group=None, merge_fn: Optional[Callable]
     return merge_fn(lists)
 
 
+def all_gather_posterior(state: torch.Tensor, k: int, temperature: float = 0.1, group=None,
+                         merge_fn: Optional[Callable] = None, force: bool = False) -> torch.Tensor:
+    """Global posterior state from per-rank states ``state (B,stride)`` (uint8: ``ops.pose_posterior(...).state`` of this rank's
+    shard against the SHARED anchors): ONE all-gather of the state bytes into ``(world,B,stride)`` followed by
+    ``ops.merge_posterior(states, k, temperature)`` in rank order -- the same merged state on every rank, which each then
+    finishes (``ops.pose_posterior_finish``).  The shape of ``all_gather_topk``: ``merge_fn`` defaults to the HIP kernel, CPU
+    tests inject their own; with no process group (or a world of one, unless ``force``) the state is returned as it is."""
+    inited = dist.is_available() and dist.is_initialized()
+    world = dist.get_world_size(group) if inited else 1
+    if not inited or (world == 1 and not force):
+        return state
+    if merge_fn is None:
+        from . import ops
+        merge_fn = ops.merge_posterior
+    states = torch.empty((world,) + tuple(state.shape), dtype=state.dtype, device=state.device)
+    # the concatenated form (world*B, stride): what every backend accepts (gloo refuses the stacked shape)
+    dist.all_gather_into_tensor(states.view((-1,) + tuple(state.shape[1:])), state.contiguous(), group=group)
+    return merge_fn(states, k, temperature)
+
+
 def all_gather_scores(scores_local: torch.Tensor, n_total: int, group=None, force: bool = False,
                       out: Optional[torch.Tensor] = None, staging: Optional[torch.Tensor] = None) -> torch.Tensor:
     """The full score row ``(B, n_total)`` from this rank's slice ``(B, hi - lo)`` of ``shard_range(n_total, rank, world)``:

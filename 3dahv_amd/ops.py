@@ -15,6 +15,7 @@ to torch's current stream.  The plain ops carry no autograd graph; the ``*_autog
 """
 from __future__ import annotations
 
+import collections
 import contextvars
 import math
 
@@ -751,6 +752,170 @@ def verify_pair_modes(vol_src: torch.Tensor, vol_tgt: torch.Tensor, R: torch.Ten
     k = _topk_k(k)
     scores = verify_pair(vol_src, vol_tgt, R, W1, W2, b2, want_scores=True, **kw)[0]
     return select_topk(topk_modes(scores, R, k, min_angle_deg, keys=keys, workspace=workspace), R)
+
+
+# ---- pose posterior --------------------------------------------------------------------------------------------
+# The softmax of the scores at temperature T as a distribution over the hypotheses (``ahv_pose_posterior_f32``, include/ahv.h):
+# its log-partition, entropy and mean score, the mass inside a geodesic cap around each of K anchors (first match) and in the
+# rest, and the mean pose and angular spread of every bucket and of the whole set.  A STATE is a ``(B, stride)`` uint8 tensor
+# (``ahv_pose_posterior_state_bytes``): calls merge into it, states of shards merge (``merge_posterior``), and
+# ``pose_posterior_finish`` turns one into numbers.
+
+# (device, B, N, K) -> workspace (the partial states of one call): static like _TOPK_WS, and under the same rule
+_POSTERIOR_WS = {}
+
+PosePosterior = collections.namedtuple(
+    "PosePosterior", ["log_z", "entropy", "mean_score", "n_excluded", "mode_prob", "rest_prob", "mode_R_mean", "R_mean",
+                      "mode_spread_deg", "spread_deg", "state"])
+
+
+def inverse_temperature(temperature) -> float:
+    """``beta = 1 / T`` in double precision, rounded to fp32: what the posterior entry points take as ``beta``."""
+    T = float(temperature)
+    if not (T > 0.0 and math.isfinite(T)):
+        raise RuntimeError("temperature = %r must be finite and > 0" % (temperature,))
+    beta = float(torch.tensor(1.0 / T, dtype=torch.float64).to(torch.float32))
+    if not (beta > 0.0 and math.isfinite(beta)):
+        raise RuntimeError("temperature = %r: 1 / T rounds to %r in fp32, it must be finite and > 0" % (temperature, beta))
+    return beta
+
+
+def _posterior_k(k) -> int:
+    k = int(k)
+    if not 0 <= k <= _lib.AHV_POSTERIOR_MAX_MODES:
+        raise RuntimeError("K = %d outside 0..%d" % (k, _lib.AHV_POSTERIOR_MAX_MODES))
+    return k
+
+
+def _posterior_state(state: torch.Tensor, k: int, what: str = "state"):
+    """(B, stride) of a state tensor ``(..., B, stride)`` uint8 for K = k."""
+    stride = _lib.load().ahv_pose_posterior_state_bytes(1, k)
+    if state.dtype != torch.uint8 or state.dim() < 2 or state.shape[-1] != stride or not state.is_contiguous():
+        raise RuntimeError("%s must be a contiguous uint8 tensor (..., B, %d) for K = %d, got %s %s"
+                           % (what, stride, k, state.dtype, tuple(state.shape)))
+    return state.shape[-2], stride
+
+
+def pose_posterior_workspace(B: int, N: int, k: int, device) -> torch.Tensor | None:
+    """A workspace for ``pose_posterior`` on (B, N, k): allocate it once, pass it to every call (no allocation under capture)."""
+    nbytes = _lib.load().ahv_pose_posterior_workspace_bytes(B, N, _posterior_k(k))
+    return torch.empty((nbytes,), dtype=torch.uint8, device=device) if nbytes else None
+
+
+def pose_posterior_state(B: int, k: int, device) -> torch.Tensor:
+    """An uninitialised state for (B, k): pass it with ``reset=True`` to the first call."""
+    return torch.empty((B, _lib.load().ahv_pose_posterior_state_bytes(1, _posterior_k(k))), dtype=torch.uint8, device=device)
+
+
+@torch.no_grad()
+def pose_posterior_finish(state: torch.Tensor, k: int, temperature: float = 0.1) -> PosePosterior:
+    """The outputs of a (merged) state (``ahv_pose_posterior_finish_f32``): one launch."""
+    k = _posterior_k(k)
+    beta = inverse_temperature(temperature)
+    B, _ = _posterior_state(state, k)
+    if state.dim() != 2:
+        raise RuntimeError("state must be (B, stride)")
+    if not state.is_cuda:
+        raise RuntimeError("3dahv_amd ops run on the GPU only (no CPU fallback); got a tensor on %s" % state.device)
+    dev = state.device
+    f = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)
+    out = PosePosterior(f(B), f(B), f(B), torch.empty((B,), dtype=torch.int64, device=dev), f(B, k), f(B), f(B, k, 3, 3), f(B, 3, 3),
+                        f(B, k), f(B), state)
+    _call(dev, "ahv_pose_posterior_finish_f32", state.data_ptr(), B, k, beta, *[t.data_ptr() for t in out[:10]])
+    return out
+
+
+@torch.no_grad()
+def merge_posterior(states: torch.Tensor, k: int, temperature: float = 0.1, state: torch.Tensor | None = None,
+                    reset: bool | None = None) -> torch.Tensor:
+    """``states (P,B,stride)`` -> one state ``(B,stride)`` (``ahv_pose_posterior_merge``), in the order p = 0 .. P-1: what follows
+    an all-gather of per-rank states.  ``state`` given: merge into it unless ``reset``."""
+    k = _posterior_k(k)
+    beta = inverse_temperature(temperature)
+    B, stride = _posterior_state(states, k, "states")
+    if states.dim() != 3:
+        raise RuntimeError("states must be (P, B, stride)")
+    if not states.is_cuda:
+        raise RuntimeError("3dahv_amd ops run on the GPU only (no CPU fallback); got a tensor on %s" % states.device)
+    if state is None:
+        state = torch.empty((B, stride), dtype=torch.uint8, device=states.device)
+        reset = True
+    elif _posterior_state(state, k) != (B, stride) or state.dim() != 2 or state.device != states.device:
+        raise RuntimeError("state must be a (B, stride) = %s uint8 tensor on %s" % ((B, stride), states.device))
+    _call(states.device, "ahv_pose_posterior_merge", states.data_ptr(), states.shape[0], B, k, beta, state.data_ptr(),
+          _lib.AHV_POSTERIOR_RESET_STATE if reset else 0)
+    return state
+
+
+@torch.no_grad()
+def pose_posterior(scores: torch.Tensor, R: torch.Tensor, temperature: float = 0.1, anchors: torch.Tensor | None = None,
+                   min_angle_deg: float | None = None, state: torch.Tensor | None = None, workspace: torch.Tensor | None = None,
+                   reset: bool | None = None) -> PosePosterior:
+    """The posterior of ``scores (B,N)`` over the hypotheses ``R (N,3,3)`` / ``(B,N,3,3)`` at ``temperature``, bucketed by the
+    ``anchors (B,K,3,3)`` (K <= 16; normally the rotations ``select_topk`` returns for a modes list; an all-zero anchor is an
+    empty slot): hypothesis i counts for the FIRST anchor within ``min_angle_deg`` of it, else for the rest.  Returns a
+    ``PosePosterior``: ``log_z``, ``entropy`` (nats), ``mean_score``, ``n_excluded`` (non-finite scores: they take no part),
+    ``mode_prob (B,K)`` and ``rest_prob`` (summing to 1), ``mode_R_mean (B,K,3,3)`` / ``R_mean`` (the rotation nearest to the
+    weighted mean matrix), ``mode_spread_deg`` / ``spread_deg``, and ``state``.  ``state`` given: this call's hypotheses are
+    merged into it (chunked N) unless ``reset``, and the outputs describe the merged state.  ``workspace``: a uint8 tensor of
+    ``ahv_pose_posterior_workspace_bytes`` bytes (``pose_posterior_workspace``), else a static one per shape.  Three launches;
+    with ``state`` and ``workspace`` given only the outputs are allocated."""
+    beta = inverse_temperature(temperature)
+    if scores.dim() != 2:
+        raise RuntimeError("scores must be (B,N)")
+    B, N = scores.shape
+    if anchors is None:
+        k, tau = 0, 0.0
+    else:
+        if anchors.dim() != 4 or anchors.shape[0] != B or tuple(anchors.shape[2:]) != (3, 3):
+            raise RuntimeError("anchors must be (B,K,3,3) with B = %d, got %s" % (B, tuple(anchors.shape)))
+        k = _posterior_k(anchors.shape[1])
+        if min_angle_deg is None:
+            raise RuntimeError("min_angle_deg is required with anchors")
+        tau = min_trace(min_angle_deg)
+    n_rot, rstride = _rot_layout(R, B)
+    if n_rot != N:
+        raise RuntimeError("R holds %d hypotheses, scores %d" % (n_rot, N))
+    lib = _lib.load()
+    nbytes = lib.ahv_pose_posterior_workspace_bytes(B, N, k)
+    if workspace is not None and workspace.numel() * workspace.element_size() < nbytes:
+        raise RuntimeError("workspace of %d bytes, need %d (ahv_pose_posterior_workspace_bytes)"
+                           % (workspace.numel() * workspace.element_size(), nbytes))
+    tensors = (scores, R) if anchors is None else (scores, R, anchors)
+    dev = _need_gpu(*tensors)
+    if state is None:
+        state = torch.empty((B, lib.ahv_pose_posterior_state_bytes(1, k)), dtype=torch.uint8, device=dev)
+        reset = True
+    elif _posterior_state(state, k)[0] != B or state.dim() != 2 or state.device != dev:
+        raise RuntimeError("state must be a (B, stride) uint8 tensor for B = %d, K = %d on %s" % (B, k, dev))
+    if workspace is None and nbytes:
+        workspace = _POSTERIOR_WS.get((dev, B, N, k))
+        if workspace is None:
+            workspace = _POSTERIOR_WS[(dev, B, N, k)] = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
+    have = 0
+    if workspace is not None:
+        if workspace.device != dev or not workspace.is_contiguous():
+            raise RuntimeError("workspace must be a contiguous tensor on %s" % dev)
+        have = workspace.numel() * workspace.element_size()
+    s, Rc = scores.detach().contiguous(), R.detach().contiguous()
+    Ac = anchors.detach().contiguous() if k else None
+    _call(dev, "ahv_pose_posterior_f32", s.data_ptr(), Rc.data_ptr(), rstride, B, N, Ac.data_ptr() if k else None, k, tau, beta,
+          state.data_ptr(), workspace.data_ptr() if workspace is not None else None, have,
+          _lib.AHV_POSTERIOR_RESET_STATE if reset else 0)
+    return pose_posterior_finish(state, k, temperature)
+
+
+def verify_pair_posterior(vol_src: torch.Tensor, vol_tgt: torch.Tensor, R: torch.Tensor, W1: torch.Tensor, W2: torch.Tensor,
+                          b2: torch.Tensor, k: int, min_angle_deg: float, temperature: float = 0.1, **kw):
+    """The verify step with distinct modes and their posterior: ``verify_pair`` with the scores kept -> ``topk_modes`` ->
+    ``select_topk`` -> ``pose_posterior`` with the modes as anchors.  Returns ``verify_pair_modes``'s triple ``(mode_scores
+    (B,K), mode_idx (B,K), R_modes (B,K,3,3))`` and the ``PosePosterior``; K <= 16.  Other keywords go to ``verify_pair``."""
+    k = _posterior_k(k)
+    beta = inverse_temperature(temperature)  # (checked before the first launch)
+    del beta
+    scores = verify_pair(vol_src, vol_tgt, R, W1, W2, b2, want_scores=True, **kw)[0]
+    m_s, m_i, m_R = select_topk(topk_modes(scores, R, _topk_k(k), min_angle_deg), R)
+    return m_s, m_i, m_R, pose_posterior(scores, R, temperature, anchors=m_R, min_angle_deg=min_angle_deg)
 
 
 # ---- rotation gradient of the score, gradient-based pose polishing ------------------------------------------
