@@ -20,10 +20,6 @@ hipError_t launch_forward_3d2d(const float*, const float*, const float*, const f
                                hipStream_t);
 hipError_t launch_score_features(const float*, const float*, int, int64_t, float*, int, hipStream_t);
 hipError_t launch_argmax(const float*, int, int64_t, int64_t, int64_t*, int, hipStream_t);
-hipError_t launch_compose_rotations(const int64_t*, const float*, int64_t, int64_t, int64_t, const float*, int64_t,
-                                    int, float*, hipStream_t);
-hipError_t launch_select_rotation(int64_t*, const float*, int64_t, int64_t, int64_t, int, float*, float*, int64_t*, bool,
-                                  hipStream_t);
 hipError_t launch_fill_keys(int64_t*, int, hipStream_t);
 int topk_parts(int64_t N);
 hipError_t launch_topk(const float*, int, int64_t, int64_t, int, int64_t*, int64_t*, bool, hipStream_t);
@@ -291,8 +287,8 @@ int ahv_compose_rotations_f32(const int64_t* best_key, const float* R, int64_t r
     if (!best_key || !R || !D || !out) return fail(AHV_EINVAL, "compose_rotations: null pointer");
     if (N == 0) return fail(AHV_EINVAL, "compose_rotations: empty rotation set");
     if (r_batch_stride != 0 && r_batch_stride < N * 9) return fail(AHV_EINVAL, "compose_rotations: bad r_batch_stride");
-    hipError_t e = ahv::launch_compose_rotations(best_key, R, r_batch_stride, n_offset, N, D, N2, B, out,
-                                                 static_cast<hipStream_t>(stream));
+    hipError_t e = ahv::launch_compose_rotations_topk(best_key, 1, R, r_batch_stride, n_offset, N, D, N2, B, out,
+                                                      static_cast<hipStream_t>(stream));  // one seed: the list at K = 1
     if (e != hipSuccess) return hip_fail("compose_rotations: launch", e);
     return AHV_OK;
 }
@@ -347,8 +343,8 @@ int ahv_select_rotation_f32(int64_t* best_key, const float* R, int64_t r_batch_s
     if (!best_key) return fail(AHV_EINVAL, "select_rotation: null best_key");
     if (R_out && (!R || N == 0)) return fail(AHV_EINVAL, "select_rotation: R_out needs a rotation set");
     if (r_batch_stride != 0 && r_batch_stride < N * 9) return fail(AHV_EINVAL, "select_rotation: bad r_batch_stride");
-    hipError_t e = ahv::launch_select_rotation(best_key, R, r_batch_stride, n_offset, N, B, R_out, best_score, best_idx,
-                                               (flags & AHV_SELECT_RESET_KEY) != 0, static_cast<hipStream_t>(stream));
+    hipError_t e = ahv::launch_select_topk(best_key, 1, R, r_batch_stride, n_offset, N, B, R_out, best_score, best_idx,
+                                           (flags & AHV_SELECT_RESET_KEY) != 0, static_cast<hipStream_t>(stream));  // B lists of one
     if (e != hipSuccess) return hip_fail("select_rotation: launch", e);
     return AHV_OK;
 }

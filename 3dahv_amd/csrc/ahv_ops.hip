@@ -1,7 +1,9 @@
 // ahv_ops.hip -- op-level drop-in kernels: each materialises the tensor the
 // reference's corresponding call returns, so the reference's own call sequence
 // (rotate_volume -> forward_3d2d -> mul/sum/mean -> max) runs unchanged on HIP.
-// These are the HBM-bound siblings of the fused scorer (ahv_score.hip).
+// These are the HBM-bound siblings of the fused scorer (ahv_score.hip).  Also here: the hypothesis generators
+// (random_rotations, so3_grid) and the library's zero fill.  What happens once the scores exist -- the arg-max of that
+// sequence, lists, modes, posterior, ascent -- is ahv_select.hip.
 #include "ahv_device.h"
 #include "ahv_dual.h"
 #include "ahv_exact.h"
@@ -519,789 +521,6 @@ __global__ __launch_bounds__(256) void score_features_kernel(const float* __rest
 }
 
 // ---------------------------------------------------------------------------------
-// arg-max over materialised scores (test_co3d.py:145), same packed key as the fused path.
-// ---------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void argmax_kernel(const float* __restrict__ scores, int B, long N,
-                                                     long n_offset, key_t* __restrict__ best_key)
-{
-    const int b = blockIdx.y;
-    const float* s = scores + (long)b * N;
-    key_t best = kKeyEmpty;
-    for (long n = (long)blockIdx.x * blockDim.x + threadIdx.x; n < N; n += (long)gridDim.x * blockDim.x) {
-        const key_t k = pack_key(s[n], (unsigned)(n_offset + n));
-        best = k > best ? k : best;
-    }
-    best = wave_max_key(best);
-    if ((threadIdx.x & 63) == 0 && best != kKeyEmpty) atomicMax(best_key + b, best);
-}
-
-// ---------------------------------------------------------------------------------
-// Coarse-to-fine support (BASELINE.json configs[4]; build-defined, the reference scores one flat
-// set): refinement hypotheses R_fine[b][n] = R[idx_b] * D[n], where idx_b is decoded on the device from
-// the packed key of the coarse stage and D is a fixed set of small rotations.  Graph-capturable.
-// ---------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void compose_rotations_kernel(const key_t* __restrict__ best_key,
-                                                                const float* __restrict__ R, long r_batch_stride,
-                                                                long n_offset, long N, const float* __restrict__ D,
-                                                                long N2, int B, float* __restrict__ out)
-{
-    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= (long)B * N2) return;
-    const int b = (int)(i / N2);
-    const long n = i - (long)b * N2;
-    const key_t key = best_key[b];
-    long idx = key_index(key) - n_offset;
-    idx = (key == kKeyEmpty || idx < 0 || idx >= N) ? 0 : idx;  // nothing scored / foreign shard: stay in bounds
-    const float* r = R + (long)b * r_batch_stride + idx * 9;
-    const float* d = D + n * 9;
-    float* o = out + i * 9;
-#pragma unroll
-    for (int a = 0; a < 3; ++a)
-#pragma unroll
-        for (int c = 0; c < 3; ++c) o[a * 3 + c] = r[a * 3] * d[c] + r[a * 3 + 1] * d[3 + c] + r[a * 3 + 2] * d[6 + c];
-}
-
-// unpack + gather in one launch: (best score, global index, R_pred = R[idx]) of test_co3d.py:145-146.
-// reset: the key is handed back EMPTY, ready for the next verify step's atomic max (the step then needs no launch
-// of its own to clear it: stream order puts this kernel between the two scorers).
-__global__ void select_rotation_kernel(key_t* __restrict__ best_key, const float* __restrict__ R, long r_batch_stride,
-                                       long n_offset, long N, int B, float* __restrict__ R_out,
-                                       float* __restrict__ best_score, long* __restrict__ best_idx, bool reset)
-{
-    const int b = blockIdx.x * blockDim.x + threadIdx.x;
-    if (b >= B) return;
-    const key_t k = best_key[b];
-    if (reset) best_key[b] = kKeyEmpty;
-    const long gidx = (k == kKeyEmpty) ? -1l : key_index(k);
-    if (best_score) best_score[b] = (k == kKeyEmpty) ? -INFINITY : key_score(k);
-    if (best_idx) best_idx[b] = gidx;
-    if (R_out) {
-        const long loc = gidx - n_offset;
-        const bool mine = (k != kKeyEmpty) && loc >= 0 && loc < N;  // with sharding only the owner rank holds the row
-        const float* r = R + (long)b * r_batch_stride + (mine ? loc : 0) * 9;
-#pragma unroll
-        for (int e = 0; e < 9; ++e) R_out[b * 9 + e] = mine ? r[e] : 0.0f;
-    }
-}
-
-// ---------------------------------------------------------------------------------
-// K best hypotheses (the list counterpart of argmax_kernel / select_rotation_kernel / compose_rotations_kernel).
-// A list is K packed keys in descending SIGNED order, distinct, padded with kKeyEmpty.  With pack_key as it is that order
-// is torch.sort(scores, dim=1, descending=True, stable=True) truncated to K (NaN first, lowest index among equal
-// scores, -0 = +0); it is NOT torch.topk's order, which leaves ties unspecified.
-//
-// Everything on the critical path stays inside ONE wave: no barrier and no LDS round trip per round.
-//  - scores -> lists (topk_kernel<true>): a workgroup of four waves walks tiles of kTopkTile scores; a lane holds four
-//    candidates (one 16-byte load), and each wave on its own runs K knock-out rounds over its 256 -- a wave-wide max by DPP
-//    row operations, the lane that offered the winner moves to its largest key strictly below it -- and leaves a sorted
-//    K-list in LDS.  The four wave lists and the workgroup's running list are then merged by counting ranks (a fresh
-//    list: all keys distinct) or, when the caller's list is merged into in the same launch, by their HEADS.
-//  - lists -> list (merge_heads): one lane per sorted list; a round is the wave-wide max of the heads, and every lane
-//    whose head is the winner steps to its next entry (so a key met in several lists is taken once).  Up to 63 lists and
-//    the running list per pass; more lists are taken in passes.  This is ahv_topk_merge_keys, and the second launch of
-//    ahv_topk_f32.
-// Order, distinctness and the tie rule fall out of the integer compare.  A sample's N scores are spread over up to
-// kTopkMaxParts workgroups whose lists go to the workspace; the second launch merges them into the caller's list ACROSS A
-// KERNEL BOUNDARY -- no ticket, no loads that must dodge a stale per-XCD L2 line.  N <= one tile: one launch, straight into
-// the list.  (The first version ran every round workgroup-wide -- eight candidates per lane, four LDS words and a barrier
-// per round, in both launches: 1.1 us per round and pair of launches, slower than torch.topk + gather at K = 64.)
-// ---------------------------------------------------------------------------------
-constexpr int kTopkThreads = 256;
-constexpr int kTopkPerLane = 4;
-constexpr int kTopkTile = kTopkThreads * kTopkPerLane;  // 1024 scores per tile
-constexpr int kTopkMaxParts = 63;                       // partial lists per sample: with the running list, one lane each
-constexpr int kTopkMaxK = 64;
-
-// wave 0 only: merge sorted lists by their heads into out[0..K) (LDS).  mine: this lane's list (K keys, descending), or
-// nullptr for a lane without one.
-__device__ __forceinline__ void merge_heads(const key_t* mine, int K, key_t* out)
-{
-    const int lane = threadIdx.x & 63;
-    int pos = 0;
-    key_t head = mine ? mine[0] : kKeyEmpty;
-    for (int r = 0; r < K; ++r) {
-        const key_t m = wave_max_key_dpp(head);
-        if (lane == 0) out[r] = m;
-        if (m == kKeyEmpty) {  // fewer than K distinct keys: pad (uniform over the wave)
-            for (int j = r + 1 + lane; j < K; j += 64) out[j] = kKeyEmpty;
-            break;
-        }
-        while (head >= m) {  // my head won (or repeats the winner): step past it; kKeyEmpty < m ends the walk
-            ++pos;
-            head = pos < K ? mine[pos] : kKeyEmpty;
-        }
-    }
-}
-
-// one wave, K knock-out rounds over the lanes' candidates c[0..kTopkPerLane): out[0..K) (LDS) = the wave's sorted list
-__device__ __forceinline__ void wave_knock_out(const key_t (&c)[kTopkPerLane], int K, key_t* out)
-{
-    const int lane = threadIdx.x & 63;
-    key_t mine = c[0];
-#pragma unroll
-    for (int i = 1; i < kTopkPerLane; ++i) mine = c[i] > mine ? c[i] : mine;
-    for (int r = 0; r < K; ++r) {
-        const key_t m = wave_max_key_dpp(mine);
-        if (lane == 0) out[r] = m;
-        if (m == kKeyEmpty) {
-            for (int j = r + 1 + lane; j < K; j += 64) out[j] = kKeyEmpty;
-            break;
-        }
-        if (mine == m) {  // knocked out: my largest key strictly below the winner
-            key_t nxt = kKeyEmpty;
-#pragma unroll
-            for (int i = 0; i < kTopkPerLane; ++i) nxt = (c[i] < m && c[i] > nxt) ? c[i] : nxt;
-            mine = nxt;
-        }
-    }
-}
-
-// kScores: src = scores [B][N] (+ n_offset); workgroup (x, b) takes the tiles x, x + gridDim.x, ... of sample b.  Tiles are
-// laid on the 16-byte grid of the sample's row (a = the row's misalignment in floats), so that a lane's four scores are
-// one 16-byte load wherever all four exist; the ragged ends go element by element.
-// !kScores: src = lists [N][B][K] (N lists per sample), every one sorted as a list is.
-// carry: the list starts as out[b][0..K) (merge into) instead of empty.  out: [gridDim.x][B][K].
-template <bool kScores>
-__global__ __launch_bounds__(kTopkThreads) void topk_kernel(const void* __restrict__ src, int B, long N, long n_offset, int K,
-                                                            key_t* __restrict__ out, bool carry)
-{
-    __shared__ key_t run[2][kTopkMaxK];  // the running list and the one being built
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, b = blockIdx.y;
-    key_t* dst = out + ((long)blockIdx.x * B + b) * K;
-    if (tid < K) run[0][tid] = carry ? dst[tid] : kKeyEmpty;
-    int cur = 0;
-    if constexpr (kScores) {
-        __shared__ key_t wl[4][kTopkMaxK];  // the four wave lists of a tile
-        const float* s = static_cast<const float*>(src) + (long)b * N;
-        const long a = (long)((reinterpret_cast<unsigned long long>(s) >> 2) & 3ull);
-        const long tiles = (N + a + kTopkTile - 1) / kTopkTile;
-        for (long t = blockIdx.x; t < tiles; t += gridDim.x) {
-            key_t c[kTopkPerLane];
-            const long n0 = t * kTopkTile + (long)tid * 4 - a;  // first of the lane's four scores
-            if (n0 >= 0 && n0 + 3 < N) {
-                const float4 q = *reinterpret_cast<const float4*>(s + n0);
-                c[0] = pack_key(q.x, (unsigned)(n_offset + n0));
-                c[1] = pack_key(q.y, (unsigned)(n_offset + n0 + 1));
-                c[2] = pack_key(q.z, (unsigned)(n_offset + n0 + 2));
-                c[3] = pack_key(q.w, (unsigned)(n_offset + n0 + 3));
-            } else {
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    const long n = n0 + e;
-                    c[e] = (n >= 0 && n < N) ? pack_key(s[n], (unsigned)(n_offset + n)) : kKeyEmpty;
-                }
-            }
-            wave_knock_out(c, K, wl[wave]);
-            __syncthreads();  // the four wave lists (and, first time round, run[0]) are in LDS
-            if (carry) {
-                if (wave == 0) merge_heads(lane < 4 ? wl[lane] : lane == 4 ? run[cur] : nullptr, K, run[cur ^ 1]);
-            } else {
-                // A fresh list: the five lists hold keys of different hypotheses, all distinct, so a key's place in the
-                // merged list is the number of keys above it -- counted by all 256 lanes at once instead of K more rounds.
-                if (tid < K) run[cur ^ 1][tid] = kKeyEmpty;
-                __syncthreads();
-                for (int e = tid; e < 5 * K; e += kTopkThreads) {
-                    const int l = e / K, j = e - l * K;
-                    const key_t k = l < 4 ? wl[l][j] : run[cur][j];
-                    if (k == kKeyEmpty) continue;
-                    int rank = 0;
-                    for (int i = 0; i < K; ++i)
-                        rank += (wl[0][i] > k) + (wl[1][i] > k) + (wl[2][i] > k) + (wl[3][i] > k) + (run[cur][i] > k);
-                    if (rank < K) run[cur ^ 1][rank] = k;
-                }
-            }
-            cur ^= 1;
-            __syncthreads();
-        }
-    } else {
-        __shared__ key_t ls[kTopkMaxParts * kTopkMaxK];  // up to 63 lists of a pass
-        const key_t* lists = static_cast<const key_t*>(src);
-        for (long g0 = 0; g0 < N; g0 += kTopkMaxParts) {
-            const int ng = (int)(N - g0 < kTopkMaxParts ? N - g0 : kTopkMaxParts);
-            for (int e = tid; e < ng * K; e += kTopkThreads) {
-                const int p = e / K;
-                ls[e] = lists[((g0 + p) * B + b) * K + (e - p * K)];
-            }
-            __syncthreads();
-            if (wave == 0) merge_heads(lane < ng ? ls + lane * K : lane == 63 ? run[cur] : nullptr, K, run[cur ^ 1]);
-            cur ^= 1;
-            __syncthreads();
-        }
-    }
-    __syncthreads();
-    if (tid < K) dst[tid] = run[cur][tid];
-}
-
-// decode + gather for a list, one thread per (b, k): the list counterpart of select_rotation_kernel
-__global__ __launch_bounds__(256) void select_topk_kernel(key_t* __restrict__ keys, int K, const float* __restrict__ R,
-                                                          long r_batch_stride, long n_offset, long N, int B,
-                                                          float* __restrict__ R_out, float* __restrict__ scores_out,
-                                                          long* __restrict__ idx_out, bool reset)
-{
-    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= (long)B * K) return;
-    const int b = (int)(i / K);
-    const key_t k = keys[i];
-    if (reset) keys[i] = kKeyEmpty;
-    const long gidx = (k == kKeyEmpty) ? -1l : key_index(k);
-    if (scores_out) scores_out[i] = (k == kKeyEmpty) ? -INFINITY : key_score(k);
-    if (idx_out) idx_out[i] = gidx;
-    if (R_out) {
-        const long loc = gidx - n_offset;
-        const bool mine = (k != kKeyEmpty) && loc >= 0 && loc < N;  // sharded: the owner rank holds the row, the others zeros
-        const float* r = R + (long)b * r_batch_stride + (mine ? loc : 0) * 9;
-#pragma unroll
-        for (int e = 0; e < 9; ++e) R_out[i * 9 + e] = mine ? r[e] : 0.0f;
-    }
-}
-
-// out[b][k * N2 + n] = R[idx_{b,k}] * D[n]: compose_rotations_kernel for K seeds (its expression, its in-bounds rule)
-__global__ __launch_bounds__(256) void compose_rotations_topk_kernel(const key_t* __restrict__ keys, int K,
-                                                                     const float* __restrict__ R, long r_batch_stride,
-                                                                     long n_offset, long N, const float* __restrict__ D,
-                                                                     long N2, int B, float* __restrict__ out)
-{
-    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= (long)B * K * N2) return;
-    const long bk = i / N2;  // b * K + k
-    const long n = i - bk * N2;
-    const int b = (int)(bk / K);
-    const key_t key = keys[bk];
-    long idx = key_index(key) - n_offset;
-    idx = (key == kKeyEmpty || idx < 0 || idx >= N) ? 0 : idx;  // empty slot / foreign shard: stay in bounds
-    const float* r = R + (long)b * r_batch_stride + idx * 9;
-    const float* d = D + n * 9;
-    float* o = out + i * 9;
-#pragma unroll
-    for (int a = 0; a < 3; ++a)
-#pragma unroll
-        for (int c = 0; c < 3; ++c) o[a * 3 + c] = r[a * 3] * d[c] + r[a * 3 + 1] * d[3 + c] + r[a * 3 + 2] * d[6 + c];
-}
-
-// ---------------------------------------------------------------------------------
-// Distinct pose modes (ahv_topk_modes_f32): greedy suppression by geodesic distance over the WHOLE scored set.  Entry j of
-// the list is the largest key still alive; the winner then kills itself (by index, unconditionally) and every alive
-// hypothesis i with t(i, w) = sum_ab R_i[a][b] R_w[a][b] >= tau (tau = 1 + 2 cos theta: for rotations "within theta of
-// the winner").  A NaN t kills nothing.  K + 1 dependent launches: the list is filled EMPTY, round 0 packs the keys into the
-// alive state, round j >= 1 applies winner j - 1 and reduces the largest survivor.  The KERNEL BOUNDARY is the hand-over of
-// keys[j - 1]: no workgroup waits on another one.
-// Alive state: the packed keys themselves, state[b][Ns] (Ns = N rounded up to 4) in the caller's workspace, kKeyEmpty =
-// dead -- 8 bytes per hypothesis, read every round, written only where a hypothesis dies; the survivor's key needs no
-// re-packing.  Grid rule of the top-K kernels: tiles of kTopkTile hypotheses, 256 threads, four consecutive hypotheses per
-// lane; tile t starts at hypothesis t * kTopkTile.  A lane's four matrices are 144 contiguous bytes: nine 16-byte loads
-// when THAT ADDRESS is 16-byte aligned (a per-sample R row with N % 4 != 0 starts mid-vector, so the tile index says
-// nothing), element by element otherwise and at the ragged end.  A lane whose four hypotheses are all dead reads no
-// matrix; a wave of such lanes issues no load.
-// ---------------------------------------------------------------------------------
-typedef long long i64x2 __attribute__((ext_vector_type(2)));
-
-// the workgroup's largest key -> one atomicMax into *dst (skipped when nothing survives: *dst was filled kKeyEmpty)
-__device__ __forceinline__ void modes_publish(key_t best, key_t* wl, key_t* dst)
-{
-    const key_t m = wave_max_key_dpp(best);
-    if ((threadIdx.x & 63) == 0) wl[threadIdx.x >> 6] = m;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        key_t r = wl[0];
-#pragma unroll
-        for (int w = 1; w < kTopkThreads / 64; ++w) r = wl[w] > r ? wl[w] : r;
-        if (r != kKeyEmpty) atomicMax(dst, r);
-    }
-}
-
-// kFirst: round 0 -- state = pack_key(scores), keys[b][0] = the arg-max key.  !kFirst: round j.
-template <bool kFirst>
-__global__ __launch_bounds__(kTopkThreads) void topk_modes_kernel(const float* __restrict__ scores, const float* __restrict__ R,
-                                                                  long r_batch_stride, long N, long Ns, long n_offset, int K,
-                                                                  int j, float tau, key_t* __restrict__ state,
-                                                                  key_t* __restrict__ keys)
-{
-    __shared__ key_t wl[kTopkThreads / 64];
-    const int tid = threadIdx.x, b = blockIdx.y;
-    key_t* st = state + (long)b * Ns;
-    key_t* list = keys + (long)b * K;
-    const long tiles = (N + kTopkTile - 1) / kTopkTile;
-    key_t best = kKeyEmpty;
-    if constexpr (kFirst) {
-        const float* s = scores + (long)b * N;
-        for (long t = blockIdx.x; t < tiles; t += gridDim.x) {
-            const long n0 = t * kTopkTile + (long)tid * 4;
-            if (n0 >= N) continue;
-            key_t c[4];
-            if (n0 + 3 < N && (reinterpret_cast<unsigned long long>(s + n0) & 15ull) == 0) {
-                const float4 q = *reinterpret_cast<const float4*>(s + n0);
-                c[0] = pack_key(q.x, (unsigned)(n_offset + n0));
-                c[1] = pack_key(q.y, (unsigned)(n_offset + n0 + 1));
-                c[2] = pack_key(q.z, (unsigned)(n_offset + n0 + 2));
-                c[3] = pack_key(q.w, (unsigned)(n_offset + n0 + 3));
-            } else {
-#pragma unroll
-                for (int e = 0; e < 4; ++e) c[e] = n0 + e < N ? pack_key(s[n0 + e], (unsigned)(n_offset + n0 + e)) : kKeyEmpty;
-            }
-            // (the row is padded to Ns: all four slots exist; the padding is written dead)
-            *reinterpret_cast<i64x2*>(st + n0) = i64x2{c[0], c[1]};
-            *reinterpret_cast<i64x2*>(st + n0 + 2) = i64x2{c[2], c[3]};
-#pragma unroll
-            for (int e = 0; e < 4; ++e) best = c[e] > best ? c[e] : best;
-        }
-        modes_publish(best, wl, list);
-    } else {
-        const key_t prev = list[j - 1];
-        if (prev == kKeyEmpty) return;  // the alive set ran out: keys[j..K) stay EMPTY (uniform over the grid)
-        const long widx = key_index(prev) - n_offset;
-        if (widx < 0 || widx >= N) return;  // (cannot happen for a list this call built: stay in bounds regardless)
-        const float* Rb = R + (long)b * r_batch_stride;
-        float w[9];
-#pragma unroll
-        for (int i = 0; i < 9; ++i) w[i] = Rb[widx * 9 + i];
-        for (long t = blockIdx.x; t < tiles; t += gridDim.x) {
-            const long n0 = t * kTopkTile + (long)tid * 4;
-            if (n0 >= N) continue;
-            const i64x2 c01 = *reinterpret_cast<const i64x2*>(st + n0), c23 = *reinterpret_cast<const i64x2*>(st + n0 + 2);
-            key_t c[4] = {c01.x, c01.y, c23.x, c23.y};
-            if (c[0] == kKeyEmpty && c[1] == kKeyEmpty && c[2] == kKeyEmpty && c[3] == kKeyEmpty) continue;
-            const float* r = Rb + n0 * 9;
-            float tr[4];
-            if (n0 + 3 < N && (reinterpret_cast<unsigned long long>(r) & 15ull) == 0) {
-                float4 q[9];
-#pragma unroll
-                for (int v = 0; v < 9; ++v) q[v] = reinterpret_cast<const float4*>(r)[v];
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    float acc = 0.0f;
-#pragma unroll
-                    for (int i = 0; i < 9; ++i) {
-                        const int f = e * 9 + i;
-                        const float4 v = q[f >> 2];
-                        const float x = (f & 3) == 0 ? v.x : (f & 3) == 1 ? v.y : (f & 3) == 2 ? v.z : v.w;
-                        acc = fmaf(x, w[i], acc);
-                    }
-                    tr[e] = acc;
-                }
-            } else {
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    float acc = 0.0f;
-                    if (n0 + e < N && c[e] != kKeyEmpty) {
-#pragma unroll
-                        for (int i = 0; i < 9; ++i) acc = fmaf(r[e * 9 + i], w[i], acc);
-                    }
-                    tr[e] = acc;
-                }
-            }
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                if (c[e] == kKeyEmpty) continue;
-                if (tr[e] >= tau || n0 + e == widx) {  // false for a NaN trace; the winner goes by its index
-                    st[n0 + e] = kKeyEmpty;
-                    continue;
-                }
-                best = c[e] > best ? c[e] : best;
-            }
-        }
-        modes_publish(best, wl, list + j);
-    }
-}
-
-// ---------------------------------------------------------------------------------
-// Pose posterior (ahv_pose_posterior_f32 / _merge / _finish_f32): softmax statistics of the scored set at inverse temperature
-// beta, split over K anchor buckets (hypothesis i belongs to the FIRST anchor k with t(i, k) >= tau, else to the rest).  What is
-// kept per bucket and for the whole set is a RECORD of kPostRec doubles -- m (the largest score met, -inf when empty), and
-// relative to it mass = sum w, S = sum w s, M = sum w R (9), w = exp((s - m) beta) -- so that two records merge by the
-// online-softmax rule: m = max, each side rescaled by exp((m_side - m) beta).  A sample's STATE is a 16-byte header (int64
-// n_excluded, int64 reserved) and K + 2 records: buckets 0 .. K-1, the rest bucket, the whole set.
-//  - posterior_partial_kernel: ONE pass over scores and R on the grid rule of the top-K / modes kernels (tiles of kTopkTile,
-//    four consecutive hypotheses per lane, 16-byte loads where THAT ADDRESS is aligned).  The anchors sit in LDS.  A lane keeps
-//    online-softmax sums (fp32 weights, fp64 sums) for the whole set and the rest bucket; a mode bucket is hit rarely and is reduced wave-wide, only
-//    when a ballot says some lane hit it, into the wave's LDS row in program order.  Wave sums are DPP row operations in fp64,
-//    the four waves are combined in the order 0..3, one partial state per workgroup goes to the workspace.
-//  - posterior_merge_kernel: states [P][B] -> state [B] in the order p = 0 .. P-1 (into the state, or from empty): the second
-//    launch of a call and the merge after an all-gather.
-//  - posterior_finish_kernel: a state -> the outputs; the rotation nearest to M is the top eigenvector of Horn's 4 x 4
-//    quaternion matrix (the maximiser of sum R o M over SO(3) = U diag(1, 1, det(U V^T)) V^T), by cyclic Jacobi in fp64.
-// No floating-point atomics: for a given (B, N, K) every sum is taken in one fixed order, so results are bitwise reproducible.
-// ---------------------------------------------------------------------------------
-constexpr int kPostMaxModes = 16;
-constexpr int kPostRec = 12;      // doubles per record: m, mass, S, M[9]
-constexpr int kPostHeader = 16;   // bytes: int64 n_excluded, int64 reserved (0)
-
-__host__ __device__ constexpr size_t posterior_state_stride_dev(int K) { return (size_t)kPostHeader + (size_t)(K + 2) * kPostRec * sizeof(double); }
-size_t posterior_state_stride(int K) { return posterior_state_stride_dev(K); }
-
-int posterior_parts(int64_t N)
-{
-    const int64_t tiles = (N + kTopkTile - 1) / kTopkTile;
-    return (int)(tiles < kTopkMaxParts ? tiles : kTopkMaxParts);
-}
-
-struct PostAcc {  // one lane's online-softmax sums: the weights are fp32 (expf), the sums fp64 -- S / mass - m cancels, and an fp32
-    float m;      // S would put its own rounding (times beta) into the entropy of a peaked distribution
-    double mass, S, M[9];
-};
-
-__device__ __forceinline__ void post_clear(PostAcc& a)
-{
-    a.m = -INFINITY;
-    a.mass = 0.0;
-    a.S = 0.0;
-#pragma unroll
-    for (int i = 0; i < 9; ++i) a.M[i] = 0.0;
-}
-
-__device__ __forceinline__ void post_add(PostAcc& a, float s, const float* r, float beta)
-{
-    if (s > a.m) {  // a new maximum: rescale what is there (by 0 when nothing is: m = -inf)
-        const double f = (double)expf((a.m - s) * beta);
-        a.mass *= f;
-        a.S *= f;
-#pragma unroll
-        for (int i = 0; i < 9; ++i) a.M[i] *= f;
-        a.m = s;
-    }
-    const double w = (double)expf((s - a.m) * beta);
-    a.mass += w;
-    a.S = fma(w, (double)s, a.S);
-#pragma unroll
-    for (int i = 0; i < 9; ++i) a.M[i] = fma(w, (double)r[i], a.M[i]);
-}
-
-// dst <- dst merged with src (records of kPostRec doubles), dst's side first
-__device__ __forceinline__ void post_merge(double* dst, const double* src, double beta)
-{
-    const double ma = dst[0], mb = src[0];
-    const double m = mb > ma ? mb : ma;
-    if (m == -INFINITY) return;  // both empty
-    const double fa = ma == -INFINITY ? 0.0 : exp((ma - m) * beta), fb = mb == -INFINITY ? 0.0 : exp((mb - m) * beta);
-    dst[0] = m;
-#pragma unroll
-    for (int i = 1; i < kPostRec; ++i) dst[i] = dst[i] * fa + src[i] * fb;
-}
-
-template <int kCtrl, int kRows, int kBanks>
-__device__ __forceinline__ double sum_f64_dpp_step(double x)
-{
-    const unsigned long long u = __builtin_bit_cast(unsigned long long, x);
-    const unsigned lo = (unsigned)__builtin_amdgcn_update_dpp(0, (int)(unsigned)u, kCtrl, kRows, kBanks, true);
-    const unsigned hi = (unsigned)__builtin_amdgcn_update_dpp(0, (int)(unsigned)(u >> 32), kCtrl, kRows, kBanks, true);
-    return x + __builtin_bit_cast(double, ((unsigned long long)hi << 32) | lo);
-}
-
-// sum over the 64 lanes in the order of wave_sum_dpp, in fp64; valid in lane 63
-__device__ __forceinline__ double wave_sum_dpp_f64(double x)
-{
-    x = sum_f64_dpp_step<0x111, 0xF, 0xF>(x);  // row_shr:1
-    x = sum_f64_dpp_step<0x112, 0xF, 0xF>(x);  // row_shr:2
-    x = sum_f64_dpp_step<0x114, 0xF, 0xE>(x);  // row_shr:4
-    x = sum_f64_dpp_step<0x118, 0xF, 0xC>(x);  // row_shr:8
-    x = sum_f64_dpp_step<0x142, 0xA, 0xF>(x);  // row_bcast:15
-    x = sum_f64_dpp_step<0x143, 0xC, 0xF>(x);  // row_bcast:31
-    return x;
-}
-
-template <int kCtrl, int kRows>
-__device__ __forceinline__ float max_f32_dpp_step(float x)
-{
-    const int xi = __builtin_bit_cast(int, x);
-    const float o = __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(xi, xi, kCtrl, kRows, 0xF, false));
-    return o > x ? o : x;
-}
-
-// the wave's largest value (no NaN among the inputs: they are finite scores or -inf), in every lane
-__device__ __forceinline__ float wave_max_f32_dpp(float x)
-{
-    x = max_f32_dpp_step<0x111, 0xF>(x);
-    x = max_f32_dpp_step<0x112, 0xF>(x);
-    x = max_f32_dpp_step<0x114, 0xF>(x);
-    x = max_f32_dpp_step<0x118, 0xF>(x);
-    x = max_f32_dpp_step<0x142, 0xA>(x);
-    x = max_f32_dpp_step<0x143, 0xC>(x);
-    return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, x), 63));
-}
-
-// the 64 lanes' sums as one record, merged into row (LDS) by lane 63.  Called by whole waves only.
-__device__ __forceinline__ void post_wave_into(const PostAcc& a, double beta, double* row)
-{
-    const float mw = wave_max_f32_dpp(a.m);
-    const double f = a.m == -INFINITY ? 0.0 : exp(((double)a.m - (double)mw) * beta);
-    double rec[kPostRec];
-    rec[0] = (double)mw;
-    rec[1] = wave_sum_dpp_f64(f * a.mass);
-    rec[2] = wave_sum_dpp_f64(f * a.S);
-#pragma unroll
-    for (int i = 0; i < 9; ++i) rec[3 + i] = wave_sum_dpp_f64(f * a.M[i]);
-    if ((threadIdx.x & 63) == 63) post_merge(row, rec, beta);
-}
-
-__global__ __launch_bounds__(kTopkThreads) void posterior_partial_kernel(const float* __restrict__ scores, const float* __restrict__ R,
-                                                                         long r_batch_stride, int B, long N,
-                                                                         const float* __restrict__ anchors, int K, float tau,
-                                                                         float beta, char* __restrict__ partial)
-{
-    __shared__ double rows[kTopkThreads / 64][kPostMaxModes + 2][kPostRec];  // per wave: buckets, rest, whole
-    __shared__ float anc[kPostMaxModes][9];
-    __shared__ int used[kPostMaxModes];  // an all-zero anchor is an empty slot: skipped by this flag, not by its value
-    __shared__ int n_excl;
-    const int tid = threadIdx.x, wave = tid >> 6, b = blockIdx.y;
-    const double beta_d = (double)beta;
-    for (int e = tid; e < (kTopkThreads / 64) * (kPostMaxModes + 2) * kPostRec; e += kTopkThreads)
-        (&rows[0][0][0])[e] = (e % kPostRec) == 0 ? (double)-INFINITY : 0.0;
-    if (tid < K * 9) (&anc[0][0])[tid] = anchors[(long)b * K * 9 + tid];
-    if (tid == 0) n_excl = 0;
-    __syncthreads();
-    if (tid < K) {
-        bool any = false;
-#pragma unroll
-        for (int i = 0; i < 9; ++i) any = any || anc[tid][i] != 0.0f;  // true for a NaN entry: its t then matches nothing
-        used[tid] = any ? 1 : 0;
-    }
-    __syncthreads();
-
-    const float* s = scores + (long)b * N;
-    const float* Rb = R + (long)b * r_batch_stride;
-    const long tiles = (N + kTopkTile - 1) / kTopkTile;
-    PostAcc whole, rest;
-    post_clear(whole);
-    post_clear(rest);
-    int excluded = 0;
-    for (long t = blockIdx.x; t < tiles; t += gridDim.x) {  // (uniform over the workgroup: every lane takes every trip)
-        const long n0 = t * kTopkTile + (long)tid * 4;
-        float sc[4], r[4][9];
-        int bk[4];  // K: rest, k < K: bucket k, -1: no such hypothesis / not in the scored set
-        const bool full = n0 + 3 < N;
-        if (full && (reinterpret_cast<unsigned long long>(s + n0) & 15ull) == 0) {
-            const float4 q = *reinterpret_cast<const float4*>(s + n0);
-            sc[0] = q.x; sc[1] = q.y; sc[2] = q.z; sc[3] = q.w;
-        } else {
-#pragma unroll
-            for (int e = 0; e < 4; ++e) sc[e] = n0 + e < N ? s[n0 + e] : 0.0f;
-        }
-        const float* rp = Rb + n0 * 9;
-        if (full && (reinterpret_cast<unsigned long long>(rp) & 15ull) == 0) {
-            float4 q[9];
-#pragma unroll
-            for (int v = 0; v < 9; ++v) q[v] = reinterpret_cast<const float4*>(rp)[v];
-#pragma unroll
-            for (int e = 0; e < 4; ++e)
-#pragma unroll
-                for (int i = 0; i < 9; ++i) {
-                    const int f = e * 9 + i;
-                    const float4 v = q[f >> 2];
-                    r[e][i] = (f & 3) == 0 ? v.x : (f & 3) == 1 ? v.y : (f & 3) == 2 ? v.z : v.w;
-                }
-        } else {
-#pragma unroll
-            for (int e = 0; e < 4; ++e)
-#pragma unroll
-                for (int i = 0; i < 9; ++i) r[e][i] = n0 + e < N ? rp[e * 9 + i] : 0.0f;
-        }
-        bool hit = false;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            const bool exists = n0 + e < N;
-            const bool scored = exists && fabsf(sc[e]) < __builtin_inff();  // false for NaN and +-inf
-            excluded += (exists && !scored) ? 1 : 0;
-            bk[e] = scored ? K : -1;
-        }
-        for (int k = K - 1; k >= 0; --k) {  // descending: the FIRST matching anchor is the one left standing
-            if (!used[k]) continue;
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                float acc = 0.0f;
-#pragma unroll
-                for (int i = 0; i < 9; ++i) acc = fmaf(r[e][i], anc[k][i], acc);
-                bk[e] = (bk[e] >= 0 && acc >= tau) ? k : bk[e];  // false for a NaN t
-            }
-        }
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            if (bk[e] < 0) continue;
-            post_add(whole, sc[e], r[e], beta);
-            if (bk[e] == K) post_add(rest, sc[e], r[e], beta);
-            else hit = true;
-        }
-        if (__ballot(hit)) {  // rare (a 15-degree cap holds 0.1 % of SO(3)); wave-uniform from here on
-            for (int k = 0; k < K; ++k) {
-                const bool mine = bk[0] == k || bk[1] == k || bk[2] == k || bk[3] == k;
-                if (!__ballot(mine)) continue;
-                PostAcc a;
-                post_clear(a);
-#pragma unroll
-                for (int e = 0; e < 4; ++e)
-                    if (bk[e] == k) post_add(a, sc[e], r[e], beta);
-                post_wave_into(a, beta_d, rows[wave][k]);
-            }
-        }
-    }
-    post_wave_into(rest, beta_d, rows[wave][K]);
-    post_wave_into(whole, beta_d, rows[wave][K + 1]);
-    if (excluded) atomicAdd(&n_excl, excluded);  // an integer count: order does not matter
-    __syncthreads();
-    char* st = partial + ((size_t)blockIdx.x * B + b) * posterior_state_stride_dev(K);
-    if (tid < K + 2) {  // the four waves in the order 0..3
-        double rec[kPostRec];
-#pragma unroll
-        for (int i = 0; i < kPostRec; ++i) rec[i] = rows[0][tid][i];
-#pragma unroll
-        for (int w = 1; w < kTopkThreads / 64; ++w) post_merge(rec, rows[w][tid], beta_d);
-        double* dst = reinterpret_cast<double*>(st + kPostHeader) + tid * kPostRec;
-#pragma unroll
-        for (int i = 0; i < kPostRec; ++i) dst[i] = rec[i];
-    }
-    if (tid == 63) {
-        reinterpret_cast<long long*>(st)[0] = n_excl;
-        reinterpret_cast<long long*>(st)[1] = 0;
-    }
-}
-
-// states [P][B] -> state [B], in the order p = 0 .. P-1; carry: state's own content comes first
-__global__ __launch_bounds__(64) void posterior_merge_kernel(const char* __restrict__ states, int P, int B, int K, float beta,
-                                                             char* __restrict__ state, bool carry)
-{
-    const int b = blockIdx.x, j = threadIdx.x;
-    const size_t stride = posterior_state_stride_dev(K);
-    char* dst = state + (size_t)b * stride;
-    if (j < K + 2) {
-        double* d = reinterpret_cast<double*>(dst + kPostHeader) + j * kPostRec;
-        double rec[kPostRec];
-#pragma unroll
-        for (int i = 0; i < kPostRec; ++i) rec[i] = carry ? d[i] : (i == 0 ? (double)-INFINITY : 0.0);
-        for (int p = 0; p < P; ++p) {
-            const double* src = reinterpret_cast<const double*>(states + ((size_t)p * B + b) * stride + kPostHeader) + j * kPostRec;
-            double in[kPostRec];
-#pragma unroll
-            for (int i = 0; i < kPostRec; ++i) in[i] = src[i];
-            post_merge(rec, in, (double)beta);
-        }
-#pragma unroll
-        for (int i = 0; i < kPostRec; ++i) d[i] = rec[i];
-    }
-    if (j == 63) {
-        long long n = carry ? reinterpret_cast<const long long*>(dst)[0] : 0;
-        for (int p = 0; p < P; ++p) n += reinterpret_cast<const long long*>(states + ((size_t)p * B + b) * stride)[0];
-        reinterpret_cast<long long*>(dst)[0] = n;
-        reinterpret_cast<long long*>(dst)[1] = 0;
-    }
-}
-
-// one Jacobi rotation of the symmetric A (4 x 4) in the (P, Q) plane, accumulated into V
-template <int P, int Q>
-__device__ __forceinline__ void jacobi4_rotate(double (&A)[4][4], double (&V)[4][4])
-{
-    const double apq = A[P][Q];
-    if (apq == 0.0) return;
-    const double theta = (A[Q][Q] - A[P][P]) / (2.0 * apq);
-    const double t = (theta >= 0.0 ? 1.0 : -1.0) / (fabs(theta) + sqrt(theta * theta + 1.0));
-    const double c = 1.0 / sqrt(t * t + 1.0), s = t * c;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {  // A <- A J
-        const double akp = A[k][P], akq = A[k][Q];
-        A[k][P] = c * akp - s * akq;
-        A[k][Q] = s * akp + c * akq;
-    }
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {  // A <- J^T A
-        const double apk = A[P][k], aqk = A[Q][k];
-        A[P][k] = c * apk - s * aqk;
-        A[Q][k] = s * apk + c * aqk;
-    }
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        const double vkp = V[k][P], vkq = V[k][Q];
-        V[k][P] = c * vkp - s * vkq;
-        V[k][Q] = s * vkp + c * vkq;
-    }
-}
-
-// Rm = the rotation nearest to M (Frobenius), spread = the angle whose cosine is (sum Rm o M - 1) / 2, in degrees.
-// M is a weighted mean of the matrices (already divided by the mass).
-__device__ __forceinline__ void post_project(const double* M, float* Rm, float* spread)
-{
-    double A[4][4] = {{M[0] + M[4] + M[8], M[7] - M[5], M[2] - M[6], M[3] - M[1]},
-                      {M[7] - M[5], M[0] - M[4] - M[8], M[1] + M[3], M[2] + M[6]},
-                      {M[2] - M[6], M[1] + M[3], -M[0] + M[4] - M[8], M[5] + M[7]},
-                      {M[3] - M[1], M[2] + M[6], M[5] + M[7], -M[0] - M[4] + M[8]}};
-    double V[4][4] = {{1, 0, 0, 0}, {0, 1, 0, 0}, {0, 0, 1, 0}, {0, 0, 0, 1}};
-#pragma unroll 1
-    for (int sweep = 0; sweep < 12; ++sweep) {  // cyclic Jacobi converges quadratically: 12 sweeps are far past fp64 for a 4 x 4
-        jacobi4_rotate<0, 1>(A, V);
-        jacobi4_rotate<0, 2>(A, V);
-        jacobi4_rotate<0, 3>(A, V);
-        jacobi4_rotate<1, 2>(A, V);
-        jacobi4_rotate<1, 3>(A, V);
-        jacobi4_rotate<2, 3>(A, V);
-    }
-    double best = A[0][0], q[4] = {V[0][0], V[1][0], V[2][0], V[3][0]};
-#pragma unroll
-    for (int c = 1; c < 4; ++c) {
-        const bool take = A[c][c] > best;
-        best = take ? A[c][c] : best;
-#pragma unroll
-        for (int k = 0; k < 4; ++k) q[k] = take ? V[k][c] : q[k];
-    }
-    const double nn = 1.0 / sqrt(q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3]);
-    const double w = q[0] * nn, x = q[1] * nn, y = q[2] * nn, z = q[3] * nn;
-    const double Rd[9] = {1.0 - 2.0 * (y * y + z * z), 2.0 * (x * y - w * z), 2.0 * (x * z + w * y),
-                          2.0 * (x * y + w * z), 1.0 - 2.0 * (x * x + z * z), 2.0 * (y * z - w * x),
-                          2.0 * (x * z - w * y), 2.0 * (y * z + w * x), 1.0 - 2.0 * (x * x + y * y)};
-    double dot = 0.0;
-#pragma unroll
-    for (int i = 0; i < 9; ++i) dot += Rd[i] * M[i];
-    double cs = (dot - 1.0) * 0.5;
-    cs = cs < -1.0 ? -1.0 : cs > 1.0 ? 1.0 : cs;  // (a NaN stays a NaN)
-    if (Rm) {
-#pragma unroll
-        for (int i = 0; i < 9; ++i) Rm[i] = (float)Rd[i];
-    }
-    if (spread) *spread = (float)(acos(cs) * 57.295779513082320877);
-}
-
-// thread j of block b: bucket j < K, the rest bucket (j = K) or the whole set (j = K + 1)
-__global__ __launch_bounds__(64) void posterior_finish_kernel(const char* __restrict__ state, int B, int K, float beta,
-                                                              float* __restrict__ log_z, float* __restrict__ entropy,
-                                                              float* __restrict__ mean_score, long long* __restrict__ n_excluded,
-                                                              float* __restrict__ mode_prob, float* __restrict__ rest_prob,
-                                                              float* __restrict__ mode_R_mean, float* __restrict__ R_mean,
-                                                              float* __restrict__ mode_spread, float* __restrict__ spread)
-{
-    const int b = blockIdx.x, j = threadIdx.x;
-    if (j >= K + 2) return;
-    const char* st = state + (size_t)b * posterior_state_stride_dev(K);
-    const double* recs = reinterpret_cast<const double*>(st + kPostHeader);
-    const double* all = recs + (K + 1) * kPostRec;
-    const double* me = recs + j * kPostRec;
-    const double bd = (double)beta, m_all = all[0], Z = all[1];
-    const bool empty = !(me[1] > 0.0);  // an empty slot, a bucket without a member, an empty scored set
-    if (j == K + 1) {
-        if (n_excluded) n_excluded[b] = reinterpret_cast<const long long*>(st)[0];
-        if (log_z) log_z[b] = empty ? -INFINITY : (float)(m_all * bd + log(Z));
-        if (entropy) entropy[b] = empty ? __builtin_nanf("") : (float)(log(Z) - bd * (all[2] / Z - m_all));
-        if (mean_score) mean_score[b] = empty ? __builtin_nanf("") : (float)(all[2] / Z);
-    } else {
-        const float p = empty ? 0.0f : (float)(me[1] * exp((me[0] - m_all) * bd) / Z);
-        if (j == K) {
-            if (rest_prob) rest_prob[b] = p;
-            return;
-        }
-        if (mode_prob) mode_prob[(long)b * K + j] = p;
-    }
-    float* Rm = j <= K ? (mode_R_mean ? mode_R_mean + ((long)b * K + j) * 9 : nullptr) : (R_mean ? R_mean + (long)b * 9 : nullptr);
-    float* sp = j <= K ? (mode_spread ? mode_spread + (long)b * K + j : nullptr) : (spread ? spread + b : nullptr);
-    if (!Rm && !sp) return;
-    if (empty) {
-        if (Rm) {
-#pragma unroll
-            for (int i = 0; i < 9; ++i) Rm[i] = 0.0f;
-        }
-        if (sp) *sp = __builtin_nanf("");
-        return;
-    }
-    double M[9];
-#pragma unroll
-    for (int i = 0; i < 9; ++i) M[i] = me[3 + i] / me[1];
-    post_project(M, Rm, sp);
-}
-
-// ---------------------------------------------------------------------------------
 // Haar-uniform rotation hypotheses generated on the device (replaces the host call
 // pytorch3d.transforms.random_rotations(N), test_co3d.py:106 / modules/model.py:184; only the
 // distribution matters -- hypotheses are inputs of the hot path).  Counter-based: rotation n
@@ -1443,27 +662,6 @@ hipError_t launch_score_features(const float* f_src, const float* f_tgt, int B, 
     return hipGetLastError();
 }
 
-hipError_t launch_compose_rotations(const int64_t* best_key, const float* R, int64_t r_batch_stride,
-                                    int64_t n_offset, int64_t N, const float* D, int64_t N2, int B, float* out,
-                                    hipStream_t stream)
-{
-    const long total = (long)B * N2;
-    hipLaunchKernelGGL(compose_rotations_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream,
-                       reinterpret_cast<const key_t*>(best_key), R, (long)r_batch_stride, (long)n_offset, (long)N, D,
-                       (long)N2, B, out);
-    return hipGetLastError();
-}
-
-hipError_t launch_select_rotation(int64_t* best_key, const float* R, int64_t r_batch_stride, int64_t n_offset,
-                                  int64_t N, int B, float* R_out, float* best_score, int64_t* best_idx, bool reset,
-                                  hipStream_t stream)
-{
-    hipLaunchKernelGGL(select_rotation_kernel, dim3((B + 63) / 64), dim3(64), 0, stream,
-                       reinterpret_cast<key_t*>(best_key), R, (long)r_batch_stride, (long)n_offset, (long)N, B, R_out,
-                       best_score, reinterpret_cast<long*>(best_idx), reset);
-    return hipGetLastError();
-}
-
 hipError_t launch_random_rotations(uint64_t seed, uint64_t offset, int64_t N, float* out, hipStream_t stream)
 {
     hipLaunchKernelGGL(random_rotations_kernel, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, stream,
@@ -1475,134 +673,6 @@ hipError_t launch_so3_grid(int64_t n_total, int64_t offset, int64_t N, float* ou
 {
     hipLaunchKernelGGL(so3_grid_kernel, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, stream, (long)n_total,
                        (long)offset, (long)N, out);
-    return hipGetLastError();
-}
-
-hipError_t launch_argmax(const float* scores, int B, int64_t N, int64_t n_offset, int64_t* best_key,
-                         int num_cu, hipStream_t stream)
-{
-    long bx = (N + 255) / 256;
-    const long cap = num_cu * 4 / (B < num_cu ? B : num_cu) + 1;
-    if (bx > cap) bx = cap;
-    hipLaunchKernelGGL(argmax_kernel, dim3((unsigned)bx, (unsigned)B), dim3(256), 0, stream, scores, B, (long)N,
-                       (long)n_offset, reinterpret_cast<key_t*>(best_key));
-    return hipGetLastError();
-}
-
-// partial lists per sample of a top-K launch over N scores: a pure function of N (the workspace is sized by it)
-int topk_parts(int64_t N)
-{
-    const int64_t tiles = (N + 3 + kTopkTile - 1) / kTopkTile;  // + 3: the row may start up to three floats past a 16-byte line
-    return (int)(tiles < kTopkMaxParts ? tiles : kTopkMaxParts);
-}
-
-hipError_t launch_topk_merge(const int64_t* lists, int P, int B, int K, int64_t* keys, bool carry, hipStream_t stream)
-{
-    hipLaunchKernelGGL(topk_kernel<false>, dim3(1, (unsigned)B), dim3(kTopkThreads), 0, stream,
-                       static_cast<const void*>(lists), B, (long)P, 0l, K, reinterpret_cast<key_t*>(keys), carry);
-    return hipGetLastError();
-}
-
-hipError_t launch_topk(const float* scores, int B, int64_t N, int64_t n_offset, int K, int64_t* keys, int64_t* workspace,
-                       bool carry, hipStream_t stream)
-{
-    const int parts = topk_parts(N);
-    if (parts <= 1) {  // one tile: straight into the caller's list
-        hipLaunchKernelGGL(topk_kernel<true>, dim3(1, (unsigned)B), dim3(kTopkThreads), 0, stream,
-                           static_cast<const void*>(scores), B, (long)N, (long)n_offset, K, reinterpret_cast<key_t*>(keys),
-                           carry);
-        return hipGetLastError();
-    }
-    hipLaunchKernelGGL(topk_kernel<true>, dim3((unsigned)parts, (unsigned)B), dim3(kTopkThreads), 0, stream,
-                       static_cast<const void*>(scores), B, (long)N, (long)n_offset, K,
-                       reinterpret_cast<key_t*>(workspace), false);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return e;
-    return launch_topk_merge(workspace, parts, B, K, keys, carry, stream);
-}
-
-hipError_t launch_select_topk(int64_t* keys, int K, const float* R, int64_t r_batch_stride, int64_t n_offset, int64_t N,
-                              int B, float* R_out, float* scores_out, int64_t* idx_out, bool reset, hipStream_t stream)
-{
-    const long total = (long)B * K;
-    hipLaunchKernelGGL(select_topk_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream,
-                       reinterpret_cast<key_t*>(keys), K, R, (long)r_batch_stride, (long)n_offset, (long)N, B, R_out,
-                       scores_out, reinterpret_cast<long*>(idx_out), reset);
-    return hipGetLastError();
-}
-
-hipError_t launch_compose_rotations_topk(const int64_t* keys, int K, const float* R, int64_t r_batch_stride,
-                                         int64_t n_offset, int64_t N, const float* D, int64_t N2, int B, float* out,
-                                         hipStream_t stream)
-{
-    const long total = (long)B * K * N2;
-    hipLaunchKernelGGL(compose_rotations_topk_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream,
-                       reinterpret_cast<const key_t*>(keys), K, R, (long)r_batch_stride, (long)n_offset, (long)N, D,
-                       (long)N2, B, out);
-    return hipGetLastError();
-}
-
-// best_key[0..B) = EMPTY (below every real key): one tiny launch, graph-capturable
-__global__ void fill_keys_kernel(key_t* __restrict__ k, int B)
-{
-    const int b = blockIdx.x * blockDim.x + threadIdx.x;
-    if (b < B) k[b] = kKeyEmpty;
-}
-
-hipError_t launch_fill_keys(int64_t* best_key, int B, hipStream_t stream)
-{
-    hipLaunchKernelGGL(fill_keys_kernel, dim3((B + 255) / 256), dim3(256), 0, stream, reinterpret_cast<key_t*>(best_key), B);
-    return hipGetLastError();
-}
-
-// hypotheses per sample of the alive state of ahv_topk_modes_f32: N rounded up to a lane's four
-int64_t topk_modes_state_stride(int64_t N) { return (N + 3) & ~(int64_t)3; }
-
-// K + 1 launches: the list filled EMPTY, round 0, rounds 1 .. K - 1 (each reads the entry the one before reduced)
-hipError_t launch_topk_modes(const float* scores, const float* R, int64_t r_batch_stride, int B, int64_t N, int64_t n_offset,
-                             int K, float tau, int64_t* keys, int64_t* state, hipStream_t stream)
-{
-    hipError_t e = launch_fill_keys(keys, B * K, stream);
-    if (e != hipSuccess) return e;
-    const int64_t tiles = (N + kTopkTile - 1) / kTopkTile;
-    const dim3 grid((unsigned)(tiles < 1024 ? tiles : 1024), (unsigned)B);
-    const long Ns = (long)topk_modes_state_stride(N);
-    hipLaunchKernelGGL(topk_modes_kernel<true>, grid, dim3(kTopkThreads), 0, stream, scores, R, (long)r_batch_stride, (long)N,
-                       Ns, (long)n_offset, K, 0, tau, reinterpret_cast<key_t*>(state), reinterpret_cast<key_t*>(keys));
-    for (int j = 1; j < K; ++j)
-        hipLaunchKernelGGL(topk_modes_kernel<false>, grid, dim3(kTopkThreads), 0, stream, scores, R, (long)r_batch_stride,
-                           (long)N, Ns, (long)n_offset, K, j, tau, reinterpret_cast<key_t*>(state),
-                           reinterpret_cast<key_t*>(keys));
-    return hipGetLastError();
-}
-
-// ---- pose posterior ---------------------------------------------------------------------------------------
-hipError_t launch_posterior_merge(const void* states, int P, int B, int K, float beta, void* state, bool carry, hipStream_t stream)
-{
-    hipLaunchKernelGGL(posterior_merge_kernel, dim3((unsigned)B), dim3(64), 0, stream, static_cast<const char*>(states), P, B, K,
-                       beta, static_cast<char*>(state), carry);
-    return hipGetLastError();
-}
-
-// two launches: one partial state per workgroup into the workspace, then their merge into (or over) the caller's state
-hipError_t launch_posterior(const float* scores, const float* R, int64_t r_batch_stride, int B, int64_t N, const float* anchors,
-                            int K, float tau, float beta, void* state, void* workspace, bool carry, hipStream_t stream)
-{
-    const int parts = posterior_parts(N);
-    hipLaunchKernelGGL(posterior_partial_kernel, dim3((unsigned)parts, (unsigned)B), dim3(kTopkThreads), 0, stream, scores, R,
-                       (long)r_batch_stride, B, (long)N, anchors, K, tau, beta, static_cast<char*>(workspace));
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return e;
-    return launch_posterior_merge(workspace, parts, B, K, beta, state, carry, stream);
-}
-
-hipError_t launch_posterior_finish(const void* state, int B, int K, float beta, float* log_z, float* entropy, float* mean_score,
-                                   int64_t* n_excluded, float* mode_prob, float* rest_prob, float* mode_R_mean, float* R_mean,
-                                   float* mode_spread_deg, float* spread_deg, hipStream_t stream)
-{
-    hipLaunchKernelGGL(posterior_finish_kernel, dim3((unsigned)B), dim3(64), 0, stream, static_cast<const char*>(state), B, K, beta,
-                       log_z, entropy, mean_score, reinterpret_cast<long long*>(n_excluded), mode_prob, rest_prob, mode_R_mean,
-                       R_mean, mode_spread_deg, spread_deg);
     return hipGetLastError();
 }
 
@@ -1648,105 +718,6 @@ hipError_t launch_zero_fill(void* const* ptrs, const size_t* bytes, int count, h
     if (blocks < 1) blocks = 1;
     if (blocks > 2048) blocks = 2048;
     hipLaunchKernelGGL(zero_fill_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, a);
-    return hipGetLastError();
-}
-
-// ---- SO(3) ascent step (ahv_so3_ascent_candidates_f32 / ahv_so3_ascent_select_f32) ----------------------
-// One thread per seed (b, k); rotations.so3_ascent_candidates / so3_ascent_select state the same rules in torch.
-// Direction: the Riemannian gradient in the body frame, w = vee(1/2 (R^T G - G^T R)); candidate slot 0 is R_cur bit for bit,
-// slot l >= 1 is R_cur exp(ladder[l-1] theta [w / |w|]x) (Rodrigues, 1 - cos a as 2 sin^2(a / 2)); |w| = 0 or a non-finite w:
-// every slot is R_cur.
-__global__ __launch_bounds__(256) void so3_ascent_candidates_kernel(const float* __restrict__ R_cur, const float* __restrict__ grad_R,
-                                                                    const float* __restrict__ theta, const float* __restrict__ ladder,
-                                                                    int L, int seeds, float* __restrict__ R_cand)
-{
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i >= seeds) return;
-    float R[9], G[9];
-#pragma unroll
-    for (int j = 0; j < 9; ++j) {
-        R[j] = R_cur[(long)i * 9 + j];
-        G[j] = grad_R[(long)i * 9 + j];
-    }
-    float A[9];   // R^T G
-#pragma unroll
-    for (int r = 0; r < 3; ++r)
-#pragma unroll
-        for (int c = 0; c < 3; ++c) A[3 * r + c] = R[r] * G[c] + R[3 + r] * G[3 + c] + R[6 + r] * G[6 + c];
-    const float wx = 0.5f * (A[7] - A[5]), wy = 0.5f * (A[2] - A[6]), wz = 0.5f * (A[3] - A[1]);
-    const float nrm = sqrtf(wx * wx + wy * wy + wz * wz);
-    const bool move = nrm > 0.0f && nrm < __builtin_inff();   // false for NaN
-    const float inv = move ? 1.0f / nrm : 0.0f;
-    const float nx = wx * inv, ny = wy * inv, nz = wz * inv;
-    const float th = theta[i];
-    float* out = R_cand + (long)i * (L + 1) * 9;
-#pragma unroll
-    for (int j = 0; j < 9; ++j) out[j] = R[j];
-    for (int l = 1; l <= L; ++l) {
-        float* o = out + l * 9;
-        if (!move) {
-#pragma unroll
-            for (int j = 0; j < 9; ++j) o[j] = R[j];
-            continue;
-        }
-        const float a = ladder[l - 1] * th;
-        const float sn = sinf(a), sh = sinf(0.5f * a), c1 = 2.0f * sh * sh;
-        // E = I + sin a K + (1 - cos a) (n n^T - I), K = [n]x
-        const float E[9] = {1.0f + c1 * (nx * nx - 1.0f), c1 * nx * ny - sn * nz, c1 * nx * nz + sn * ny,
-                            c1 * nx * ny + sn * nz, 1.0f + c1 * (ny * ny - 1.0f), c1 * ny * nz - sn * nx,
-                            c1 * nx * nz - sn * ny, c1 * ny * nz + sn * nx, 1.0f + c1 * (nz * nz - 1.0f)};
-#pragma unroll
-        for (int r = 0; r < 3; ++r)
-#pragma unroll
-            for (int c = 0; c < 3; ++c) o[3 * r + c] = R[3 * r] * E[c] + R[3 * r + 1] * E[3 + c] + R[3 * r + 2] * E[6 + c];
-    }
-}
-
-// A candidate replaces the incumbent only if its score is strictly greater (false for NaN), slots scanned in order: a seed's
-// score never decreases, slot 0 (R_cur itself) wins a tie.  theta <- ladder[l-1] theta for the accepted slot, theta min(ladder)
-// when slot 0 stayed.
-__global__ __launch_bounds__(256) void so3_ascent_select_kernel(const float* __restrict__ R_cand, const float* __restrict__ cand_scores,
-                                                                const float* __restrict__ ladder, int L, int seeds,
-                                                                float* __restrict__ R_cur, float* __restrict__ score_cur,
-                                                                float* __restrict__ theta)
-{
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i >= seeds) return;
-    const float* sc = cand_scores + (long)i * (L + 1);
-    float best = sc[0], lmin = ladder[0];
-    int slot = 0;
-    for (int l = 1; l <= L; ++l) {
-        const float s = sc[l];
-        if (s > best) {
-            best = s;
-            slot = l;
-        }
-        lmin = fminf(lmin, ladder[l - 1]);
-    }
-    const float* src = R_cand + ((long)i * (L + 1) + slot) * 9;
-#pragma unroll
-    for (int j = 0; j < 9; ++j) R_cur[(long)i * 9 + j] = src[j];
-    score_cur[i] = best;
-    theta[i] = theta[i] * (slot ? ladder[slot - 1] : lmin);
-}
-
-hipError_t launch_so3_ascent_candidates(const float* R_cur, const float* grad_R, const float* theta, const float* ladder, int L,
-                                        int B, int K, float* R_cand, hipStream_t stream)
-{
-    const int seeds = B * K;
-    if (seeds == 0) return hipSuccess;
-    hipLaunchKernelGGL(so3_ascent_candidates_kernel, dim3((seeds + 255) / 256), dim3(256), 0, stream, R_cur, grad_R, theta,
-                       ladder, L, seeds, R_cand);
-    return hipGetLastError();
-}
-
-hipError_t launch_so3_ascent_select(const float* R_cand, const float* cand_scores, const float* ladder, int L, int B, int K,
-                                    float* R_cur, float* score_cur, float* theta, hipStream_t stream)
-{
-    const int seeds = B * K;
-    if (seeds == 0) return hipSuccess;
-    hipLaunchKernelGGL(so3_ascent_select_kernel, dim3((seeds + 255) / 256), dim3(256), 0, stream, R_cand, cand_scores, ladder,
-                       L, seeds, R_cur, score_cur, theta);
     return hipGetLastError();
 }
 

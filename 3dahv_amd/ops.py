@@ -554,6 +554,24 @@ def compose_rotations(best_key: torch.Tensor, R: torch.Tensor, D: torch.Tensor, 
 _TOPK_WS = {}
 
 
+def _workspace(cache: dict, key: tuple, nbytes: int, dtype: torch.dtype, given: torch.Tensor | None = None):
+    """``(workspace or None, bytes it holds)`` for a call that needs ``nbytes``: the caller's tensor when ``given``, else the
+    static buffer ``cache[key]`` (``key[0]`` is the device), allocated on first use; none at all when nothing is needed.  With
+    ``given`` nothing is allocated (capture)."""
+    dev = key[0]
+    ws = given
+    if ws is None and nbytes:
+        ws = cache.get(key)
+        if ws is None:
+            ws = cache[key] = torch.empty((nbytes // dtype.itemsize,), dtype=dtype, device=dev)
+    have = 0
+    if ws is not None:
+        if ws.device != dev or not ws.is_contiguous():
+            raise RuntimeError("workspace must be a contiguous tensor on %s" % dev)
+        have = ws.numel() * ws.element_size()
+    return ws, have
+
+
 def _topk_k(k) -> int:
     k = int(k)
     if not 1 <= k <= _lib.AHV_TOPK_MAX_K:
@@ -587,14 +605,9 @@ def topk(scores: torch.Tensor, k: int, n_offset: int = 0, keys: torch.Tensor | N
     elif _topk_list(keys) != (B, k) or keys.device != dev:
         raise RuntimeError("keys must be a (B,K) = %s int64 tensor on %s" % ((B, k), dev))
     s = scores.detach().contiguous()
-    nbytes = _lib.load().ahv_topk_workspace_bytes(B, N, k)
-    ws = None
-    if nbytes:
-        ws = _TOPK_WS.get((dev, B, N, k))
-        if ws is None:
-            ws = _TOPK_WS[(dev, B, N, k)] = torch.empty((nbytes // 8,), dtype=torch.int64, device=dev)
+    ws, have = _workspace(_TOPK_WS, (dev, B, N, k), _lib.load().ahv_topk_workspace_bytes(B, N, k), torch.int64)
     _call(dev, "ahv_topk_f32", s.data_ptr(), B, N, n_offset, k, keys.data_ptr(), ws.data_ptr() if ws is not None else None,
-          nbytes, _lib.AHV_TOPK_RESET_LIST if reset else 0)
+          have, _lib.AHV_TOPK_RESET_LIST if reset else 0)
     return keys
 
 
@@ -728,16 +741,8 @@ def topk_modes(scores: torch.Tensor, R: torch.Tensor, k: int, min_angle_deg: flo
     elif _topk_list(keys) != (B, k) or keys.device != dev:
         raise RuntimeError("keys must be a (B,K) = %s int64 tensor on %s" % ((B, k), dev))
     s, Rc = scores.detach().contiguous(), R.detach().contiguous()
-    nbytes = _lib.load().ahv_topk_modes_workspace_bytes(B, N, k)
-    if workspace is None and nbytes:
-        workspace = _MODES_WS.get((dev, B, N))
-        if workspace is None:
-            workspace = _MODES_WS[(dev, B, N)] = torch.empty((nbytes // 8,), dtype=torch.int64, device=dev)
-    have = 0
-    if workspace is not None:
-        if workspace.device != dev or not workspace.is_contiguous():
-            raise RuntimeError("workspace must be a contiguous tensor on %s" % dev)
-        have = workspace.numel() * workspace.element_size()
+    workspace, have = _workspace(_MODES_WS, (dev, B, N), _lib.load().ahv_topk_modes_workspace_bytes(B, N, k), torch.int64,
+                                 workspace)
     _call(dev, "ahv_topk_modes_f32", s.data_ptr(), Rc.data_ptr(), rstride, B, N, n_offset, k, tau, keys.data_ptr(),
           workspace.data_ptr() if workspace is not None else None, have)
     return keys
@@ -888,15 +893,7 @@ def pose_posterior(scores: torch.Tensor, R: torch.Tensor, temperature: float = 0
         reset = True
     elif _posterior_state(state, k)[0] != B or state.dim() != 2 or state.device != dev:
         raise RuntimeError("state must be a (B, stride) uint8 tensor for B = %d, K = %d on %s" % (B, k, dev))
-    if workspace is None and nbytes:
-        workspace = _POSTERIOR_WS.get((dev, B, N, k))
-        if workspace is None:
-            workspace = _POSTERIOR_WS[(dev, B, N, k)] = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
-    have = 0
-    if workspace is not None:
-        if workspace.device != dev or not workspace.is_contiguous():
-            raise RuntimeError("workspace must be a contiguous tensor on %s" % dev)
-        have = workspace.numel() * workspace.element_size()
+    workspace, have = _workspace(_POSTERIOR_WS, (dev, B, N, k), nbytes, torch.uint8, workspace)
     s, Rc = scores.detach().contiguous(), R.detach().contiguous()
     Ac = anchors.detach().contiguous() if k else None
     _call(dev, "ahv_pose_posterior_f32", s.data_ptr(), Rc.data_ptr(), rstride, B, N, Ac.data_ptr() if k else None, k, tau, beta,

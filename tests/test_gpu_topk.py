@@ -265,6 +265,66 @@ def test_select_and_compose(ahv, setup, per_sample):
     assert float(np.max(np.abs(f3[:, (K - 1) * N2:].cpu().numpy() - want0))) <= 2.0 ** -23
 
 
+@pytest.mark.parametrize("per_sample", [False, True])
+def test_single_best_decode_against_the_host_codec(ahv, setup, per_sample):
+    """``select_rotation`` / ``compose_rotations`` (the list kernels at K = 1) against ``dist.unpack_keys_host`` and a torch
+    gather of the rows -- not against the list calls, which run the same kernels.  B = 1, 64, 65, 257 keys cross the
+    workgroup boundary (256 slots); this rank holds hypotheses 10 .. 46 of 47 (N = 37, n_offset = 10)."""
+    dev = setup[0]
+    NF, lo = 47, 10
+    N = NF - lo
+    for B in (1, 64, 65, 257):
+        rng = np.random.default_rng(B)
+        sc = rng.standard_normal(B).astype(np.float32)
+        gi = rng.integers(lo, NF, B)
+        Rn = ahv.rotations.haar_rotations_np(B * NF, 5).reshape(B, NF, 3, 3)
+        R = torch.from_numpy(Rn if per_sample else Rn[0]).to(dev)[..., lo:, :, :]
+        for special in ("empty", "foreign", "nan"):
+            s, g = sc.copy(), gi.copy()
+            at = B // 2
+            if special == "foreign":
+                g[at] = lo - 6          # below the slice; with B >= 64 one above it as well (a global index past n_offset + N)
+                g[B - 1] = NF + 3 if B > 1 else g[B - 1]
+            if special == "nan":
+                s[at] = np.nan
+                s[0] = -0.0 if B > 1 else s[0]
+            keys = ahv.dist.pack_keys_host(s, g).reshape(B).copy()
+            if special == "empty":
+                keys[at] = EMPTY
+            want_s, want_i = ahv.dist.unpack_keys_host(keys)
+            if special == "empty":
+                assert want_s[at] == -np.inf and want_i[at] == -1
+            mine = torch.from_numpy((keys != EMPTY) & (want_i >= lo) & (want_i < NF)).to(dev)
+            loc = torch.from_numpy(np.clip(want_i - lo, 0, N - 1)).to(dev)
+            rows = R[torch.arange(B, device=dev), loc] if per_sample else R[loc]
+            want_R = torch.where(mine[:, None, None], rows, torch.zeros_like(rows))
+            assert int((~mine).sum()) == {"empty": 1, "foreign": 2 if B > 1 else 1, "nan": 0}[special]
+            for reset in (False, True):
+                k = torch.from_numpy(keys.copy()).to(dev)
+                got_s, got_i, got_R = ahv.ops.select_rotation(k, R, n_offset=lo, reset_key=reset)
+                assert got_s.shape == (B,) and got_i.shape == (B,) and got_R.shape == (B, 3, 3)
+                assert np.array_equal(got_i.cpu().numpy(), want_i)
+                assert np.array_equal(got_s.cpu().numpy().view(np.uint32), want_s.view(np.uint32))
+                assert torch.equal(got_R, want_R)
+                assert np.array_equal(k.cpu().numpy(), np.full(B, EMPTY) if reset else keys)
+    # compose_rotations: 5 x 67 matrices span two workgroups; an EMPTY key and a foreign one compose row 0 (stay in bounds)
+    B, N2 = 5, 67
+    D = ahv.rotations.refine_rotations(torch.eye(3), N2, 8.0, generator=torch.Generator().manual_seed(1)).to(dev)
+    Rn = ahv.rotations.haar_rotations_np(B * NF, 6).reshape(B, NF, 3, 3)
+    R = torch.from_numpy(Rn if per_sample else Rn[0]).to(dev)[..., lo:, :, :]
+    g = np.array([lo, NF - 1, 23, 3, 30])
+    keys = ahv.dist.pack_keys_host(np.arange(B, dtype=np.float32), g).reshape(B).copy()
+    keys[4] = EMPTY
+    loc = torch.tensor([0, N - 1, 23 - lo, 0, 0], device=dev)
+    rows = R[torch.arange(B, device=dev), loc] if per_sample else R[loc]
+    fine = ahv.ops.compose_rotations(torch.from_numpy(keys).to(dev), R, D, n_offset=lo)
+    assert fine.shape == (B, N2, 3, 3)
+    want = host_compose(rows[:, None].cpu().numpy(), D.cpu().numpy())
+    err = float(np.max(np.abs(fine.cpu().numpy() - want)))
+    print("compose_rotations: max abs diff to the host expression %.3e" % err)
+    assert err <= 2.0 ** -23
+
+
 # ---- the multi-seed coarse-to-fine step ---------------------------------------------------------------------------------
 
 @pytest.mark.parametrize("B", [1, 3])
