@@ -25,6 +25,9 @@ AHV_TOPK_RESET_LIST = 1
 AHV_SO3_MAX_LADDER = 8
 AHV_POSTERIOR_MAX_MODES = 16
 AHV_POSTERIOR_RESET_STATE = 1
+AHV_VIEWS_MAX = 16
+AHV_VIEWS_RESET_BEST = 1
+AHV_VIEWS_NO_ANGLE_LIMIT = 2
 
 _vp = ctypes.c_void_p
 _i64 = ctypes.c_int64
@@ -97,6 +100,10 @@ SIGNATURES["ahv_pose_posterior_f32"] = (_int, [_vp, _vp, _i64, _int, _i64, _vp, 
                                                ctypes.c_size_t, _u32, _vp])
 SIGNATURES["ahv_pose_posterior_merge"] = (_int, [_vp, _int, _int, _int, ctypes.c_float, _vp, _u32, _vp])
 SIGNATURES["ahv_pose_posterior_finish_f32"] = (_int, [_vp, _int, _int, ctypes.c_float] + [_vp] * 10 + [_vp])
+SIGNATURES["ahv_view_rotations_f32"] = (_int, [_vp, _i64, _vp, _int, _int, _i64, _vp, _vp])
+# (scores, Q, q_batch_stride, A, weights: HOST floats, B, V, N, n_offset, min_trace, fused, best_key, flags, stream)
+SIGNATURES["ahv_fuse_view_scores_f32"] = (_int, [_vp, _vp, _i64, _vp, _vp, _int, _int, _i64, _i64, ctypes.c_float, _vp, _vp, _u32,
+                                                 _vp])
 
 # measurement / developer entry points (include/ahv_diag.h): not part of the drop-in boundary
 DIAG_SIGNATURES = {

@@ -557,6 +557,21 @@ class Feature_Aligner(nn.Module):
         from .patch import verify_hypotheses
         return verify_hypotheses(self, img_feat_src, img_feat_tgt, proposals, want_scores=want_scores, topk=topk, **kw)
 
+    def verify_views(self, vol_refs, vol_query, hypotheses, view_poses, **kw):
+        """The verify step against V posed reference views with this module's head weights (``ops.verify_views``):
+        ``vol_refs (B,V,16,8,8,8)`` with absolute rotations ``view_poses (B,V,3,3)``, the query volume ``(B,16,8,8,8)`` and
+        ``hypotheses`` of the query's absolute rotation -> ``(fused scores (B,N) | None, packed keys)``;
+        ``ops.select_rotation(keys, hypotheses)`` decodes the pose.  An inference call by the rule of ``verify_hypotheses``
+        (no_grad, or eval mode); a module in training mode with autograd recording is refused."""
+        from .patch import _inference_call
+        if not _inference_call(self):
+            raise RuntimeError("verify_views is the inference step (no autograd edge); the module is in training mode with "
+                               "autograd recording -- use rotate_volume / forward_3d2d (differentiable) or "
+                               "ops.score_hypotheses_autograd for the loss")
+        W1, W2, b2 = self.head_weights()
+        with torch.no_grad():
+            return ops.verify_views(vol_refs.detach(), vol_query.detach(), hypotheses, view_poses, W1, W2, b2, **kw)
+
     # ---- once-per-pair encoder replayed from a hipGraph -------------------------------------------
     def graphed_forward_2d3d(self, batch: int = 1):
         """Returns ``fn(layer4_src, layer4_tgt) -> (vol_src, vol_tgt)`` that replays ``forward_2d3d``

@@ -31,6 +31,9 @@ hipError_t launch_compose_rotations_topk(const int64_t*, int, const float*, int6
 int64_t topk_modes_state_stride(int64_t N);
 hipError_t launch_topk_modes(const float*, const float*, int64_t, int, int64_t, int64_t, int, float, int64_t*, int64_t*,
                              hipStream_t);
+hipError_t launch_view_rotations(const float*, int64_t, const float*, int, int, int64_t, float*, hipStream_t);
+hipError_t launch_fuse_views(const float*, const float*, int64_t, const float*, const float*, int, int, int64_t, int64_t, float,
+                             bool, float*, int64_t*, hipStream_t);
 size_t posterior_state_stride(int K);
 int posterior_parts(int64_t N);
 hipError_t launch_posterior(const float*, const float*, int64_t, int, int64_t, const float*, int, float, float, void*, void*, bool,
@@ -660,6 +663,65 @@ int ahv_topk_modes_f32(const float* scores, const float* R, int64_t r_batch_stri
     hipError_t e = ahv::launch_topk_modes(scores, R, r_batch_stride, B, N, n_offset, K, min_trace, keys,
                                           static_cast<int64_t*>(workspace), s);
     if (e != hipSuccess) return hip_fail("topk_modes: launch", e);
+    return AHV_OK;
+}
+
+// ---- multi-view verification ---------------------------------------------------------------------------------
+static int views_sizes(const char* who, int B, int V, int64_t N)
+{
+    if (V < 1 || V > AHV_VIEWS_MAX) return fail(AHV_EINVAL, "%s: V = %d outside 1..%d", who, V, AHV_VIEWS_MAX);
+    if (B < 1 || N < 1) return fail(AHV_EINVAL, "%s: B = %d and N = %lld must be at least 1", who, B, (long long)N);
+    if (B > 65535) return fail(AHV_EINVAL, "%s: B > 65535", who);
+    return AHV_OK;
+}
+
+int ahv_view_rotations_f32(const float* Q, int64_t q_batch_stride, const float* A, int B, int V, int64_t N, float* out,
+                           void* stream)
+{
+    if (int rc = views_sizes("view_rotations", B, V, N)) return rc;
+    if (N > 4294967296ll) return fail(AHV_EINVAL, "view_rotations: N must fit in 32 bits");
+    if (q_batch_stride != 0 && q_batch_stride != N * 9)
+        return fail(AHV_EINVAL, "view_rotations: q_batch_stride %lld must be 0 or N*9", (long long)q_batch_stride);
+    if ((int64_t)B * V * N > (int64_t)1 << 38)
+        return fail(AHV_EINVAL, "view_rotations: B*V*N = %lld output matrices exceed one launch (2^38)", (long long)((int64_t)B * V * N));
+    if (!Q || !A || !out) return fail(AHV_EINVAL, "view_rotations: null pointer");
+    hipError_t e = ahv::launch_view_rotations(Q, q_batch_stride, A, B, V, N, out, static_cast<hipStream_t>(stream));
+    if (e != hipSuccess) return hip_fail("view_rotations: launch", e);
+    return AHV_OK;
+}
+
+int ahv_fuse_view_scores_f32(const float* scores, const float* Q, int64_t q_batch_stride, const float* A, const float* weights,
+                             int B, int V, int64_t N, int64_t n_offset, float min_trace, float* fused, int64_t* best_key,
+                             unsigned flags, void* stream)
+{
+    if (int rc = views_sizes("fuse_view_scores", B, V, N)) return rc;
+    if (n_offset < 0 || n_offset + N > 4294967296ll)
+        return fail(AHV_EINVAL, "fuse_view_scores: n_offset + N must fit in 32 bits");
+    if (flags & ~(AHV_VIEWS_RESET_BEST | AHV_VIEWS_NO_ANGLE_LIMIT)) return fail(AHV_EINVAL, "fuse_view_scores: unknown flags 0x%x", flags);
+    const bool limit = !(flags & AHV_VIEWS_NO_ANGLE_LIMIT);
+    if (limit && !(min_trace > -1.0f && min_trace < 3.0f))   // false for a NaN
+        return fail(AHV_EINVAL, "fuse_view_scores: min_trace = %g outside (-1, 3) (1 + 2 cos theta, 0 < theta < 180 degrees; "
+                    "AHV_VIEWS_NO_ANGLE_LIMIT for none)", (double)min_trace);
+    if (q_batch_stride != 0 && q_batch_stride != N * 9)
+        return fail(AHV_EINVAL, "fuse_view_scores: q_batch_stride %lld must be 0 or N*9", (long long)q_batch_stride);
+    if (!scores || !best_key || (limit && (!Q || !A))) return fail(AHV_EINVAL, "fuse_view_scores: null pointer");
+    if (weights) {
+        bool any = false;
+        for (int v = 0; v < V; ++v) {
+            if (!(weights[v] >= 0.0f && weights[v] < __builtin_inff()))   // false for a NaN
+                return fail(AHV_EINVAL, "fuse_view_scores: weights[%d] = %g must be finite and >= 0", v, (double)weights[v]);
+            any = any || weights[v] > 0.0f;
+        }
+        if (!any) return fail(AHV_EINVAL, "fuse_view_scores: weights are all zero (no view would take part)");
+    }
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (flags & AHV_VIEWS_RESET_BEST) {
+        hipError_t e = ahv::launch_fill_keys(best_key, B, s);
+        if (e != hipSuccess) return hip_fail("fuse_view_scores: key reset", e);
+    }
+    hipError_t e = ahv::launch_fuse_views(scores, Q, q_batch_stride, A, weights, B, V, N, n_offset, min_trace, limit, fused,
+                                          best_key, s);
+    if (e != hipSuccess) return hip_fail("fuse_view_scores: launch", e);
     return AHV_OK;
 }
 

@@ -382,6 +382,114 @@ __global__ __launch_bounds__(kTopkThreads) void topk_modes_kernel(const float* _
 }
 
 // ---------------------------------------------------------------------------------
+// Multi-view verification (ahv_view_rotations_f32 / ahv_fuse_view_scores_f32): V posed reference views of one object, one
+// query whose rotation is wanted, N hypotheses Q_n of it.  View v (absolute rotation A_v) sees hypothesis n as the relative
+// rotation R_{v,n} = Q_n A_v^T (gt_src_2_tgt_R = R_tgt R_src^-1), the scorer gives s_{v,n}, and
+//     S_n = (sum_v g_{v,n} w_v s_{v,n}) / (sum_v g_{v,n} w_v),   g_{v,n} = [w_v > 0] [no limit or t(Q_n, A_v) >= tau],
+// summed over v = 0 .. V-1 in that order in fp32, the product rounded before the add; -inf when no view participates.  A view
+// with w_v = 0 is never read; a NaN t does not participate; a participating NaN score makes S_n NaN.
+//  - view_rotations_kernel: the composition, one thread per output matrix, laid out as the scorer's per-sample set of B V samples.
+//  - fuse_views_kernel: ONE pass over scores [B][V][N] (and Q, only under an angle limit) on the grid rule of the modes kernels
+//    (tiles of kTopkTile, four consecutive hypotheses per lane: load_scores4 / load_rotations4 -- a view's row starts at
+//    s + (b V + v) N, mid-vector when N % 4 != 0).  A[b][.] and the weights sit in LDS; the weights arrive BY VALUE in the kernel
+//    arguments, so a launch reads no host memory.  The packed key of S_n is reduced per workgroup (modes_publish: DPP inside a
+//    wave, LDS across the four, one atomicMax per workgroup and sample) into the caller's key.  No float atomics: for given
+//    inputs every sum is taken in one fixed order.
+// ---------------------------------------------------------------------------------
+constexpr int kViewsMax = 16;
+
+struct ViewWeights {
+    float w[kViewsMax];
+};
+
+__global__ __launch_bounds__(256) void view_rotations_kernel(const float* __restrict__ Q, long q_batch_stride,
+                                                             const float* __restrict__ A, int V, long N, long total,
+                                                             float* __restrict__ out)
+{
+    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;  // (b V + v) N + n
+    if (i >= total) return;
+    const long bv = i / N;
+    const long n = i - bv * N;
+    const long b = bv / V;
+    const float* q = Q + b * q_batch_stride + n * 9;
+    const float* d = A + bv * 9;  // A_v: column c of A_v^T is row c of A_v
+    float* o = out + i * 9;
+#pragma unroll
+    for (int a = 0; a < 3; ++a)
+#pragma unroll
+        for (int c = 0; c < 3; ++c) o[a * 3 + c] = q[a * 3] * d[c * 3] + q[a * 3 + 1] * d[c * 3 + 1] + q[a * 3 + 2] * d[c * 3 + 2];
+}
+
+__global__ __launch_bounds__(kTopkThreads) void fuse_views_kernel(const float* __restrict__ scores, const float* __restrict__ Q,
+                                                                  long q_batch_stride, const float* __restrict__ A,
+                                                                  const ViewWeights weights, int V, long N, long n_offset,
+                                                                  float tau, bool limit, float* __restrict__ fused,
+                                                                  key_t* __restrict__ best_key)
+{
+#pragma clang fp contract(off)  // w s is rounded before it is added: the definition's operation order
+    __shared__ key_t wl[kTopkThreads / 64];
+    __shared__ float Al[kViewsMax][9];
+    __shared__ float wv[kViewsMax];
+    const int tid = threadIdx.x, b = blockIdx.y;
+    if (limit && tid < V * 9) (&Al[0][0])[tid] = A[(long)b * V * 9 + tid];  // (Q and A are not read without a limit)
+    if (tid < V) wv[tid] = weights.w[tid];
+    __syncthreads();
+    const float* s = scores + (long)b * V * N;
+    const float* Qb = limit ? Q + (long)b * q_batch_stride : nullptr;
+    float* f = fused ? fused + (long)b * N : nullptr;
+    const long tiles = (N + kTopkTile - 1) / kTopkTile;
+    key_t best = kKeyEmpty;
+    for (long t = blockIdx.x; t < tiles; t += gridDim.x) {
+        const long n0 = t * kTopkTile + (long)tid * 4;
+        if (n0 >= N) continue;
+        float r[4][9];
+        if (limit) {
+            const bool every[4] = {true, true, true, true};
+            load_rotations4(Qb, n0, N, every, r);
+        }
+        float num[4] = {0.0f, 0.0f, 0.0f, 0.0f}, den[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+        for (int v = 0; v < V; ++v) {
+            const float w = wv[v];
+            if (!(w > 0.0f)) continue;  // an absent view: its scores are not read (uniform over the workgroup)
+            float sc[4];
+            load_scores4(s + (long)v * N, n0, N, 0.0f, sc);
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                bool g = true;
+                if (limit) {
+                    float acc = 0.0f;
+#pragma unroll
+                    for (int i = 0; i < 9; ++i) acc = fmaf(r[e][i], Al[v][i], acc);
+                    g = acc >= tau;  // false for a NaN t
+                }
+                const float p = w * sc[e];
+                num[e] = g ? num[e] + p : num[e];
+                den[e] = g ? den[e] + w : den[e];
+            }
+        }
+        float S[4];
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            S[e] = den[e] > 0.0f ? num[e] / den[e] : -INFINITY;
+            if (n0 + e < N) {
+                const key_t k = pack_key(S[e], (unsigned)(n_offset + n0 + e));
+                best = k > best ? k : best;
+            }
+        }
+        if (f) {
+            if (n0 + 3 < N && aligned16(f + n0)) {
+                *reinterpret_cast<float4*>(f + n0) = make_float4(S[0], S[1], S[2], S[3]);
+            } else {
+#pragma unroll
+                for (int e = 0; e < 4; ++e)
+                    if (n0 + e < N) f[n0 + e] = S[e];
+            }
+        }
+    }
+    modes_publish(best, wl, best_key + b);
+}
+
+// ---------------------------------------------------------------------------------
 // Pose posterior (ahv_pose_posterior_f32 / _merge / _finish_f32): softmax statistics of the scored set at inverse temperature
 // beta, split over K anchor buckets (hypothesis i belongs to the FIRST anchor k with t(i, k) >= tau, else to the rest).  What is
 // kept per bucket and for the whole set is a RECORD of kPostRec doubles -- m (the largest score met, -inf when empty), and
@@ -923,6 +1031,30 @@ hipError_t launch_topk_modes(const float* scores, const float* R, int64_t r_batc
         hipLaunchKernelGGL(topk_modes_kernel<false>, grid, dim3(kTopkThreads), 0, stream, scores, R, (long)r_batch_stride,
                            (long)N, Ns, (long)n_offset, K, j, tau, reinterpret_cast<key_t*>(state),
                            reinterpret_cast<key_t*>(keys));
+    return hipGetLastError();
+}
+
+// ---- multi-view verification --------------------------------------------------------------------------------
+hipError_t launch_view_rotations(const float* Q, int64_t q_batch_stride, const float* A, int B, int V, int64_t N, float* out,
+                                 hipStream_t stream)
+{
+    const long total = (long)B * V * N;
+    hipLaunchKernelGGL(view_rotations_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, Q,
+                       (long)q_batch_stride, A, V, (long)N, total, out);
+    return hipGetLastError();
+}
+
+// weights: V floats on the HOST, copied into the kernel arguments here (the launch itself reads no host memory)
+hipError_t launch_fuse_views(const float* scores, const float* Q, int64_t q_batch_stride, const float* A, const float* weights,
+                             int B, int V, int64_t N, int64_t n_offset, float tau, bool limit, float* fused, int64_t* best_key,
+                             hipStream_t stream)
+{
+    ViewWeights w;
+    for (int v = 0; v < kViewsMax; ++v) w.w[v] = v < V ? (weights ? weights[v] : 1.0f) : 0.0f;
+    const int64_t tiles = (N + kTopkTile - 1) / kTopkTile;
+    const dim3 grid((unsigned)(tiles < 1024 ? tiles : 1024), (unsigned)B);
+    hipLaunchKernelGGL(fuse_views_kernel, grid, dim3(kTopkThreads), 0, stream, scores, Q, (long)q_batch_stride, A, w, V, (long)N,
+                       (long)n_offset, tau, limit, fused, reinterpret_cast<key_t*>(best_key));
     return hipGetLastError();
 }
 

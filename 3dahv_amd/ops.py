@@ -915,6 +915,132 @@ def verify_pair_posterior(vol_src: torch.Tensor, vol_tgt: torch.Tensor, R: torch
     return m_s, m_i, m_R, pose_posterior(scores, R, temperature, anchors=m_R, min_angle_deg=min_angle_deg)
 
 
+# ---- multi-view verification ---------------------------------------------------------------------------------------
+# V posed reference views of one object (absolute rotations A_v), one query whose absolute rotation is wanted, N hypotheses Q_n
+# of it: view v sees hypothesis n as R_{v,n} = Q_n A_v^T (gt_src_2_tgt_R = R_tgt R_src^-1), and the per-view scores are fused
+# into ONE (B,N) row -- S_n, the weighted mean over the participating views -- and one packed key (``ahv_fuse_view_scores_f32``,
+# include/ahv.h).
+
+def _view_poses(A: torch.Tensor, Q: torch.Tensor):
+    """``(B, V, N, q_batch_stride)`` of reference poses ``A (B,V,3,3)`` and hypotheses ``Q (N,3,3)`` / ``(B,N,3,3)``."""
+    if A.dim() != 4 or tuple(A.shape[2:]) != (3, 3):
+        raise RuntimeError("A must be (B,V,3,3), got %s" % (tuple(A.shape),))
+    B, V = A.shape[:2]
+    if not 1 <= V <= _lib.AHV_VIEWS_MAX:
+        raise RuntimeError("V = %d outside 1..%d" % (V, _lib.AHV_VIEWS_MAX))
+    if Q.dim() == 3 and tuple(Q.shape[1:]) == (3, 3):
+        return B, V, Q.shape[0], 0
+    if Q.dim() == 4 and Q.shape[0] == B and tuple(Q.shape[2:]) == (3, 3):
+        return B, V, Q.shape[1], Q.shape[1] * 9
+    raise RuntimeError("Q must be (N,3,3) or (B,N,3,3) with B = %d, got %s" % (B, tuple(Q.shape)))
+
+
+def _view_weights(weights, V: int):
+    """The per-view weights as V host floats (they travel in the kernel's arguments), or None for all ones."""
+    if weights is None:
+        return None
+    if isinstance(weights, torch.Tensor):
+        if weights.is_cuda:
+            raise RuntimeError("weights are host values (a sequence or a CPU tensor of V floats): they are passed in the kernel's "
+                               "arguments, and reading them from the GPU would synchronise")
+        weights = weights.detach().reshape(-1).tolist()
+    w = [float(x) for x in weights]
+    if len(w) != V:
+        raise RuntimeError("weights must hold V = %d values, got %d" % (V, len(w)))
+    import ctypes
+    return (ctypes.c_float * V)(*w)
+
+
+def view_rotations(Q: torch.Tensor, A: torch.Tensor, out: torch.Tensor | None = None) -> torch.Tensor:
+    """``out[b, v, n] = Q[n] @ A[b, v].T`` -> (B,V,N,3,3) (``ahv_view_rotations_f32``): hypothesis n of the query's rotation as
+    the relative rotation reference view v would see.  Q (N,3,3) shared by the batch or (B,N,3,3); A (B,V,3,3).  Reshaped to
+    (B*V,N,3,3) it is the per-sample rotation set of ``score_hypotheses`` for the B*V (view, query) samples."""
+    _refuse_grad("view_rotations", Q, A)
+    B, V, N, qstride = _view_poses(A, Q)
+    dev = _need_gpu(Q, A)
+    Qc, Ac = Q.detach().contiguous(), A.detach().contiguous()
+    if out is None:
+        out = torch.empty((B, V, N, 3, 3), dtype=torch.float32, device=dev)
+    elif tuple(out.shape) != (B, V, N, 3, 3) or not out.is_contiguous() or out.device != dev or out.dtype != torch.float32:
+        raise RuntimeError("out must be a contiguous float32 (B,V,N,3,3) tensor on %s" % dev)
+    _call(dev, "ahv_view_rotations_f32", Qc.data_ptr(), qstride, Ac.data_ptr(), B, V, N, out.data_ptr())
+    return out
+
+
+def fuse_view_scores(scores: torch.Tensor, Q: torch.Tensor, A: torch.Tensor, weights=None, max_view_angle_deg: float | None = None,
+                     n_offset: int = 0, want_scores: bool = True, best_key: torch.Tensor | None = None,
+                     reset_best: bool | None = None):
+    """Per-view scores ``(B,V,N)`` -> ``(fused (B,N) or None, best_key (B,) int64)`` in ONE launch (``ahv_fuse_view_scores_f32``):
+    ``S_n = sum_v g w_v s_{v,n} / sum_v g w_v`` over the participating views, in the order v = 0 .. V-1 in fp32; -inf where no
+    view participates.  ``weights``: V host floats (finite, >= 0, not all zero; None = ones); a view with weight 0 is absent
+    and its scores are never read.  ``max_view_angle_deg``: view v takes part in hypothesis n only where the relative rotation
+    ``Q[n] @ A[b, v].T`` is within that angle (``min_trace``'s rule; a NaN trace does not take part); None = no limit, and Q
+    and A are then only checked for their shapes.  ``best_key`` given: the packed key of ``(S_n, n_offset + n)`` is merged into it
+    (chunked N, shards) unless ``reset_best``; else a fresh key is returned.  Decode with ``select_rotation(key, Q)``.
+    The fused row is an ordinary (B,N) score row with ``Q`` as its matrices: ``topk``, ``topk_modes`` and ``pose_posterior``
+    take it unchanged, and as a weighted mean of cosine similarities it stays in [-1, 1], so a temperature means what it means
+    for one pair.  Inference only."""
+    _refuse_grad("fuse_view_scores", scores, Q, A)
+    B, V, N, qstride = _view_poses(A, Q)
+    if scores.dim() != 3 or tuple(scores.shape) != (B, V, N):
+        raise RuntimeError("scores must be (B,V,N) = %s, got %s" % ((B, V, N), tuple(scores.shape)))
+    w = _view_weights(weights, V)
+    flags = 0
+    if max_view_angle_deg is None:
+        flags |= _lib.AHV_VIEWS_NO_ANGLE_LIMIT
+        tau = 0.0
+    else:
+        tau = min_trace(max_view_angle_deg)
+    dev = _need_gpu(scores, Q, A)
+    if best_key is None:
+        best_key = torch.empty((B,), dtype=torch.int64, device=dev)
+        reset_best = True
+    elif best_key.dtype != torch.int64 or best_key.numel() != B or best_key.device != dev or not best_key.is_contiguous():
+        raise RuntimeError("best_key must be a contiguous int64 tensor of B = %d elements on %s" % (B, dev))
+    if reset_best:
+        flags |= _lib.AHV_VIEWS_RESET_BEST
+    s, Qc, Ac = scores.detach().contiguous(), Q.detach().contiguous(), A.detach().contiguous()
+    fused = torch.empty((B, N), dtype=torch.float32, device=dev) if want_scores else None
+    _call(dev, "ahv_fuse_view_scores_f32", s.data_ptr(), Qc.data_ptr(), qstride, Ac.data_ptr(), w, B, V, N, n_offset, tau,
+          fused.data_ptr() if want_scores else None, best_key.data_ptr(), flags)
+    return fused, best_key
+
+
+def verify_views(vol_refs: torch.Tensor, vol_query: torch.Tensor, Q: torch.Tensor, A: torch.Tensor, W1: torch.Tensor,
+                 W2: torch.Tensor, b2: torch.Tensor, weights=None, max_view_angle_deg: float | None = None, n_offset: int = 0,
+                 want_scores: bool = True, best_key: torch.Tensor | None = None, reset_best: bool | None = None,
+                 split_f16: bool | None = None, want_view_scores: bool = False):
+    """The verify step against V posed reference views: ``vol_refs (B,V,16,8,8,8)`` with absolute rotations ``A (B,V,3,3)``,
+    the query volume ``vol_query (B,16,8,8,8)``, hypotheses ``Q (N,3,3)`` / ``(B,N,3,3)`` of the QUERY's absolute rotation.
+    ``view_rotations`` -> ONE scoring launch over the B*V (view, query) samples -> ``fuse_view_scores``.  Returns ``(fused (B,N)
+    or None, best_key (B,))`` and, with ``want_view_scores``, the per-view scores ``(B,V,N)`` as third element; keywords as
+    ``fuse_view_scores``, ``split_f16`` as ``score_hypotheses``.  ``select_rotation(best_key, Q)`` decodes the pose, and the fused
+    row goes to ``topk`` / ``topk_modes`` / ``pose_posterior`` with ``Q`` unchanged.
+    The scoring launch is ``verify_pair``'s (the query's features are built inside it, per sample, from the query volume repeated
+    per view), so at V = 1 and A = I the fused row is ``verify_pair``'s score row bit for bit.  Inference only."""
+    _refuse_grad("verify_views", vol_refs, vol_query, Q, A, W1, W2, b2)
+    B, V, N, _ = _view_poses(A, Q)
+    if vol_refs.dim() != 6 or tuple(vol_refs.shape) != (B, V) + _VOL:
+        raise RuntimeError("vol_refs must be (B,V,16,8,8,8) = %s, got %s" % ((B, V) + _VOL, tuple(vol_refs.shape)))
+    if tuple(vol_query.shape) != (B,) + _VOL:
+        raise RuntimeError("vol_query must be (B,16,8,8,8) with B = %d, got %s" % (B, tuple(vol_query.shape)))
+    _view_weights(weights, V)  # (weights and angle are checked before the first launch)
+    if max_view_angle_deg is not None:
+        min_trace(max_view_angle_deg)
+    dev = _need_gpu(vol_refs, vol_query, Q, A, W1, W2, b2)
+    split = bool(_SPLIT_F16.get() if split_f16 is None else split_f16)
+    with torch.no_grad():
+        Rv = view_rotations(Q, A).reshape(B * V, N, 3, 3)
+        vq = vol_query.detach()[:, None].expand((B, V) + _VOL).reshape((B * V,) + _VOL)
+        feat = torch.empty((B * V, 32, 64), dtype=torch.float32, device=dev) if split else None
+        view_scores, _ = _score_hypotheses_nograd(vol_refs.detach().reshape((B * V,) + _VOL), vq, Rv, W1, W2, b2, 0, True, None,
+                                                  None, split, None, tgt_is_volume=True, feat_tgt_out=feat)
+        view_scores = view_scores.reshape(B, V, N)
+        fused, key = fuse_view_scores(view_scores, Q, A, weights, max_view_angle_deg, n_offset, want_scores, best_key,
+                                      reset_best)
+    return (fused, key, view_scores) if want_view_scores else (fused, key)
+
+
 # ---- rotation gradient of the score, gradient-based pose polishing ------------------------------------------
 
 @torch.no_grad()

@@ -332,6 +332,48 @@ def gen_rotation_grad(rotate_volume, fa, vol_src, vol_tgt):
     np.savez(os.path.join(OUT, "rotation_grad.npz"), R=R, names=names, **out)
 
 
+def gen_multiview(rotate_volume, fa, vol_src3):
+    """G13 `multiview`: B = 2 queries x V = 3 posed reference views x N = 40 hypotheses of the query's absolute rotation.
+    `utils.rotate_volume` (utils.py:113-131) and `Feature_Aligner.forward_3d2d` (modules/modules.py:112-124) execute as
+    shipped.  Object b is volume b of the seeded pairs; reference view v of it is `rotate_volume(object, A_v)`, the query
+    `rotate_volume(object, Q_true)` -- so that, with the reference's convention gt_src_2_tgt_R = R_tgt R_src^-1, view v sees
+    the query under hypothesis n as R_{v,n} = Q_n A_v^T (formed here in torch).  The per-view similarities are the script line
+    test_co3d.py:143; the fused score is their mean over the views and the answer torch.max of it.  Q is shared by the two
+    queries and holds Q_true of query b at index PLANT[b]; the winner must be that index with a lead of at least 1e-3."""
+    B, V, N, PLANT = 2, 3, 40, (7, 29)
+    A = np.stack([np.stack([axis_rot("z", 25.0), axis_rot("x", -30.0) @ axis_rot("y", 20.0), axis_rot("y", 35.0) @ axis_rot("z", -15.0)]),
+                  np.stack([axis_rot("x", 30.0), axis_rot("z", 40.0) @ axis_rot("x", -10.0), axis_rot("y", -25.0)])]).astype(np.float32)
+    Q = rot.haar_rotations_np(N, seed=13).astype(np.float32)
+    Q_true = np.stack([axis_rot("y", 15.0) @ axis_rot("x", 10.0), axis_rot("z", -20.0) @ axis_rot("y", 12.0)]).astype(np.float32)
+    for b in range(B):
+        Q[PLANT[b]] = Q_true[b]
+    W1, W2, b2 = head_weights(fa)
+    with torch.no_grad():
+        obj = vol_src3[:B]
+        At, Qt = torch.from_numpy(A), torch.from_numpy(Q)
+        vol_refs = torch.stack([rotate_volume(obj[b:b + 1].expand(V, -1, -1, -1, -1), At[b]) for b in range(B)])
+        vol_query = rotate_volume(obj, torch.from_numpy(Q_true))
+        R = torch.matmul(Qt[None, None], At.transpose(-1, -2)[:, :, None])        # (B,V,N,3,3): Q_n A_v^T
+        f_tgt = fa.forward_3d2d(vol_query)
+        sims = []
+        for b in range(B):
+            for v in range(V):
+                warped = rotate_volume(vol_refs[b, v][None].expand(N, -1, -1, -1, -1), R[b, v])
+                f = fa.forward_3d2d(warped).reshape(1, N, -1, 64)
+                sims.append((f * f_tgt[b:b + 1, None]).sum(dim=2).mean(dim=-1)[0])
+        scores = torch.stack(sims).reshape(B, V, N)
+        fused = scores.mean(dim=1)
+        best, idx = torch.max(fused, dim=1)
+    top2 = torch.topk(fused, 2, dim=1).values
+    margin = (top2[:, 0] - top2[:, 1]).numpy()
+    print("G13 multiview: best", best.tolist(), "idx", idx.tolist(), "margin", margin.tolist(),
+          "per-view arg-max", scores.argmax(dim=2).tolist())
+    assert idx.tolist() == list(PLANT) and margin.min() >= 1e-3, (idx.tolist(), margin)
+    np.savez(os.path.join(OUT, "multiview.npz"), vol_refs=vol_refs.numpy(), vol_query=vol_query.numpy(), A=A, Q=Q, W1=W1, W2=W2,
+             b2=b2, R=R.numpy(), scores=scores.numpy(), fused=fused.numpy(), best=best.numpy(), best_idx=idx.numpy(),
+             plant=np.array(PLANT, dtype=np.int64), margin=margin)
+
+
 def main():
     os.makedirs(OUT, exist_ok=True)
     torch.set_num_threads(8)
@@ -345,6 +387,9 @@ def main():
     fa, vol_src3, vol_tgt3 = seeded_pair(Feature_Aligner)
     W1, W2, b2 = head_weights(fa)
     vol_src, vol_tgt = vol_src3[:1], vol_tgt3[:1]
+    if "--only-g13" in sys.argv:    # the multi-view fixture alone
+        gen_multiview(rotate_volume, fa, vol_src3)
+        return
     if "--only-g12" in sys.argv:    # the rotation gradient alone (needs score_n128.npz and edge_rotations.npz in place)
         gen_rotation_grad(rotate_volume, fa, vol_src, vol_tgt)
         return
@@ -457,6 +502,7 @@ def main():
     gen_nonfinite(rotate_volume, fa, vol_src, vol_tgt)
     gen_infonce(rotate_volume, fa, vol_src3, vol_tgt3)
     gen_rotation_grad(rotate_volume, fa, vol_src, vol_tgt)
+    gen_multiview(rotate_volume, fa, vol_src3)
     gen_encoder_full(Feature_Aligner)
 
     total = sum(os.path.getsize(os.path.join(OUT, f)) for f in os.listdir(OUT))
