@@ -28,6 +28,8 @@ AHV_POSTERIOR_RESET_STATE = 1
 AHV_VIEWS_MAX = 16
 AHV_VIEWS_RESET_BEST = 1
 AHV_VIEWS_NO_ANGLE_LIMIT = 2
+AHV_VIEW_SLOT_EXCLUDED = -1
+AHV_VIEW_SLOT_OVERFLOW = -2
 
 _vp = ctypes.c_void_p
 _i64 = ctypes.c_int64
@@ -104,6 +106,12 @@ SIGNATURES["ahv_view_rotations_f32"] = (_int, [_vp, _i64, _vp, _int, _int, _i64,
 # (scores, Q, q_batch_stride, A, weights: HOST floats, B, V, N, n_offset, min_trace, fused, best_key, flags, stream)
 SIGNATURES["ahv_fuse_view_scores_f32"] = (_int, [_vp, _vp, _i64, _vp, _vp, _int, _int, _i64, _i64, ctypes.c_float, _vp, _vp, _u32,
                                                  _vp])
+SIGNATURES["ahv_view_rotations_compact_workspace_bytes"] = (ctypes.c_size_t, [_int, _int, _i64])
+# (Q, q_batch_stride, A, weights: HOST floats, B, V, N, min_trace, capacity, out, slot, counts, workspace, workspace_bytes, stream)
+SIGNATURES["ahv_view_rotations_compact_f32"] = (_int, [_vp, _i64, _vp, _vp, _int, _int, _i64, ctypes.c_float, _i64, _vp, _vp, _vp,
+                                                       _vp, ctypes.c_size_t, _vp])
+# (scores, slot, weights: HOST floats, B, V, N, capacity, n_offset, fused, best_key, flags, stream)
+SIGNATURES["ahv_fuse_view_scores_compact_f32"] = (_int, [_vp, _vp, _vp, _int, _int, _i64, _i64, _i64, _vp, _vp, _u32, _vp])
 
 # measurement / developer entry points (include/ahv_diag.h): not part of the drop-in boundary
 DIAG_SIGNATURES = {

@@ -561,8 +561,10 @@ class Feature_Aligner(nn.Module):
         """The verify step against V posed reference views with this module's head weights (``ops.verify_views``):
         ``vol_refs (B,V,16,8,8,8)`` with absolute rotations ``view_poses (B,V,3,3)``, the query volume ``(B,16,8,8,8)`` and
         ``hypotheses`` of the query's absolute rotation -> ``(fused scores (B,N) | None, packed keys)``;
-        ``ops.select_rotation(keys, hypotheses)`` decodes the pose.  An inference call by the rule of ``verify_hypotheses``
-        (no_grad, or eval mode); a module in training mode with autograd recording is refused."""
+        ``ops.select_rotation(keys, hypotheses)`` decodes the pose.  Keywords go to ``ops.verify_views``: with
+        ``max_view_angle_deg``, ``compact=True`` (and ``capacity`` / ``want_counts``) scores only the pairs the limit lets take
+        part, to the same bits.  An inference call by the rule of ``verify_hypotheses`` (no_grad, or eval mode); a module in
+        training mode with autograd recording is refused."""
         from .patch import _inference_call
         if not _inference_call(self):
             raise RuntimeError("verify_views is the inference step (no autograd edge); the module is in training mode with "

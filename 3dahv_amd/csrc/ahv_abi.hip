@@ -34,6 +34,11 @@ hipError_t launch_topk_modes(const float*, const float*, int64_t, int, int64_t, 
 hipError_t launch_view_rotations(const float*, int64_t, const float*, int, int, int64_t, float*, hipStream_t);
 hipError_t launch_fuse_views(const float*, const float*, int64_t, const float*, const float*, int, int, int64_t, int64_t, float,
                              bool, float*, int64_t*, hipStream_t);
+int64_t view_compact_tiles(int64_t N);
+hipError_t launch_view_rotations_compact(const float*, int64_t, const float*, const float*, int, int, int64_t, float, int64_t,
+                                         float*, int32_t*, int64_t*, void*, hipStream_t);
+hipError_t launch_fuse_views_compact(const float*, const int32_t*, const float*, int, int, int64_t, int64_t, int64_t, float*,
+                                     int64_t*, hipStream_t);
 size_t posterior_state_stride(int K);
 int posterior_parts(int64_t N);
 hipError_t launch_posterior(const float*, const float*, int64_t, int, int64_t, const float*, int, float, float, void*, void*, bool,
@@ -675,6 +680,30 @@ static int views_sizes(const char* who, int B, int V, int64_t N)
     return AHV_OK;
 }
 
+// weights: V HOST floats or NULL (all ones)
+static int views_weights(const char* who, const float* weights, int V)
+{
+    if (!weights) return AHV_OK;
+    bool any = false;
+    for (int v = 0; v < V; ++v) {
+        if (!(weights[v] >= 0.0f && weights[v] < __builtin_inff()))   // false for a NaN
+            return fail(AHV_EINVAL, "%s: weights[%d] = %g must be finite and >= 0", who, v, (double)weights[v]);
+        any = any || weights[v] > 0.0f;
+    }
+    if (!any) return fail(AHV_EINVAL, "%s: weights are all zero (no view would take part)", who);
+    return AHV_OK;
+}
+
+// the compact entries: the slot map is int32 and a list holds at most the whole set
+static int views_compact_sizes(const char* who, int B, int V, int64_t N, int64_t capacity)
+{
+    if (int rc = views_sizes(who, B, V, N)) return rc;
+    if (N >= (int64_t)1 << 31) return fail(AHV_EINVAL, "%s: N = %lld must be below 2^31 (the slot map is int32)", who, (long long)N);
+    if (capacity < 1 || capacity > N)
+        return fail(AHV_EINVAL, "%s: capacity = %lld outside 1..N = %lld", who, (long long)capacity, (long long)N);
+    return AHV_OK;
+}
+
 int ahv_view_rotations_f32(const float* Q, int64_t q_batch_stride, const float* A, int B, int V, int64_t N, float* out,
                            void* stream)
 {
@@ -705,15 +734,7 @@ int ahv_fuse_view_scores_f32(const float* scores, const float* Q, int64_t q_batc
     if (q_batch_stride != 0 && q_batch_stride != N * 9)
         return fail(AHV_EINVAL, "fuse_view_scores: q_batch_stride %lld must be 0 or N*9", (long long)q_batch_stride);
     if (!scores || !best_key || (limit && (!Q || !A))) return fail(AHV_EINVAL, "fuse_view_scores: null pointer");
-    if (weights) {
-        bool any = false;
-        for (int v = 0; v < V; ++v) {
-            if (!(weights[v] >= 0.0f && weights[v] < __builtin_inff()))   // false for a NaN
-                return fail(AHV_EINVAL, "fuse_view_scores: weights[%d] = %g must be finite and >= 0", v, (double)weights[v]);
-            any = any || weights[v] > 0.0f;
-        }
-        if (!any) return fail(AHV_EINVAL, "fuse_view_scores: weights are all zero (no view would take part)");
-    }
+    if (int rc = views_weights("fuse_view_scores", weights, V)) return rc;
     hipStream_t s = static_cast<hipStream_t>(stream);
     if (flags & AHV_VIEWS_RESET_BEST) {
         hipError_t e = ahv::launch_fill_keys(best_key, B, s);
@@ -722,6 +743,56 @@ int ahv_fuse_view_scores_f32(const float* scores, const float* Q, int64_t q_batc
     hipError_t e = ahv::launch_fuse_views(scores, Q, q_batch_stride, A, weights, B, V, N, n_offset, min_trace, limit, fused,
                                           best_key, s);
     if (e != hipSuccess) return hip_fail("fuse_view_scores: launch", e);
+    return AHV_OK;
+}
+
+size_t ahv_view_rotations_compact_workspace_bytes(int B, int V, int64_t N)
+{
+    if (B <= 0 || V < 1 || V > AHV_VIEWS_MAX || N <= 0) return 0;
+    return sizeof(int32_t) * (size_t)B * (size_t)V * (size_t)ahv::view_compact_tiles(N);   // one count per (b, v, tile)
+}
+
+int ahv_view_rotations_compact_f32(const float* Q, int64_t q_batch_stride, const float* A, const float* weights, int B, int V,
+                                   int64_t N, float min_trace, int64_t capacity, float* out, int32_t* slot, int64_t* counts,
+                                   void* workspace, size_t workspace_bytes, void* stream)
+{
+    if (int rc = views_compact_sizes("view_rotations_compact", B, V, N, capacity)) return rc;
+    if (!(min_trace > -1.0f && min_trace < 3.0f))   // false for a NaN
+        return fail(AHV_EINVAL, "view_rotations_compact: min_trace = %g outside (-1, 3) (1 + 2 cos theta, 0 < theta < 180 degrees)",
+                    (double)min_trace);
+    if (q_batch_stride != 0 && q_batch_stride != N * 9)
+        return fail(AHV_EINVAL, "view_rotations_compact: q_batch_stride %lld must be 0 or N*9", (long long)q_batch_stride);
+    if (!Q || !A || !counts) return fail(AHV_EINVAL, "view_rotations_compact: null pointer");
+    if (!out != !slot)
+        return fail(AHV_EINVAL, "view_rotations_compact: out and slot must both be given, or both be NULL (count only)");
+    if (int rc = views_weights("view_rotations_compact", weights, V)) return rc;
+    const size_t need = ahv_view_rotations_compact_workspace_bytes(B, V, N);
+    if (!workspace || workspace_bytes < need || (reinterpret_cast<uintptr_t>(workspace) & 3))
+        return fail(AHV_EINVAL, "view_rotations_compact: needs a 4-byte aligned workspace of %zu bytes "
+                    "(ahv_view_rotations_compact_workspace_bytes), got %zu", need, workspace_bytes);
+    hipError_t e = ahv::launch_view_rotations_compact(Q, q_batch_stride, A, weights, B, V, N, min_trace, capacity, out, slot, counts,
+                                                      workspace, static_cast<hipStream_t>(stream));
+    if (e != hipSuccess) return hip_fail("view_rotations_compact: launch", e);
+    return AHV_OK;
+}
+
+int ahv_fuse_view_scores_compact_f32(const float* scores, const int32_t* slot, const float* weights, int B, int V, int64_t N,
+                                     int64_t capacity, int64_t n_offset, float* fused, int64_t* best_key, unsigned flags,
+                                     void* stream)
+{
+    if (int rc = views_compact_sizes("fuse_view_scores_compact", B, V, N, capacity)) return rc;
+    if (n_offset < 0 || n_offset + N > 4294967296ll)
+        return fail(AHV_EINVAL, "fuse_view_scores_compact: n_offset + N must fit in 32 bits");
+    if (flags & ~AHV_VIEWS_RESET_BEST) return fail(AHV_EINVAL, "fuse_view_scores_compact: unknown flags 0x%x", flags);
+    if (!scores || !slot || !best_key) return fail(AHV_EINVAL, "fuse_view_scores_compact: null pointer");
+    if (int rc = views_weights("fuse_view_scores_compact", weights, V)) return rc;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (flags & AHV_VIEWS_RESET_BEST) {
+        hipError_t e = ahv::launch_fill_keys(best_key, B, s);
+        if (e != hipSuccess) return hip_fail("fuse_view_scores_compact: key reset", e);
+    }
+    hipError_t e = ahv::launch_fuse_views_compact(scores, slot, weights, B, V, N, capacity, n_offset, fused, best_key, s);
+    if (e != hipSuccess) return hip_fail("fuse_view_scores_compact: launch", e);
     return AHV_OK;
 }
 

@@ -402,6 +402,35 @@ struct ViewWeights {
     float w[kViewsMax];
 };
 
+// o = Q_n A_v^T with the bits of view_rotations_kernel (q = Q_n, d = A_v: entry (a, c) is row a of Q_n times row c of A_v).
+// That kernel states the entry as p0 + p1 + p2 and leaves the contraction to the compiler, which -- vectorising the nine entries
+// in pairs -- does not contract them alike: the last product is always fused, fma(q2, d2, .), onto fma(q0, d0, rn(p1)) in
+// columns 0 and 2, onto fma(q1, d1, rn(p0)) in column 1, and entry (2, 2) is fma(q2, d2, rn(rn(p0) + rn(p1))).  The same
+// expression at a second site is contracted differently again (it was tried: 1 ulp apart in entry (0, 1)), so this site spells
+// the dense kernel's operations out; the dense kernel stays as it is, and tests/test_gpu_views_compact.py compares the two bit
+// for bit on every shape, which is what notices a compiler that changes its mind.
+__device__ __forceinline__ void view_compose_pinned(const float (&q)[9], const float* d, float* o)
+{
+#pragma clang fp contract(off)
+#pragma unroll
+    for (int a = 0; a < 3; ++a)
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            const float p0 = q[a * 3] * d[c * 3], p1 = q[a * 3 + 1] * d[c * 3 + 1];
+            const float inner = (a == 2 && c == 2) ? p0 + p1 : c == 1 ? fmaf(q[a * 3 + 1], d[c * 3 + 1], p0) : fmaf(q[a * 3], d[c * 3], p1);
+            o[a * 3 + c] = fmaf(q[a * 3 + 2], d[c * 3 + 2], inner);
+        }
+}
+
+// t(Q_n, A_v) = sum_ab Q_n[a][b] A_v[a][b]: ONE fp32 fmaf chain in one order for every kernel that decides participation
+__device__ __forceinline__ float view_trace(const float (&q)[9], const float* a)
+{
+    float acc = 0.0f;
+#pragma unroll
+    for (int i = 0; i < 9; ++i) acc = fmaf(q[i], a[i], acc);
+    return acc;
+}
+
 __global__ __launch_bounds__(256) void view_rotations_kernel(const float* __restrict__ Q, long q_batch_stride,
                                                              const float* __restrict__ A, int V, long N, long total,
                                                              float* __restrict__ out)
@@ -456,13 +485,209 @@ __global__ __launch_bounds__(kTopkThreads) void fuse_views_kernel(const float* _
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
                 bool g = true;
-                if (limit) {
-                    float acc = 0.0f;
-#pragma unroll
-                    for (int i = 0; i < 9; ++i) acc = fmaf(r[e][i], Al[v][i], acc);
-                    g = acc >= tau;  // false for a NaN t
-                }
+                if (limit) g = view_trace(r[e], Al[v]) >= tau;  // false for a NaN t
                 const float p = w * sc[e];
+                num[e] = g ? num[e] + p : num[e];
+                den[e] = g ? den[e] + w : den[e];
+            }
+        }
+        float S[4];
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            S[e] = den[e] > 0.0f ? num[e] / den[e] : -INFINITY;
+            if (n0 + e < N) {
+                const key_t k = pack_key(S[e], (unsigned)(n_offset + n0 + e));
+                best = k > best ? k : best;
+            }
+        }
+        if (f) {
+            if (n0 + 3 < N && aligned16(f + n0)) {
+                *reinterpret_cast<float4*>(f + n0) = make_float4(S[0], S[1], S[2], S[3]);
+            } else {
+#pragma unroll
+                for (int e = 0; e < 4; ++e)
+                    if (n0 + e < N) f[n0 + e] = S[e];
+            }
+        }
+    }
+    modes_publish(best, wl, best_key + b);
+}
+
+// ---------------------------------------------------------------------------------
+// Angle-limited multi-view verification, compact (ahv_view_rotations_compact_f32 / ahv_fuse_view_scores_compact_f32): under an
+// angle limit only the pairs with g_{v,n} = [w_v > 0] [t(Q_n, A_v) >= tau] are composed and scored.  Per (b, v) the
+// participating hypotheses are numbered in increasing n (a stable compaction): slot[b][v][n] = that number m while m < capacity,
+// kViewSlotOverflow past it, kViewSlotExcluded for a pair that does not take part; out[b][v][m] = Q_n A_v^T, the identity in
+// every slot past the list's end, so that out is the scorer's per-sample set of B V samples at N = capacity.
+//  - view_compact_kernel<false>: workgroup (t, b) serves ALL V views of tile t (Q is read once): one count per (b, v, tile) to
+//    the workspace.
+//  - view_compact_kernel<true>: the same decision again (view_trace: the same bits), then the hand-over of the counts ACROSS
+//    THE KERNEL BOUNDARY: a wave sums its views' tile counts -- those ahead of tile t and all of them (tiles integers per
+//    view: 49 at N = 50 000; the sum is taken per workgroup, so the step costs tiles^2 loads per view and is meant for the N of
+//    a verify step, not for 10^8).  Inside the tile a lane's rank is the ballot of the lanes below it, the popcount, and the
+//    four wave totals in LDS.  The slot map, the composed matrices (view_compose_pinned), counts (tile 0) and the identity padding (workgroup t pads
+//    the slots of ITS index range) follow.  With out = slot = NULL one workgroup per sample only sums: counts alone.
+//  - fuse_views_compact_kernel: fuse_views_kernel with an int32 slot load and a gathered score load in place of the trace
+//    test -- the same products, adds and division in the same order, hence the same bits for the same scores.  A slot outside
+//    0 .. capacity-1 does not take part (no read behind the score row for a slot map that is not a compaction's).
+// ---------------------------------------------------------------------------------
+constexpr int kViewSlotExcluded = -1;
+constexpr int kViewSlotOverflow = -2;
+
+int64_t view_compact_tiles(int64_t N) { return (N + kTopkTile - 1) / kTopkTile; }
+
+// sl[e] = slot[n0 + e], fill where hypothesis n0 + e does not exist (load_scores4's rules)
+__device__ __forceinline__ void load_slots4(const int* __restrict__ s, long n0, long N, int fill, int (&sl)[4])
+{
+    if (n0 + 3 < N && aligned16(s + n0)) {
+        const int4 q = *reinterpret_cast<const int4*>(s + n0);
+        sl[0] = q.x; sl[1] = q.y; sl[2] = q.z; sl[3] = q.w;
+    } else {
+#pragma unroll
+        for (int e = 0; e < 4; ++e) sl[e] = n0 + e < N ? s[n0 + e] : fill;
+    }
+}
+
+__device__ __forceinline__ int wave_sum_int(int x)
+{
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) x += __shfl_xor(x, off, 64);
+    return x;
+}
+
+// grid (tiles, B): one workgroup per tile and sample.  kEmit with out == nullptr: grid (1, B), counts only.
+template <bool kEmit>
+__global__ __launch_bounds__(kTopkThreads) void view_compact_kernel(const float* __restrict__ Q, long q_batch_stride,
+                                                                    const float* __restrict__ A, const ViewWeights weights,
+                                                                    int V, long N, long tiles, float tau, long capacity,
+                                                                    int* __restrict__ tile_counts, float* __restrict__ out,
+                                                                    int* __restrict__ slot, long long* __restrict__ counts)
+{
+    __shared__ float Al[kViewsMax][9];
+    __shared__ float wv[kViewsMax];
+    __shared__ int wt[kViewsMax][kTopkThreads / 64];  // participating pairs of view v in wave w of this tile
+    __shared__ int ahead[kViewsMax], all[kViewsMax];  // ... in the tiles ahead of this one, in every tile
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, b = blockIdx.y;
+    const long t = blockIdx.x;
+    if constexpr (kEmit) {
+        for (int v = wave; v < V; v += kTopkThreads / 64) {  // (uniform over the wave)
+            const int* tc = tile_counts + ((long)b * V + v) * tiles;
+            int before = 0, every = 0;
+            for (long i = lane; i < tiles; i += 64) {
+                const int c = tc[i];
+                every += c;
+                before += i < t ? c : 0;
+            }
+            before = wave_sum_int(before);
+            every = wave_sum_int(every);
+            if (lane == 0) {
+                ahead[v] = before;
+                all[v] = every;
+            }
+        }
+        if (!out) {  // count only (uniform over the grid)
+            __syncthreads();
+            if (tid < V) counts[(long)b * V + tid] = all[tid];
+            return;
+        }
+    }
+    if (tid < V * 9) (&Al[0][0])[tid] = A[(long)b * V * 9 + tid];
+    if (tid < V) wv[tid] = weights.w[tid];
+    __syncthreads();
+    const long n0 = t * kTopkTile + (long)tid * 4;
+    float r[4][9];
+    const bool want[4] = {true, true, true, true};
+    load_rotations4(Q + (long)b * q_batch_stride, n0, N, want, r);  // a lane past N reads nothing and holds zeros
+    unsigned long long gm = 0ull;  // bit 4 v + e: view v takes part in hypothesis n0 + e
+    for (int v = 0; v < V; ++v) {
+        if (!(wv[v] > 0.0f)) continue;  // an absent view (uniform over the workgroup)
+#pragma unroll
+        for (int e = 0; e < 4; ++e)
+            if (n0 + e < N && view_trace(r[e], Al[v]) >= tau) gm |= 1ull << (4 * v + e);  // false for a NaN t
+    }
+    for (int v = 0; v < V; ++v) {
+        int c = 0;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) c += __popcll(__ballot((gm >> (4 * v + e)) & 1ull));
+        if (lane == 0) wt[v][wave] = c;
+    }
+    __syncthreads();
+    if constexpr (!kEmit) {
+        if (tid < V) tile_counts[((long)b * V + tid) * tiles + t] = wt[tid][0] + wt[tid][1] + wt[tid][2] + wt[tid][3];
+    } else {
+        const unsigned long long below = (1ull << lane) - 1ull;
+        for (int v = 0; v < V; ++v) {
+            const long bv = (long)b * V + v;
+            long m = ahead[v];  // the slot of this lane's first participating hypothesis
+            for (int w = 0; w < wave; ++w) m += wt[v][w];
+            bool g[4];
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                g[e] = ((gm >> (4 * v + e)) & 1ull) != 0ull;
+                m += __popcll(__ballot(g[e]) & below);  // the lanes below hold smaller n, whichever e
+            }
+            int sl[4];
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                sl[e] = kViewSlotExcluded;
+                if (!g[e]) continue;
+                sl[e] = m < capacity ? (int)m : kViewSlotOverflow;
+                if (m < capacity) view_compose_pinned(r[e], Al[v], out + (bv * capacity + m) * 9);
+                ++m;
+            }
+            int* srow = slot + bv * N;
+            if (n0 + 3 < N && aligned16(srow + n0)) {
+                *reinterpret_cast<int4*>(srow + n0) = make_int4(sl[0], sl[1], sl[2], sl[3]);
+            } else {
+#pragma unroll
+                for (int e = 0; e < 4; ++e)
+                    if (n0 + e < N) srow[n0 + e] = sl[e];
+            }
+            // the identity in the slots of this workgroup's index range past the list's end (capacity <= N: every slot has a tile)
+            const long end = (long)all[v] < capacity ? (long)all[v] : capacity;
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                const long p = n0 + e;
+                if (p < end || p >= capacity) continue;
+                float* o = out + (bv * capacity + p) * 9;
+#pragma unroll
+                for (int i = 0; i < 9; ++i) o[i] = (i & 3) == 0 ? 1.0f : 0.0f;
+            }
+        }
+        if (t == 0 && tid < V) counts[(long)b * V + tid] = all[tid];
+    }
+}
+
+__global__ __launch_bounds__(kTopkThreads) void fuse_views_compact_kernel(const float* __restrict__ scores,
+                                                                          const int* __restrict__ slot, const ViewWeights weights,
+                                                                          int V, long N, long capacity, long n_offset,
+                                                                          float* __restrict__ fused, key_t* __restrict__ best_key)
+{
+#pragma clang fp contract(off)  // w s is rounded before it is added: the definition's operation order
+    __shared__ key_t wl[kTopkThreads / 64];
+    __shared__ float wv[kViewsMax];
+    const int tid = threadIdx.x, b = blockIdx.y;
+    if (tid < V) wv[tid] = weights.w[tid];
+    __syncthreads();
+    const float* s = scores + (long)b * V * capacity;
+    const int* sm = slot + (long)b * V * N;
+    float* f = fused ? fused + (long)b * N : nullptr;
+    const long tiles = (N + kTopkTile - 1) / kTopkTile;
+    key_t best = kKeyEmpty;
+    for (long t = blockIdx.x; t < tiles; t += gridDim.x) {
+        const long n0 = t * kTopkTile + (long)tid * 4;
+        if (n0 >= N) continue;
+        float num[4] = {0.0f, 0.0f, 0.0f, 0.0f}, den[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+        for (int v = 0; v < V; ++v) {
+            const float w = wv[v];
+            if (!(w > 0.0f)) continue;  // an absent view: neither its slots nor its scores are read (uniform over the workgroup)
+            int sl[4];
+            load_slots4(sm + (long)v * N, n0, N, kViewSlotExcluded, sl);
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                const bool g = sl[e] >= 0 && (long)sl[e] < capacity;
+                const float sc = g ? s[(long)v * capacity + sl[e]] : 0.0f;  // slots rise with n: a near-coalesced gather
+                const float p = w * sc;
                 num[e] = g ? num[e] + p : num[e];
                 den[e] = g ? den[e] + w : den[e];
             }
@@ -1055,6 +1280,40 @@ hipError_t launch_fuse_views(const float* scores, const float* Q, int64_t q_batc
     const dim3 grid((unsigned)(tiles < 1024 ? tiles : 1024), (unsigned)B);
     hipLaunchKernelGGL(fuse_views_kernel, grid, dim3(kTopkThreads), 0, stream, scores, Q, (long)q_batch_stride, A, w, V, (long)N,
                        (long)n_offset, tau, limit, fused, reinterpret_cast<key_t*>(best_key));
+    return hipGetLastError();
+}
+
+// two launches: the per-tile counts into the workspace, then -- across the kernel boundary -- the slot map, the composed
+// matrices, counts and the identity padding.  out == slot == nullptr: counts only (one summing workgroup per sample).
+hipError_t launch_view_rotations_compact(const float* Q, int64_t q_batch_stride, const float* A, const float* weights, int B, int V,
+                                         int64_t N, float tau, int64_t capacity, float* out, int32_t* slot, int64_t* counts,
+                                         void* workspace, hipStream_t stream)
+{
+    ViewWeights w;
+    for (int v = 0; v < kViewsMax; ++v) w.w[v] = v < V ? (weights ? weights[v] : 1.0f) : 0.0f;
+    const int64_t tiles = view_compact_tiles(N);
+    const dim3 grid((unsigned)tiles, (unsigned)B);
+    int* tc = static_cast<int*>(workspace);
+    hipLaunchKernelGGL(view_compact_kernel<false>, grid, dim3(kTopkThreads), 0, stream, Q, (long)q_batch_stride, A, w, V, (long)N,
+                       (long)tiles, tau, (long)capacity, tc, static_cast<float*>(nullptr), static_cast<int*>(nullptr),
+                       static_cast<long long*>(nullptr));
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(view_compact_kernel<true>, out ? grid : dim3(1u, (unsigned)B), dim3(kTopkThreads), 0, stream, Q,
+                       (long)q_batch_stride, A, w, V, (long)N, (long)tiles, tau, (long)capacity, tc, out, slot,
+                       reinterpret_cast<long long*>(counts));
+    return hipGetLastError();
+}
+
+hipError_t launch_fuse_views_compact(const float* scores, const int32_t* slot, const float* weights, int B, int V, int64_t N,
+                                     int64_t capacity, int64_t n_offset, float* fused, int64_t* best_key, hipStream_t stream)
+{
+    ViewWeights w;
+    for (int v = 0; v < kViewsMax; ++v) w.w[v] = v < V ? (weights ? weights[v] : 1.0f) : 0.0f;
+    const int64_t tiles = (N + kTopkTile - 1) / kTopkTile;
+    const dim3 grid((unsigned)(tiles < 1024 ? tiles : 1024), (unsigned)B);
+    hipLaunchKernelGGL(fuse_views_compact_kernel, grid, dim3(kTopkThreads), 0, stream, scores, slot, w, V, (long)N, (long)capacity,
+                       (long)n_offset, fused, reinterpret_cast<key_t*>(best_key));
     return hipGetLastError();
 }
 

@@ -1009,7 +1009,8 @@ def fuse_view_scores(scores: torch.Tensor, Q: torch.Tensor, A: torch.Tensor, wei
 def verify_views(vol_refs: torch.Tensor, vol_query: torch.Tensor, Q: torch.Tensor, A: torch.Tensor, W1: torch.Tensor,
                  W2: torch.Tensor, b2: torch.Tensor, weights=None, max_view_angle_deg: float | None = None, n_offset: int = 0,
                  want_scores: bool = True, best_key: torch.Tensor | None = None, reset_best: bool | None = None,
-                 split_f16: bool | None = None, want_view_scores: bool = False):
+                 split_f16: bool | None = None, want_view_scores: bool = False, compact: bool = False,
+                 capacity: int | None = None, want_counts: bool = False):
     """The verify step against V posed reference views: ``vol_refs (B,V,16,8,8,8)`` with absolute rotations ``A (B,V,3,3)``,
     the query volume ``vol_query (B,16,8,8,8)``, hypotheses ``Q (N,3,3)`` / ``(B,N,3,3)`` of the QUERY's absolute rotation.
     ``view_rotations`` -> ONE scoring launch over the B*V (view, query) samples -> ``fuse_view_scores``.  Returns ``(fused (B,N)
@@ -1017,8 +1018,19 @@ def verify_views(vol_refs: torch.Tensor, vol_query: torch.Tensor, Q: torch.Tenso
     ``fuse_view_scores``, ``split_f16`` as ``score_hypotheses``.  ``select_rotation(best_key, Q)`` decodes the pose, and the fused
     row goes to ``topk`` / ``topk_modes`` / ``pose_posterior`` with ``Q`` unchanged.
     The scoring launch is ``verify_pair``'s (the query's features are built inside it, per sample, from the query volume repeated
-    per view), so at V = 1 and A = I the fused row is ``verify_pair``'s score row bit for bit.  Inference only."""
+    per view), so at V = 1 and A = I the fused row is ``verify_pair``'s score row bit for bit.  Inference only.
+    ``compact=True`` (needs ``max_view_angle_deg``): only the (view, hypothesis) pairs the angle limit lets take part are composed
+    and scored -- ``view_rotations_compact`` -> the same scoring launch over ``(B*V, M)`` -> ``fuse_view_scores_compact``; the
+    fused row and the key are the dense call's bit for bit.  ``capacity=None``: M is the largest count, read on the host (ONE
+    synchronisation); ``capacity=M``: no host read (graph-capturable), and a pair past its view's M-th is not scored and does
+    not take part (``want_counts=True`` appends ``counts (B,V)`` int64, unclipped, as the last element: compare it with M).
+    ``want_view_scores`` then gives ``(B,V,N)`` with NaN at every pair that was not scored."""
     _refuse_grad("verify_views", vol_refs, vol_query, Q, A, W1, W2, b2)
+    if compact:
+        return _verify_views_compact(vol_refs, vol_query, Q, A, W1, W2, b2, weights, max_view_angle_deg, n_offset, want_scores,
+                                     best_key, reset_best, split_f16, want_view_scores, capacity, want_counts)
+    if capacity is not None or want_counts:
+        raise RuntimeError("capacity and want_counts belong to compact=True")
     B, V, N, _ = _view_poses(A, Q)
     if vol_refs.dim() != 6 or tuple(vol_refs.shape) != (B, V) + _VOL:
         raise RuntimeError("vol_refs must be (B,V,16,8,8,8) = %s, got %s" % ((B, V) + _VOL, tuple(vol_refs.shape)))
@@ -1039,6 +1051,139 @@ def verify_views(vol_refs: torch.Tensor, vol_query: torch.Tensor, Q: torch.Tenso
         fused, key = fuse_view_scores(view_scores, Q, A, weights, max_view_angle_deg, n_offset, want_scores, best_key,
                                       reset_best)
     return (fused, key, view_scores) if want_view_scores else (fused, key)
+
+
+# ---- angle-limited multi-view verification, compact -------------------------------------------------------------
+# Under an angle limit only a share of the V N pairs takes part (Haar hypotheses: ``haar_view_fraction``); the compact path
+# composes and scores those alone and fuses through a slot map (``ahv_view_rotations_compact_f32``, include/ahv.h).
+
+def haar_view_fraction(max_view_angle_deg) -> float:
+    """``(theta - sin theta) / pi``: the share of Haar-uniform rotations within ``theta`` of any fixed rotation (0.182 at 90
+    degrees, 0.058 at 60) -- the expected ``counts / N`` of ``view_rotations_compact`` on a Haar set, for sizing ``capacity``."""
+    theta = math.radians(float(max_view_angle_deg))
+    if not 0.0 <= theta <= math.pi:
+        raise RuntimeError("max_view_angle_deg = %r outside [0, 180]" % (max_view_angle_deg,))
+    return (theta - math.sin(theta)) / math.pi
+
+
+def view_rotations_compact_workspace(B: int, V: int, N: int, device) -> torch.Tensor:
+    """A workspace for ``view_rotations_compact`` on (B, V, N): allocate it once, pass it to every call (no allocation under
+    capture)."""
+    nbytes = _lib.load().ahv_view_rotations_compact_workspace_bytes(B, V, N)
+    return torch.empty((max(nbytes, 4) // 4,), dtype=torch.int32, device=device)
+
+
+def _view_capacity(capacity, N: int) -> int:
+    M = int(capacity)
+    if not 1 <= M <= N:
+        raise RuntimeError("capacity = %r outside 1..N = %d" % (capacity, N))
+    return M
+
+
+def view_rotations_compact(Q: torch.Tensor, A: torch.Tensor, max_view_angle_deg: float, weights=None, capacity: int | None = None,
+                           workspace: torch.Tensor | None = None):
+    """The participating pairs of ``view_rotations`` under the angle limit, compacted (``ahv_view_rotations_compact_f32``) ->
+    ``(R (B,V,M,3,3), slot (B,V,N) int32, counts (B,V) int64)``.  View v takes part in hypothesis n by ``fuse_view_scores``'s
+    rule (weight > 0 and ``Q[n] @ A[b, v].T`` within the angle); per (b, v) those n are numbered in increasing order:
+    ``slot[b, v, n]`` is that number, -1 (``AHV_VIEW_SLOT_EXCLUDED``) where the pair does not take part, -2
+    (``AHV_VIEW_SLOT_OVERFLOW``) where it does but M slots were taken; ``R[b, v, m]`` equals ``view_rotations(Q, A)[b, v, n]`` bit
+    for bit at the n with slot m and is the identity past the list's end; ``counts`` is never clipped to M.
+    ``capacity=None``: a count-only call first, ``counts.max()`` is read on the host (ONE synchronisation), M = max(1, that).
+    ``capacity=M``: no host read -- graph-capturable (pass ``workspace`` from ``view_rotations_compact_workspace``); compare
+    ``counts`` with M when you choose.  Inference only."""
+    _refuse_grad("view_rotations_compact", Q, A)
+    B, V, N, qstride = _view_poses(A, Q)
+    if max_view_angle_deg is None:
+        raise RuntimeError("view_rotations_compact needs max_view_angle_deg (without a limit every pair takes part: view_rotations)")
+    tau = min_trace(max_view_angle_deg)
+    w = _view_weights(weights, V)
+    M = None if capacity is None else _view_capacity(capacity, N)
+    dev = _need_gpu(Q, A)
+    nbytes = _lib.load().ahv_view_rotations_compact_workspace_bytes(B, V, N)
+    if workspace is None:
+        workspace = view_rotations_compact_workspace(B, V, N, dev)
+    elif workspace.device != dev or workspace.dtype != torch.int32 or workspace.numel() * 4 < nbytes or not workspace.is_contiguous():
+        raise RuntimeError("workspace must be a contiguous int32 tensor of at least %d elements on %s" % (nbytes // 4, dev))
+    Qc, Ac = Q.detach().contiguous(), A.detach().contiguous()
+    counts = torch.empty((B, V), dtype=torch.int64, device=dev)
+    if M is None:
+        _call(dev, "ahv_view_rotations_compact_f32", Qc.data_ptr(), qstride, Ac.data_ptr(), w, B, V, N, tau, 1, None, None,
+              counts.data_ptr(), workspace.data_ptr(), workspace.numel() * 4)
+        M = max(1, int(counts.max().item()))  # the one host synchronisation
+    R = torch.empty((B, V, M, 3, 3), dtype=torch.float32, device=dev)
+    slot = torch.empty((B, V, N), dtype=torch.int32, device=dev)
+    _call(dev, "ahv_view_rotations_compact_f32", Qc.data_ptr(), qstride, Ac.data_ptr(), w, B, V, N, tau, M, R.data_ptr(),
+          slot.data_ptr(), counts.data_ptr(), workspace.data_ptr(), workspace.numel() * 4)
+    return R, slot, counts
+
+
+def fuse_view_scores_compact(scores: torch.Tensor, slot: torch.Tensor, weights=None, n_offset: int = 0, want_scores: bool = True,
+                             best_key: torch.Tensor | None = None, reset_best: bool | None = None):
+    """Scores of the compacted pairs ``(B,V,M)`` and the slot map ``(B,V,N)`` of ``view_rotations_compact`` -> ``(fused (B,N) or
+    None, best_key (B,) int64)`` in ONE launch (``ahv_fuse_view_scores_compact_f32``): ``fuse_view_scores`` with "view v takes
+    part in hypothesis n" read from the slot map (``slot >= 0``) and its score from ``scores[b, v, slot]``; Q and A are not
+    needed.  The same sums in the same order: with M >= every count, the dense call's fused row and key bit for bit.  A pair
+    marked -2 (overflow) does not take part.  Other keywords as ``fuse_view_scores``.  Inference only."""
+    _refuse_grad("fuse_view_scores_compact", scores)
+    if scores.dim() != 3 or slot.dim() != 3 or tuple(slot.shape[:2]) != tuple(scores.shape[:2]):
+        raise RuntimeError("scores must be (B,V,M) and slot (B,V,N) with one (B,V), got %s and %s"
+                           % (tuple(scores.shape), tuple(slot.shape)))
+    B, V, M = scores.shape
+    N = slot.shape[2]
+    if not 1 <= V <= _lib.AHV_VIEWS_MAX:
+        raise RuntimeError("V = %d outside 1..%d" % (V, _lib.AHV_VIEWS_MAX))
+    _view_capacity(M, N)
+    w = _view_weights(weights, V)
+    dev = _need_gpu(scores)
+    if slot.device != dev or slot.dtype != torch.int32:
+        raise RuntimeError("slot must be an int32 tensor on %s, got %s on %s" % (dev, slot.dtype, slot.device))
+    if best_key is None:
+        best_key = torch.empty((B,), dtype=torch.int64, device=dev)
+        reset_best = True
+    elif best_key.dtype != torch.int64 or best_key.numel() != B or best_key.device != dev or not best_key.is_contiguous():
+        raise RuntimeError("best_key must be a contiguous int64 tensor of B = %d elements on %s" % (B, dev))
+    flags = _lib.AHV_VIEWS_RESET_BEST if reset_best else 0
+    s, sl = scores.detach().contiguous(), slot.contiguous()
+    fused = torch.empty((B, N), dtype=torch.float32, device=dev) if want_scores else None
+    _call(dev, "ahv_fuse_view_scores_compact_f32", s.data_ptr(), sl.data_ptr(), w, B, V, N, M, n_offset,
+          fused.data_ptr() if want_scores else None, best_key.data_ptr(), flags)
+    return fused, best_key
+
+
+def _verify_views_compact(vol_refs, vol_query, Q, A, W1, W2, b2, weights, max_view_angle_deg, n_offset, want_scores, best_key,
+                          reset_best, split_f16, want_view_scores, capacity, want_counts):
+    """``verify_views(compact=True)``: the dense path's three stages on the participating pairs alone."""
+    if max_view_angle_deg is None:
+        raise RuntimeError("verify_views(compact=True) needs max_view_angle_deg: without an angle limit every pair takes part "
+                           "and there is nothing to compact")
+    B, V, N, _ = _view_poses(A, Q)
+    if vol_refs.dim() != 6 or tuple(vol_refs.shape) != (B, V) + _VOL:
+        raise RuntimeError("vol_refs must be (B,V,16,8,8,8) = %s, got %s" % ((B, V) + _VOL, tuple(vol_refs.shape)))
+    if tuple(vol_query.shape) != (B,) + _VOL:
+        raise RuntimeError("vol_query must be (B,16,8,8,8) with B = %d, got %s" % (B, tuple(vol_query.shape)))
+    _view_weights(weights, V)  # (weights, angle and capacity are checked before the first launch)
+    min_trace(max_view_angle_deg)
+    if capacity is not None:
+        _view_capacity(capacity, N)
+    dev = _need_gpu(vol_refs, vol_query, Q, A, W1, W2, b2)
+    split = bool(_SPLIT_F16.get() if split_f16 is None else split_f16)
+    with torch.no_grad():
+        Rc, slot, counts = view_rotations_compact(Q, A, max_view_angle_deg, weights, capacity)
+        M = Rc.shape[2]
+        vq = vol_query.detach()[:, None].expand((B, V) + _VOL).reshape((B * V,) + _VOL)
+        feat = torch.empty((B * V, 32, 64), dtype=torch.float32, device=dev) if split else None
+        view_scores, _ = _score_hypotheses_nograd(vol_refs.detach().reshape((B * V,) + _VOL), vq, Rc.reshape(B * V, M, 3, 3), W1, W2,
+                                                  b2, 0, True, None, None, split, None, tgt_is_volume=True, feat_tgt_out=feat)
+        view_scores = view_scores.reshape(B, V, M)
+        fused, key = fuse_view_scores_compact(view_scores, slot, weights, n_offset, want_scores, best_key, reset_best)
+        res = (fused, key)
+        if want_view_scores:  # (B,V,N) through the slot map, stock torch: off the hot path
+            took = slot >= 0
+            full = torch.gather(view_scores, 2, slot.clamp(min=0).to(torch.int64))
+            res += (torch.where(took, full, torch.full_like(full, float("nan"))),)
+        if want_counts:
+            res += (counts,)
+    return res
 
 
 # ---- rotation gradient of the score, gradient-based pose polishing ------------------------------------------
