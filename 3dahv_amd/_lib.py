@@ -112,6 +112,10 @@ SIGNATURES["ahv_view_rotations_compact_f32"] = (_int, [_vp, _i64, _vp, _vp, _int
                                                        _vp, ctypes.c_size_t, _vp])
 # (scores, slot, weights: HOST floats, B, V, N, capacity, n_offset, fused, best_key, flags, stream)
 SIGNATURES["ahv_fuse_view_scores_compact_f32"] = (_int, [_vp, _vp, _vp, _int, _int, _i64, _i64, _i64, _vp, _vp, _u32, _vp])
+SIGNATURES["ahv_resample_workspace_bytes"] = (ctypes.c_size_t, [_int, _i64])
+# (scores, B, N, beta, M, u: DEVICE floats or NULL, idx, workspace, workspace_bytes, flags, stream)
+SIGNATURES["ahv_resample_f32"] = (_int, [_vp, _int, _i64, ctypes.c_float, _i64, _vp, _vp, _vp, ctypes.c_size_t, _u32, _vp])
+SIGNATURES["ahv_compose_rotations_indexed_f32"] = (_int, [_vp, _vp, _i64, _i64, _vp, _i64, _int, _vp, _vp])
 
 # measurement / developer entry points (include/ahv_diag.h): not part of the drop-in boundary
 DIAG_SIGNATURES = {

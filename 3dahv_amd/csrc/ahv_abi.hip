@@ -46,6 +46,10 @@ hipError_t launch_posterior(const float*, const float*, int64_t, int, int64_t, c
 hipError_t launch_posterior_merge(const void*, int, int, int, float, void*, bool, hipStream_t);
 hipError_t launch_posterior_finish(const void*, int, int, float, float*, float*, float*, int64_t*, float*, float*, float*, float*,
                                    float*, float*, hipStream_t);
+size_t resample_stride(int64_t N);
+hipError_t launch_resample(const float*, int, int64_t, float, int64_t, const float*, int64_t*, void*, hipStream_t);
+hipError_t launch_compose_rotations_indexed(const int64_t*, const float*, int64_t, int64_t, const float*, int64_t, int, float*,
+                                            hipStream_t);
 hipError_t launch_random_rotations(uint64_t, uint64_t, int64_t, float*, hipStream_t);
 hipError_t launch_so3_grid(int64_t, int64_t, int64_t, float*, hipStream_t);
 hipError_t launch_score_backward(const float*, const float*, const float*, int64_t, const float*, const float*,
@@ -878,6 +882,50 @@ int ahv_pose_posterior_finish_f32(const void* state, int B, int K, float beta, f
     hipError_t e = ahv::launch_posterior_finish(state, B, K, beta, log_z, entropy, mean_score, n_excluded, mode_prob, rest_prob,
                                                 mode_R_mean, R_mean, mode_spread_deg, spread_deg, static_cast<hipStream_t>(stream));
     if (e != hipSuccess) return hip_fail("pose_posterior_finish: launch", e);
+    return AHV_OK;
+}
+
+// ---- posterior resampling ------------------------------------------------------------------------------------
+size_t ahv_resample_workspace_bytes(int B, int64_t N)
+{
+    if (B <= 0 || N <= 0 || N > 4294967296ll) return 0;
+    return (size_t)B * ahv::resample_stride(N);   // per sample a 32-byte header and one 16-byte record per tile, plus one
+}
+
+int ahv_resample_f32(const float* scores, int B, int64_t N, float beta, int64_t M, const float* u, int64_t* idx, void* workspace,
+                     size_t workspace_bytes, unsigned flags, void* stream)
+{
+    if (B < 0) return fail(AHV_EINVAL, "resample: negative size");
+    if (B > 65535) return fail(AHV_EINVAL, "resample: B > 65535");
+    if (N < 1 || N > 4294967296ll) return fail(AHV_EINVAL, "resample: N = %lld outside 1..2^32", (long long)N);
+    if (M < 1 || M >= (int64_t)1 << 31) return fail(AHV_EINVAL, "resample: M = %lld outside 1..2^31-1", (long long)M);
+    if (bad_beta(beta)) return fail(AHV_EINVAL, "resample: beta = %g must be finite and > 0 (1 / temperature)", (double)beta);
+    if (flags) return fail(AHV_EINVAL, "resample: unknown flags 0x%x", flags);
+    if (B == 0) return AHV_OK;
+    if (!scores || !idx) return fail(AHV_EINVAL, "resample: null pointer");
+    const size_t need = ahv_resample_workspace_bytes(B, N);
+    if (!workspace || workspace_bytes < need || (reinterpret_cast<uintptr_t>(workspace) & 15))
+        return fail(AHV_EINVAL, "resample: needs a 16-byte aligned workspace of %zu bytes (ahv_resample_workspace_bytes), got %zu",
+                    need, workspace_bytes);
+    hipError_t e = ahv::launch_resample(scores, B, N, beta, M, u, idx, workspace, static_cast<hipStream_t>(stream));
+    if (e != hipSuccess) return hip_fail("resample: launch", e);
+    return AHV_OK;
+}
+
+int ahv_compose_rotations_indexed_f32(const int64_t* idx, const float* R, int64_t r_batch_stride, int64_t N, const float* D,
+                                      int64_t M, int B, float* out, void* stream)
+{
+    if (B < 0 || N < 0 || M < 0) return fail(AHV_EINVAL, "compose_rotations_indexed: negative size");
+    if ((int64_t)B * M > (int64_t)1 << 38)
+        return fail(AHV_EINVAL, "compose_rotations_indexed: B*M = %lld output matrices exceed one launch (2^38)",
+                    (long long)((int64_t)B * M));
+    if (r_batch_stride != 0 && r_batch_stride != N * 9)
+        return fail(AHV_EINVAL, "compose_rotations_indexed: r_batch_stride %lld must be 0 or N*9", (long long)r_batch_stride);
+    if (B == 0 || M == 0) return AHV_OK;
+    if (!idx || !R || !D || !out) return fail(AHV_EINVAL, "compose_rotations_indexed: null pointer");
+    if (N == 0) return fail(AHV_EINVAL, "compose_rotations_indexed: empty rotation set");
+    hipError_t e = ahv::launch_compose_rotations_indexed(idx, R, r_batch_stride, N, D, M, B, out, static_cast<hipStream_t>(stream));
+    if (e != hipSuccess) return hip_fail("compose_rotations_indexed: launch", e);
     return AHV_OK;
 }
 

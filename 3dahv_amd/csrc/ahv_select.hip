@@ -1,5 +1,6 @@
 // ahv_select.hip -- pose selection: everything that happens AFTER the scores exist.  Packed keys (arg-max, fill), K-best
-// lists (top-K, merge, decode + gather, compose), distinct modes, the pose posterior and the SO(3) ascent step.  These kernels
+// lists (top-K, merge, decode + gather, compose), distinct modes, the pose posterior, draws from it (systematic resampling, the
+// indexed compose) and the SO(3) ascent step.  These kernels
 // read scores, keys and rotation matrices only: no volume, no MFMA.  (unpack_best_kernel, the decode without a gather, sits
 // with the scorer in ahv_score.hip.)
 #include "ahv_device.h"
@@ -1088,6 +1089,286 @@ __global__ __launch_bounds__(64) void posterior_finish_kernel(const char* __rest
     post_project(M, Rm, sp);
 }
 
+// ---------------------------------------------------------------------------------
+// Posterior resampling (ahv_resample_f32): M systematic (low-variance) draws from the softmax of a score row.  With m the
+// largest finite score, w_i = exp((s_i - m) beta) for a finite s_i, else 0, C_i the inclusive prefix sum of w and Z = C_{N-1},
+// draw j sits at t_j = (j + u) Z / M and returns the one i with C_{i-1} <= t_j < C_i.  Stated per HYPOTHESIS instead: i owns the
+// slots [h_{i-1}, h_i), h_i = clamp(ceil(C_i M / Z - u), 0, M) -- the number of draws that sit below C_i.  What must hold
+// whatever the rounding holds by construction: the boundaries are INTEGERS, clamped tile by tile into the tile's own range,
+// made non-decreasing by an integer max-scan, and the last hypothesis with a positive weight takes the range's end; a
+// hypothesis without weight takes the boundary of the one before it and owns nothing.  Every slot then has exactly one owner,
+// the draw list is non-decreasing, and there is one fixed summation order per (B, N): bitwise reproducible, no atomics.
+//  - resample_partial_kernel: per tile of kTopkTile hypotheses (load_scores4) the tile's own finite maximum m_t and
+//    sum expf((s - m_t) beta) in fp64 (a lane's four in sequence, DPP inside a wave, the four waves in the order 0..3): one
+//    record { m_t, sum_t } per TILE to the workspace.
+//  - resample_scan_kernel: one wave per sample.  m = max m_t; q_t = sum_t exp((m_t - m) beta) in fp64; the exclusive prefix
+//    P_t in the order t = 0 .. T-1 by one lane (a serial pass over T = N / 1024 records: meant for the N of a verify step);
+//    the tile boundaries G_t = h(P_t), G_0 = 0 and G_t = M behind the last tile that holds weight.  P_t is a running sum of
+//    non-negative terms and h is monotone in its argument, so G is non-decreasing as it comes.  Record t becomes { P_t, G_t }.
+//  - resample_emit_kernel: a tile that owns no slot is skipped.  Otherwise the weights again, against m this time; the in-tile
+//    inclusive scan in fp64 (a lane's four in sequence, a wave scan by shuffles, four wave totals through LDS); the integer
+//    boundaries and their max-scan in the same shape; the tile's 1024 boundaries in LDS as int32.  Then the threads stride
+//    over the tile's DRAWS j in [G_t, G_{t+1}), each finding its hypothesis by a binary search in LDS -- a peaked row, where
+//    one hypothesis owns nearly all M slots, is written by all 256 lanes and not by one.  A sample without a finite score has
+//    G = 0, M, M, ...: tile 0 writes -1 into every slot.
+// The hand-over between the launches is the KERNEL BOUNDARY: no ticket, no workgroup waits on another one, no atomics.
+// The quotient is taken as (C M) / Z and not as C (M / Z): where the weights are exactly 1 (equal scores) C M and Z are
+// integers, the division is exact wherever its result is an integer, and the draw list is the exact-arithmetic one.
+// ---------------------------------------------------------------------------------
+constexpr int kResHeader = 32;  // bytes per sample in front of the records: doubles m, Z, u, reserved (0)
+constexpr int kResRecord = 16;  // bytes per record; tiles + 1 records per sample
+
+int64_t resample_tiles(int64_t N) { return (N + kTopkTile - 1) / kTopkTile; }
+size_t resample_stride(int64_t N) { return (size_t)kResHeader + (size_t)(resample_tiles(N) + 1) * kResRecord; }
+
+__device__ __forceinline__ bool res_finite(float s) { return fabsf(s) < __builtin_inff(); }  // false for NaN and +-inf
+
+// the number of draws j in [0, M) with (j + u) Z / M < C, for 0 <= C <= Z (to rounding), Z > 0
+__device__ __forceinline__ long long res_boundary(double C, double Md, double Z, double u, long long M)
+{
+    const double x = ceil(C * Md / Z - u);
+    if (!(x > 0.0)) return 0;  // (also a NaN: cannot arise, stays in range)
+    return x >= Md ? M : (long long)x;
+}
+
+__device__ __forceinline__ int wave_max_int(int x)
+{
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) {
+        const int o = __shfl_xor(x, off, 64);
+        x = o > x ? o : x;
+    }
+    return x;
+}
+
+__global__ __launch_bounds__(kTopkThreads) void resample_partial_kernel(const float* __restrict__ scores, long N, long tiles,
+                                                                        float beta, char* __restrict__ ws, size_t stride)
+{
+    __shared__ float wm[kTopkThreads / 64];
+    __shared__ double wsum[kTopkThreads / 64];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, b = blockIdx.y;
+    const float* s = scores + (long)b * N;
+    double* rec = reinterpret_cast<double*>(ws + (size_t)b * stride + kResHeader);
+    for (long t = blockIdx.x; t < tiles; t += gridDim.x) {  // (uniform over the workgroup)
+        float sc[4];
+        load_scores4(s, t * kTopkTile + (long)tid * 4, N, -INFINITY, sc);
+        float mx = -INFINITY;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) mx = (res_finite(sc[e]) && sc[e] > mx) ? sc[e] : mx;
+        mx = wave_max_f32_dpp(mx);
+        if (lane == 0) wm[wave] = mx;
+        __syncthreads();
+        float mt = wm[0];
+#pragma unroll
+        for (int w = 1; w < kTopkThreads / 64; ++w) mt = wm[w] > mt ? wm[w] : mt;
+        double acc = 0.0;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) acc += res_finite(sc[e]) ? (double)expf((sc[e] - mt) * beta) : 0.0;
+        acc = wave_sum_dpp_f64(acc);
+        if (lane == 63) wsum[wave] = acc;
+        __syncthreads();
+        if (tid == 0) {
+            double sum = wsum[0];
+#pragma unroll
+            for (int w = 1; w < kTopkThreads / 64; ++w) sum += wsum[w];
+            rec[2 * t] = (double)mt;
+            rec[2 * t + 1] = sum;
+        }
+        __syncthreads();  // wm / wsum are free for the next tile
+    }
+}
+
+// one wave per sample; u: [B] or nullptr
+__global__ __launch_bounds__(64) void resample_scan_kernel(char* __restrict__ ws, size_t stride, long tiles, long long M,
+                                                           float beta, const float* __restrict__ u)
+{
+    __shared__ long last_tile;
+    const int lane = threadIdx.x, b = blockIdx.x;
+    double* hdr = reinterpret_cast<double*>(ws + (size_t)b * stride);
+    double* rec = hdr + kResHeader / 8;
+    const double bd = (double)beta, Md = (double)M;
+    double m = -INFINITY;
+    for (long t = lane; t < tiles; t += 64) m = rec[2 * t] > m ? rec[2 * t] : m;
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) {
+        const double o = __shfl_xor(m, off, 64);
+        m = o > m ? o : m;
+    }
+    for (long t = lane; t < tiles; t += 64) {  // q_t over sum_t
+        const double mt = rec[2 * t];
+        rec[2 * t + 1] = mt == -INFINITY ? 0.0 : rec[2 * t + 1] * exp((mt - m) * bd);
+    }
+    __syncthreads();
+    float uv = u ? u[b] : 0.5f;
+    uv = (uv >= 0.0f && uv < 1.0f) ? uv : 0.5f;  // false for a NaN
+    double Z = 0.0;
+    if (lane == 0) {  // the prefix in the order t = 0 .. T-1; P_t over m_t
+        long last = -1;
+        for (long t = 0; t < tiles; ++t) {
+            const double q = rec[2 * t + 1];
+            rec[2 * t] = Z;
+            Z += q;
+            last = q > 0.0 ? t : last;
+        }
+        rec[2 * tiles] = Z;
+        hdr[0] = m;
+        hdr[1] = Z;
+        hdr[2] = (double)uv;
+        hdr[3] = 0.0;
+        last_tile = last;
+    }
+    __syncthreads();
+    Z = hdr[1];
+    const long last = last_tile;
+    long long* G = reinterpret_cast<long long*>(rec);
+    for (long t = lane; t <= tiles; t += 64)  // G_t over q_t
+        G[2 * t + 1] = t == 0 ? 0 : t > last ? M : res_boundary(rec[2 * t], Md, Z, (double)uv, M);
+}
+
+__global__ __launch_bounds__(kTopkThreads) void resample_emit_kernel(const float* __restrict__ scores, long N, long tiles,
+                                                                     float beta, long long M, const char* __restrict__ ws,
+                                                                     size_t stride, long long* __restrict__ idx)
+{
+    __shared__ __attribute__((aligned(16))) int hb[kTopkTile];                  // the tile's boundaries: hypothesis i owns the slots [hb[i-1], hb[i])
+    __shared__ double wtot[kTopkThreads / 64];     // the waves' weight
+    __shared__ int wlast[kTopkThreads / 64], wh[kTopkThreads / 64];
+    __shared__ key_t wkey[kTopkThreads / 64];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, b = blockIdx.y;
+    const float* s = scores + (long)b * N;
+    const double* hdr = reinterpret_cast<const double*>(ws + (size_t)b * stride);
+    const double* rec = hdr + kResHeader / 8;
+    const long long* G = reinterpret_cast<const long long*>(rec);
+    long long* out = idx + (long)b * M;
+    const double md = hdr[0], Z = hdr[1], u = hdr[2], Md = (double)M;
+    const float m = (float)md;  // (exact: it is a score)
+    for (long t = blockIdx.x; t < tiles; t += gridDim.x) {  // (uniform over the workgroup)
+        const long long g0 = G[2 * t + 1], g1 = G[2 * t + 3];
+        if (g1 <= g0 || g0 < 0 || g1 > M) continue;  // the tile owns no slot (a workspace that is not the scan's: stay in bounds)
+        if (md == -INFINITY) {  // no finite score in the sample: tile 0 owns every slot
+            for (long long j = g0 + tid; j < g1; j += kTopkThreads) out[j] = -1;
+            continue;
+        }
+        const long n0 = t * kTopkTile + (long)tid * 4;
+        float sc[4];
+        load_scores4(s, n0, N, -INFINITY, sc);
+        double r[4];
+        bool has[4];    // a weight above 0
+        int mine = -1;  // this lane's last hypothesis with weight, as its place in the tile
+        double run = 0.0;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            const double w = res_finite(sc[e]) ? (double)expf((sc[e] - m) * beta) : 0.0;
+            has[e] = w > 0.0;
+            mine = has[e] ? tid * 4 + e : mine;
+            run += w;
+            r[e] = run;
+        }
+        double incl = run;  // the wave's inclusive scan of the lanes' totals
+#pragma unroll
+        for (int off = 1; off < 64; off <<= 1) {
+            const double o = __shfl_up(incl, off, 64);
+            incl = lane >= off ? incl + o : incl;
+        }
+        double excl = __shfl_up(incl, 1, 64);
+        excl = lane == 0 ? 0.0 : excl;
+        const int wl = wave_max_int(mine);
+        if (lane == 63) wtot[wave] = incl;
+        if (lane == 0) wlast[wave] = wl;
+        __syncthreads();
+        double base = 0.0;
+        int lastpos = wlast[0];
+#pragma unroll
+        for (int w = 1; w < kTopkThreads / 64; ++w) {
+            base = w <= wave ? base + wtot[w - 1] : base;
+            lastpos = wlast[w] > lastpos ? wlast[w] : lastpos;
+        }
+        if (lastpos < 0) {
+            // Slots, but no weight: every fp32 weight of the tile underflowed against m while its fp64 tile sum did not (scores
+            // more than 87 / beta below the maximum, and u = 0 or a tile in front of all others).  The slots go to the tile's
+            // largest finite score, which is where the exact weights put them.
+            key_t k = kKeyEmpty;
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                const key_t c = res_finite(sc[e]) ? pack_key(sc[e], (unsigned)(tid * 4 + e)) : kKeyEmpty;
+                k = c > k ? c : k;
+            }
+            k = wave_max_key_dpp(k);
+            if (lane == 0) wkey[wave] = k;
+            __syncthreads();
+            k = wkey[0];
+#pragma unroll
+            for (int w = 1; w < kTopkThreads / 64; ++w) k = wkey[w] > k ? wkey[w] : k;
+            const long long at = t * kTopkTile + (k == kKeyEmpty ? 0 : key_index(k));
+            for (long long j = g0 + tid; j < g1; j += kTopkThreads) out[j] = at;
+            __syncthreads();
+            continue;
+        }
+        const double P = rec[2 * t];
+        int h[4];  // (M < 2^31)
+        int hrun = (int)g0;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            const int i = tid * 4 + e;
+            long long v = g0;  // without weight: the boundary of the one before (after the max-scan)
+            if (i >= lastpos) {
+                v = g1;
+            } else if (has[e]) {
+                v = res_boundary(P + (base + (excl + r[e])), Md, Z, u, M);
+                v = v < g0 ? g0 : v > g1 ? g1 : v;
+            }
+            hrun = (int)v > hrun ? (int)v : hrun;
+            h[e] = hrun;
+        }
+        int hin = hrun;  // the wave's inclusive max-scan of the lanes' last boundaries
+#pragma unroll
+        for (int off = 1; off < 64; off <<= 1) {
+            const int o = __shfl_up(hin, off, 64);
+            hin = (lane >= off && o > hin) ? o : hin;
+        }
+        int hex = __shfl_up(hin, 1, 64);
+        hex = lane == 0 ? (int)g0 : hex;
+        if (lane == 63) wh[wave] = hin;
+        __syncthreads();
+#pragma unroll
+        for (int w = 1; w < kTopkThreads / 64; ++w) hex = (w <= wave && wh[w - 1] > hex) ? wh[w - 1] : hex;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) h[e] = h[e] > hex ? h[e] : hex;
+        *reinterpret_cast<int4*>(hb + tid * 4) = make_int4(h[0], h[1], h[2], h[3]);
+        __syncthreads();
+        for (long long j = g0 + tid; j < g1; j += kTopkThreads) {  // the owner of slot j: the first i with hb[i] > j
+            int lo = 0, hi = lastpos;  // (hb[lastpos] = g1 > j)
+            while (lo < hi) {
+                const int mid = (lo + hi) >> 1;
+                if ((long long)hb[mid] > j) hi = mid;
+                else lo = mid + 1;
+            }
+            out[j] = t * kTopkTile + lo;
+        }
+        __syncthreads();  // hb and the wave words are free for the next tile
+    }
+}
+
+// out[b][j] = R[b][idx[b][j]] D[j], the product as compose_rotations_topk_kernel writes it; an index outside [0, N) composes row 0
+__global__ __launch_bounds__(256) void compose_rotations_indexed_kernel(const long long* __restrict__ idx,
+                                                                        const float* __restrict__ R, long r_batch_stride, long N,
+                                                                        const float* __restrict__ D, long M, long total,
+                                                                        float* __restrict__ out)
+{
+    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;  // b M + j
+    if (i >= total) return;
+    const long b = i / M;
+    const long j = i - b * M;
+    long n = (long)idx[i];
+    n = (n < 0 || n >= N) ? 0 : n;  // -1 (a sample without a finite score) or a foreign list: stay in bounds
+    const float* r = R + b * r_batch_stride + n * 9;
+    const float* d = D + j * 9;
+    float* o = out + i * 9;
+#pragma unroll
+    for (int a = 0; a < 3; ++a)
+#pragma unroll
+        for (int c = 0; c < 3; ++c) o[a * 3 + c] = r[a * 3] * d[c] + r[a * 3 + 1] * d[3 + c] + r[a * 3 + 2] * d[6 + c];
+}
+
 // ---- SO(3) ascent step (ahv_so3_ascent_candidates_f32 / ahv_so3_ascent_select_f32) ----------------------
 // One thread per seed (b, k); rotations.so3_ascent_candidates / so3_ascent_select state the same rules in torch.
 // Direction: the Riemannian gradient in the body frame, w = vee(1/2 (R^T G - G^T R)); candidate slot 0 is R_cur bit for bit,
@@ -1344,6 +1625,35 @@ hipError_t launch_posterior_finish(const void* state, int B, int K, float beta, 
     hipLaunchKernelGGL(posterior_finish_kernel, dim3((unsigned)B), dim3(64), 0, stream, static_cast<const char*>(state), B, K, beta,
                        log_z, entropy, mean_score, reinterpret_cast<long long*>(n_excluded), mode_prob, rest_prob, mode_R_mean,
                        R_mean, mode_spread_deg, spread_deg);
+    return hipGetLastError();
+}
+
+// ---- posterior resampling ---------------------------------------------------------------------------------
+// three launches: a record per tile, the scan of the records, the draws (u: [B] on the device, or nullptr)
+hipError_t launch_resample(const float* scores, int B, int64_t N, float beta, int64_t M, const float* u, int64_t* idx,
+                           void* workspace, hipStream_t stream)
+{
+    const int64_t tiles = resample_tiles(N);
+    const size_t stride = resample_stride(N);
+    const dim3 grid((unsigned)(tiles < 1024 ? tiles : 1024), (unsigned)B);
+    char* ws = static_cast<char*>(workspace);
+    hipLaunchKernelGGL(resample_partial_kernel, grid, dim3(kTopkThreads), 0, stream, scores, (long)N, (long)tiles, beta, ws, stride);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(resample_scan_kernel, dim3((unsigned)B), dim3(64), 0, stream, ws, stride, (long)tiles, (long long)M, beta, u);
+    e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(resample_emit_kernel, grid, dim3(kTopkThreads), 0, stream, scores, (long)N, (long)tiles, beta, (long long)M,
+                       static_cast<const char*>(ws), stride, reinterpret_cast<long long*>(idx));
+    return hipGetLastError();
+}
+
+hipError_t launch_compose_rotations_indexed(const int64_t* idx, const float* R, int64_t r_batch_stride, int64_t N, const float* D,
+                                            int64_t M, int B, float* out, hipStream_t stream)
+{
+    const long total = (long)B * M;
+    hipLaunchKernelGGL(compose_rotations_indexed_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream,
+                       reinterpret_cast<const long long*>(idx), R, (long)r_batch_stride, (long)N, D, (long)M, total, out);
     return hipGetLastError();
 }
 

@@ -915,6 +915,120 @@ def verify_pair_posterior(vol_src: torch.Tensor, vol_tgt: torch.Tensor, R: torch
     return m_s, m_i, m_R, pose_posterior(scores, R, temperature, anchors=m_R, min_angle_deg=min_angle_deg)
 
 
+# ---- posterior resampling -----------------------------------------------------------------------------------------
+# M systematic (low-variance) draws from the softmax of a score row at temperature T (``ahv_resample_f32``, include/ahv.h): draw
+# j sits at (j + u) Z / M on the cumulative weights and returns the hypothesis whose interval holds it.  The draw list is
+# non-decreasing, hypothesis i appears floor(M p_i) or ceil(M p_i) times, and the same inputs give the same bytes.  Rows do not
+# compose across shards: gather the scores first (``dist.all_gather_scores``).
+
+# (device, B, N) -> workspace (the tile records of one call): static like _TOPK_WS, and under the same rule
+_RESAMPLE_WS = {}
+
+ResampledVerify = collections.namedtuple(
+    "ResampledVerify", ["score", "idx", "R_pred", "draws", "fine_scores", "R_fine", "coarse_scores", "coarse_key"])
+
+
+def _draws(m) -> int:
+    m = int(m)
+    if not 1 <= m < (1 << 31):
+        raise RuntimeError("M = %d draws outside 1..2^31-1" % m)
+    return m
+
+
+def resample_workspace(B: int, N: int, device) -> torch.Tensor | None:
+    """A workspace for ``resample`` on (B, N): allocate it once, pass it to every call (no allocation under capture)."""
+    nbytes = _lib.load().ahv_resample_workspace_bytes(int(B), int(N))
+    return torch.empty((nbytes,), dtype=torch.uint8, device=device) if nbytes else None
+
+
+@torch.no_grad()
+def resample(scores: torch.Tensor, m: int, temperature: float = 0.1, u: torch.Tensor | None = None,
+             out: torch.Tensor | None = None, workspace: torch.Tensor | None = None) -> torch.Tensor:
+    """``m`` systematic draws per sample from the softmax of ``scores (B,N)`` at ``temperature`` (``ahv_resample_f32``): a
+    non-decreasing int64 list ``(B,m)`` of hypothesis indices, hypothesis i in it ``floor(m p_i)`` or ``ceil(m p_i)`` times;
+    non-finite scores are never drawn and a row without a finite score gives -1 everywhere.  ``u``: a float32 tensor ``(B,)``
+    on the device, one offset in [0, 1) per sample (read on the device: a captured graph follows it), or None for 0.5; a value
+    outside [0, 1) or NaN counts as 0.5.  ``out``: an int64 ``(B,m)`` tensor to write to; ``workspace``: a uint8 tensor of
+    ``ahv_resample_workspace_bytes`` bytes (``resample_workspace``), else a static one per shape.  With both given the call
+    allocates nothing.  Three launches."""
+    if scores.dim() != 2:
+        raise RuntimeError("scores must be (B,N)")
+    m = _draws(m)
+    beta = inverse_temperature(temperature)
+    B, N = scores.shape
+    if N < 1:
+        raise RuntimeError("scores hold no hypothesis (N = 0)")
+    if u is not None:
+        if not isinstance(u, torch.Tensor) or u.dtype != torch.float32 or tuple(u.shape) != (B,) or not u.is_contiguous():
+            raise RuntimeError("u must be a contiguous float32 tensor (B,) = (%d,) on the device of scores, or None" % B)
+    if out is not None and (out.dtype != torch.int64 or tuple(out.shape) != (B, m) or not out.is_contiguous()):
+        raise RuntimeError("out must be a contiguous int64 tensor (B,M) = %s" % ((B, m),))
+    nbytes = _lib.load().ahv_resample_workspace_bytes(B, N)
+    if workspace is not None and workspace.numel() * workspace.element_size() < nbytes:
+        raise RuntimeError("workspace of %d bytes, need %d (ahv_resample_workspace_bytes)"
+                           % (workspace.numel() * workspace.element_size(), nbytes))
+    dev = _need_gpu(scores) if u is None else _need_gpu(scores, u)
+    if out is None:
+        out = torch.empty((B, m), dtype=torch.int64, device=dev)
+    elif out.device != dev:
+        raise RuntimeError("Expected all tensors to be on the same device, found %s and %s" % (dev, out.device))
+    if B == 0:
+        return out
+    workspace, have = _workspace(_RESAMPLE_WS, (dev, B, N), nbytes, torch.uint8, workspace)
+    s = scores.detach().contiguous()
+    _call(dev, "ahv_resample_f32", s.data_ptr(), B, N, beta, m, u.data_ptr() if u is not None else None, out.data_ptr(),
+          workspace.data_ptr(), have, 0)
+    return out
+
+
+@torch.no_grad()
+def compose_rotations_indexed(idx: torch.Tensor, R: torch.Tensor, D: torch.Tensor, out: torch.Tensor | None = None) -> torch.Tensor:
+    """Refinement hypotheses of a draw list: ``out[b, j] = R[idx[b, j]] @ D[j]`` -> (B, M, 3, 3)
+    (``ahv_compose_rotations_indexed_f32``).  ``idx (B,M)`` int64 (``resample``), R (N,3,3) or (B,N,3,3), D (M,3,3).  An index
+    outside [0, N), -1 included, composes row 0 (stays in bounds, as ``compose_rotations_topk`` does: look at ``idx``)."""
+    if idx.dim() != 2 or idx.dtype != torch.int64:
+        raise RuntimeError("idx must be a (B,M) int64 tensor")
+    if not idx.is_cuda:
+        raise RuntimeError("3dahv_amd ops run on the GPU only (no CPU fallback); got a tensor on %s" % idx.device)
+    if not idx.is_contiguous():
+        raise RuntimeError("idx must be contiguous")
+    B, M = idx.shape
+    _need_gpu(R, D)
+    if R.device != idx.device:
+        raise RuntimeError("Expected all tensors to be on the same device, found %s and %s" % (idx.device, R.device))
+    N, rstride = _rot_layout(R, B)
+    if D.dim() != 3 or tuple(D.shape) != (M, 3, 3):
+        raise RuntimeError("D must be (M,3,3) with M = %d draws, got %s" % (M, tuple(D.shape)))
+    Rc, Dc = R.detach().contiguous(), D.detach().contiguous()
+    if out is None:
+        out = torch.empty((B, M, 3, 3), dtype=torch.float32, device=Rc.device)
+    elif tuple(out.shape) != (B, M, 3, 3) or not out.is_contiguous() or out.dtype != torch.float32:
+        raise RuntimeError("out must be a contiguous float32 (B, M, 3, 3) tensor")
+    _call(out.device, "ahv_compose_rotations_indexed_f32", idx.data_ptr(), Rc.data_ptr(), rstride, N, Dc.data_ptr(), M, B,
+          out.data_ptr())
+    return out
+
+
+def verify_pair_resampled(vol_src: torch.Tensor, vol_tgt: torch.Tensor, R: torch.Tensor, D: torch.Tensor, W1: torch.Tensor,
+                          W2: torch.Tensor, b2: torch.Tensor, temperature: float = 0.1, u: torch.Tensor | None = None, **kw):
+    """The verify step with posterior-weighted refinement: ``verify_pair`` with the scores kept -> ``resample`` (``M =
+    D.shape[0]`` draws) -> ``compose_rotations_indexed`` (draw j refined by ``D[j]``) -> ``score_hypotheses`` on the draws ->
+    ``select_rotation``.  Returns a ``ResampledVerify``: the fine winner ``score (B,)``, ``idx (B,)`` in [0, M) and ``R_pred
+    (B,3,3)``, the draw list ``draws (B,M)``, ``fine_scores (B,M)``, the composed set ``R_fine (B,M,3,3)``, and the coarse
+    ``coarse_scores (B,N)`` / arg-max ``coarse_key (B,)``.  Other keywords go to ``verify_pair``."""
+    if D.dim() != 3 or tuple(D.shape[1:]) != (3, 3):
+        raise RuntimeError("D must be (M,3,3)")
+    m = _draws(D.shape[0])
+    beta = inverse_temperature(temperature)  # (checked before the first launch)
+    del beta
+    s1, key1, f_tgt = verify_pair(vol_src, vol_tgt, R, W1, W2, b2, want_scores=True, want_feat_tgt=True, **kw)
+    draws = resample(s1, m, temperature, u=u)
+    R_fine = compose_rotations_indexed(draws, R, D)
+    s2, key2 = score_hypotheses(vol_src, f_tgt, R_fine, W1, W2, b2, want_scores=True)
+    score, idx, R_pred = select_rotation(key2, R_fine)
+    return ResampledVerify(score, idx, R_pred, draws, s2, R_fine, s1, key1)
+
+
 # ---- multi-view verification ---------------------------------------------------------------------------------------
 # V posed reference views of one object (absolute rotations A_v), one query whose absolute rotation is wanted, N hypotheses Q_n
 # of it: view v sees hypothesis n as R_{v,n} = Q_n A_v^T (gt_src_2_tgt_R = R_tgt R_src^-1), and the per-view scores are fused

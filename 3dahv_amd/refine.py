@@ -77,6 +77,19 @@ class CoarseToFine:
     R_after, theta``.  Multi-rank: after the second key all-reduce every rank holds the same winner and the whole volumes, and
     the rotation gradient is a function of the hypothesis alone bit for bit, so every rank computes the same bits -- still
     two collectives per step.  ``polish_iters=0`` is the step described above, unchanged; ``fused`` with polishing raises.
+    ``resample=True`` (posterior-weighted refinement, ``ops.resample``): stage 2 scores ``M = D.shape[0]`` systematic DRAWS
+    from the softmax of the coarse row at ``resample_temperature`` instead of M refinements of one winner: draw j is coarse
+    hypothesis ``idx[j]`` refined by ``D[j]``, so a peak that holds 70 % of the posterior mass gets 70 % of the refinements and
+    three broad peaks share them.  ``resample_u``: the offset in [0, 1) of the draws -- a float, a float32 tensor (B,) on the
+    device (read there: a captured step follows it), or None for 0.5.  Slot 0 of the draw list is overwritten with the coarse
+    arg-max index (one small device copy); D[0] = I, so the fine score never falls below the coarse one, as in every other
+    mode of the step.  The coarse stage keeps its scores; ``compose_rotations_indexed`` takes ``compose_rotations``'s place.
+    Resampling does not compose across shards (a prefix needs the whole row), so a multi-rank step follows the modes pattern:
+    ``dist.all_gather_scores``, every rank resamples the whole row (the same draw list, byte for byte), takes the coarse
+    arg-max from the gathered row locally, composes all M draws and scores its slice; then the fine key all-reduce -- two
+    collectives per step.  ``self.last["resample"]`` is the draw list (B, M); the fine index returned lies in [0, M): the
+    coarse hypothesis is ``self.last["resample"][b, idx]``.  ``polish_iters`` composes unchanged.  Exclusive with ``seeds > 1``,
+    with ``modes`` and with ``fused``: each raises.  ``resample=False`` is every step described above, unchanged.
     ``use_graph``: None = captured when the step carries collectives, eager otherwise (see __init__); ``run_many`` replays
     several steps from one graph."""
 
@@ -85,7 +98,8 @@ class CoarseToFine:
                  batch: int = 1, use_graph: Optional[bool] = None, group=None, seed: int = 0, backend=None,
                  want_scores: bool = False, force_collectives: bool = False, no_teams: bool = False,
                  fused: Optional[bool] = None, seeds: int = 1, polish_iters: int = 0, polish_angle_deg: float = 2.0,
-                 polish_ladder=(0.25, 0.5, 1.0, 2.0), modes: int = 0, mode_angle_deg: float = 15.0):
+                 polish_ladder=(0.25, 0.5, 1.0, 2.0), modes: int = 0, mode_angle_deg: float = 15.0, resample: bool = False,
+                 resample_temperature: float = 0.1, resample_u=None):
         dev = R_coarse.device
         self.ops = ops if backend is None else backend
         self.W1, self.W2, self.b2 = W1, W2, b2
@@ -124,6 +138,26 @@ class CoarseToFine:
             self.mode_angle_deg = float(mode_angle_deg)
             ops.min_trace(self.mode_angle_deg)   # raises outside (0, 180)
             self.seeds = self.modes              # the stage-2 layout is the multi-seed one: K blocks of N2
+        self.resample = bool(resample)
+        if self.resample:
+            if self.modes:   # (first: modes = K has set seeds = K)
+                raise RuntimeError("resample = True and modes = %d are two selections of the stage-2 seeds: pass one of them"
+                                   % self.modes)
+            if self.seeds > 1:
+                raise RuntimeError("resample = True and seeds = %d are two selections of the stage-2 seeds: pass one of them"
+                                   % self.seeds)
+            if fused:
+                raise RuntimeError("the one-launch step (fused=True) refines around ONE seed; resample = True needs fused=False")
+            self.resample_temperature = float(resample_temperature)
+            ops.inverse_temperature(self.resample_temperature)   # raises unless finite and > 0
+            if resample_u is not None and not isinstance(resample_u, torch.Tensor):
+                u = float(resample_u)
+                if not 0.0 <= u < 1.0:
+                    raise RuntimeError("resample_u = %r outside [0, 1)" % (resample_u,))
+                resample_u = torch.full((batch,), u, dtype=torch.float32, device=dev)
+            if resample_u is not None and (resample_u.dtype != torch.float32 or tuple(resample_u.shape) != (batch,)):
+                raise RuntimeError("resample_u must be a float, or a float32 tensor (B,) = (%d,)" % batch)
+            self.resample_u = resample_u
         self.polish_iters = int(polish_iters)
         if self.polish_iters < 0:
             raise RuntimeError("polish_iters must be >= 0")
@@ -157,6 +191,14 @@ class CoarseToFine:
             self._block_keys = torch.full((batch, K), KEY_EMPTY, dtype=torch.int64, device=dev)
             self._block_off = (torch.arange(K, dtype=torch.int64, device=dev) * self.D.shape[0])[None]
             self._modes_ws = (ops.topk_modes_workspace(batch, n1, K, dev) if backend is None and dev.type == "cuda" else None)
+            self._s_all = self._s_stage = None
+            if self.collectives:
+                self._s_all = torch.empty((batch, n1), dtype=torch.float32, device=dev)
+                self._s_stage = torch.empty((self.world + 1, batch, -(-n1 // self.world)), dtype=torch.float32, device=dev)
+        if self.resample:   # the draw list, the workspace and (multi-rank) the gathered row live with the object
+            n1, M = self.R_coarse.shape[-3], self.D.shape[0]
+            self._draws = torch.full((batch, M), -1, dtype=torch.int64, device=dev)
+            self._resample_ws = (ops.resample_workspace(batch, n1, dev) if backend is None and dev.type == "cuda" else None)
             self._s_all = self._s_stage = None
             if self.collectives:
                 self._s_all = torch.empty((batch, n1), dtype=torch.float32, device=dev)
@@ -197,6 +239,8 @@ class CoarseToFine:
             return r["fine_score"], r["fine_idx"], r["R_pred"], r["coarse_score"], r["coarse_idx"]
         if self.modes:
             return self._step_modes(vol_src, vol_tgt, slot)
+        if self.resample:
+            return self._step_resample(vol_src, vol_tgt, slot)
         if self.seeds > 1:
             return self._step_seeds(vol_src, vol_tgt, slot)
         key1, key2 = self._keys
@@ -303,6 +347,37 @@ class CoarseToFine:
             R_pred = R[torch.arange(B, device=R.device), best]
             idx = best * N2 + m_idx[torch.arange(B, device=R.device), best]
         return score, idx, R_pred, top_scores[:, 0], top_idx[:, 0]
+
+    def _step_resample(self, vol_src, vol_tgt, slot: int = 0):
+        """The step with ``resample=True``: stage 2 scores M draws from the coarse posterior, draw j refined by ``D[j]``."""
+        o = self.ops
+        key1, key2 = self._keys
+        kw = {"no_teams": True} if self.no_teams else {}
+        Rc = self.R_coarse[self.c_lo:self.c_hi]
+        if self.collectives:  # a prefix needs the whole row: gather it, then every rank draws the same list
+            s1, _, f_tgt = o.verify_pair(vol_src, vol_tgt, Rc, self.W1, self.W2, self.b2, n_offset=self.c_lo, want_scores=True,
+                                         want_feat_tgt=True, **kw)
+            s_all = all_gather_scores(s1, self.R_coarse.shape[-3], group=self.group, force=True, out=self._s_all,
+                                      staging=self._s_stage)
+            key1 = o.argmax(s_all, return_key=True)   # the coarse arg-max from the gathered row, locally: no key all-reduce
+            coarse_score, coarse_idx, _ = o.select_rotation(key1, self.R_coarse, n_offset=0)
+        else:
+            s_all, _, f_tgt = o.verify_pair(vol_src, vol_tgt, Rc, self.W1, self.W2, self.b2, n_offset=0, want_scores=True,
+                                            best_key=key1, reset_best=False, want_feat_tgt=True, **kw)
+            coarse_score, coarse_idx, _ = o.select_rotation(key1, self.R_coarse, n_offset=0, reset_key=True)
+        draws = o.resample(s_all, self.D.shape[0], self.resample_temperature, u=self.resample_u, out=self._draws,
+                           workspace=self._resample_ws)
+        draws[:, 0].copy_(coarse_idx)   # glue: D[0] = I, so the coarse winner itself is among the fine hypotheses
+        R_fine_all = o.compose_rotations_indexed(draws, self.R_coarse, self.D, out=self._R_fine)
+        R_fine = R_fine_all if self.world == 1 else R_fine_all[:, self.f_lo:self.f_hi]
+        s2, _ = o.score_hypotheses(vol_src, f_tgt, R_fine, self.W1, self.W2, self.b2, n_offset=self.f_lo,
+                                   want_scores=self.want_scores, best_key=key2, reset_best=False, **kw)
+        self._merge(key2)
+        score, idx, R_pred = o.select_rotation(key2, R_fine_all, n_offset=0, reset_key=True)
+        self.last = {"coarse_scores": s_all if self.want_scores else None, "fine_scores": s2,
+                     "R_fine": R_fine if self.want_scores else None, "resample": draws}
+        score, R_pred = self._polish(vol_src, f_tgt, score, R_pred, slot)
+        return score, idx, R_pred, coarse_score, coarse_idx
 
     def check(self):
         """Host sync.  Raises if a one-launch step abandoned its device-wide meeting point (another kernel held compute units
