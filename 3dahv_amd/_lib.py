@@ -49,6 +49,8 @@ SIGNATURES = {
     "ahv_reset_best": (_int, [_vp, _int, _vp]),
     "ahv_rotate_volume_f32": (_int, [_vp, _i64, _vp, _i64, _int, _int, _int, _int, _vp, _vp]),
     "ahv_rotate_volume_backward_f32": (_int, [_vp, _i64, _vp, _i64, _int, _int, _int, _int, _vp, _vp]),
+    # (grad_out, vol, vol_batch_stride, R, N, C, D, H, W, grad_R, stream)
+    "ahv_rotate_volume_rotation_grad_f32": (_int, [_vp, _vp, _i64, _vp, _i64, _int, _int, _int, _int, _vp, _vp]),
     "ahv_forward_3d2d_f32": (_int, [_vp, _vp, _vp, _vp, _i64, _vp, _vp]),
     "ahv_score_features_f32": (_int, [_vp, _vp, _int, _i64, _vp, _vp]),
     "ahv_argmax_f32": (_int, [_vp, _int, _i64, _i64, _vp, _u32, _vp]),

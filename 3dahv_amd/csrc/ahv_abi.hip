@@ -58,6 +58,8 @@ hipError_t launch_score_backward(const float*, const float*, const float*, int64
 hipError_t launch_zero_fill(void* const* ptrs, const size_t* bytes, int count, hipStream_t stream);
 hipError_t launch_score_rotation_grad(const float*, const float*, const float*, int64_t, const float*, const float*,
                                       const float*, int, int64_t, const float*, float*, float*, int, hipStream_t);
+hipError_t launch_rotate_volume_rotation_grad(const float*, const float*, int64_t, const float*, int64_t, int, int, int, int,
+                                              float*, int, hipStream_t);
 hipError_t launch_so3_ascent_candidates(const float*, const float*, const float*, const float*, int, int, int, float*,
                                         hipStream_t);
 hipError_t launch_so3_ascent_select(const float*, const float*, const float*, int, int, int, float*, float*, float*,
@@ -263,6 +265,23 @@ int ahv_rotate_volume_backward_f32(const float* grad_out, int64_t vol_batch_stri
     if (cu < 0) return fail(AHV_EDEVICE, "no usable HIP device");
     hipError_t e = ahv::launch_rotate_volume_backward(grad_out, vol_batch_stride, R, N, C, D, H, W, grad_vol, cu, s);
     if (e != hipSuccess) return hip_fail("rotate_volume_backward: launch", e);
+    return AHV_OK;
+}
+
+int ahv_rotate_volume_rotation_grad_f32(const float* grad_out, const float* vol, int64_t vol_batch_stride, const float* R,
+                                        int64_t N, int C, int D, int H, int W, float* grad_R, void* stream)
+{
+    if (N < 0 || C < 1 || D < 1 || H < 1 || W < 1)
+        return fail(AHV_EINVAL, "rotate_volume_rotation_grad: bad shape N=%lld C=%d D=%d H=%d W=%d", (long long)N, C, D, H, W);
+    if (vol_batch_stride != 0 && vol_batch_stride < (int64_t)C * D * H * W)
+        return fail(AHV_EINVAL, "rotate_volume_rotation_grad: batch stride must be 0 or >= C*D*H*W");
+    if (N == 0) return AHV_OK; /* nothing to read or write, pointers may be null */
+    if (!grad_out || !vol || !R || !grad_R) return fail(AHV_EINVAL, "rotate_volume_rotation_grad: null pointer");
+    const int cu = cu_count();
+    if (cu < 0) return fail(AHV_EDEVICE, "no usable HIP device");
+    hipError_t e = ahv::launch_rotate_volume_rotation_grad(grad_out, vol, vol_batch_stride, R, N, C, D, H, W, grad_R, cu,
+                                                           static_cast<hipStream_t>(stream));
+    if (e != hipSuccess) return hip_fail("rotate_volume_rotation_grad: launch", e);
     return AHV_OK;
 }
 

@@ -71,7 +71,12 @@ def _hip_backend() -> Backend:
         if torch.is_grad_enabled() and any(x.requires_grad for x in (v, t, W1, W2, b2)):
             return ops.score_hypotheses_autograd(v, t, R, W1, W2, b2)     # the training pair: HIP forward + backward
         return ops.score_hypotheses(v, t, R, W1, W2, b2)[0]
-    return Backend(rotate_volume=ops.rotate_volume, forward_3d2d=ops.forward_3d2d, score_hypotheses=score)
+
+    def rotate(volume, R):
+        if torch.is_grad_enabled() and R.requires_grad:
+            return ops.rotate_volume_autograd(volume, R)     # materialised with rotations that need a gradient: both edges
+        return ops.rotate_volume(volume, R)
+    return Backend(rotate_volume=rotate, forward_3d2d=ops.forward_3d2d, score_hypotheses=score)
 
 
 _backend: Optional[Backend] = None

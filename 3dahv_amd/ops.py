@@ -7,6 +7,7 @@ Same names, argument meaning and error behaviour as the reference callables:
 * ``score_features`` / ``argmax``  -- the inline lines test_co3d.py:143 / :145
 * ``score_hypotheses``  -- all of the above fused into one launch (test_co3d.py:137-145)
 * ``verify_pair``  -- the same with ``forward_3d2d(vol_tgt)`` (test_co3d.py:141) inside that launch
+* ``rotate_volume_autograd`` / ``rotate_volume_rotation_grad``  -- ``rotate_volume`` differentiable w.r.t. the rotations too
 * ``score_hypotheses_autograd`` / ``forward_3d2d_autograd`` / ``score_hypotheses_backward``  -- the same with
   autograd edges for training (infoNCE_loss, modules/model_co3d.py:41-61): HIP forward + HIP backward
 
@@ -98,17 +99,68 @@ def rotate_volume(volume: torch.Tensor, rotation_matrix: torch.Tensor, padding_m
     reference passes): it is read once, never materialised.  Differentiable w.r.t. ``volume`` like the
     reference's (utils.py:113-131; infoNCE_loss back-propagates through it, modules/model_co3d.py:49-54): when
     autograd is recording and ``volume`` requires grad the call goes through ``_RotateVolumeFn`` (HIP forward, HIP
-    adjoint).  A rotation matrix that requires grad is refused loudly: the rotation gradient exists on the fused path
-    (``score_hypotheses`` / ``score_rotation_grad``), not for the materialised volumes of this op.
+    adjoint).  A rotation matrix that requires grad is refused loudly by THIS function: ``rotate_volume_autograd`` is the
+    form that is differentiable w.r.t. both inputs (the patched ``utils.rotate_volume`` routes such a call there), and when
+    the rotated volumes only feed the reference's head and score, ``score_hypotheses`` / ``score_rotation_grad`` give
+    d score / d R without materialising 32 KB per hypothesis.
     """
     if torch.is_grad_enabled():
         if rotation_matrix.requires_grad:
             raise NotImplementedError("rotate_volume: no gradient w.r.t. rotation_matrix is implemented for the op-level "
-                                      "rotation (32 KB materialised per hypothesis); detach it, or score with "
-                                      "score_hypotheses, whose autograd edge carries d score / d R")
+                                      "rotation (32 KB materialised per hypothesis); detach it, call "
+                                      "rotate_volume_autograd (differentiable w.r.t. volume and rotation_matrix), or "
+                                      "score with score_hypotheses, whose autograd edge carries d score / d R")
         if volume.requires_grad:
             return _RotateVolumeFn.apply(volume, rotation_matrix)
     return _rotate_volume_nograd(volume, rotation_matrix, padding_mode)
+
+
+def rotate_volume_autograd(volume: torch.Tensor, rotation_matrix: torch.Tensor, padding_mode: str = "zeros") -> torch.Tensor:
+    """``rotate_volume`` with autograd edges to BOTH inputs, like the reference's ``F.affine_grid`` + ``F.grid_sample``
+    (utils.py:113-131): the volume adjoint by ``ahv_rotate_volume_backward_f32``, the rotation gradient by
+    ``ahv_rotate_volume_rotation_grad_f32`` (``rotate_volume_rotation_grad``), each only when its input needs one.  Without
+    a recording graph, or with neither input requiring grad, it is the plain ``rotate_volume``."""
+    if padding_mode != "zeros":
+        raise NotImplementedError("only padding_mode='zeros' (the only mode the reference uses) is implemented")
+    if torch.is_grad_enabled() and (volume.requires_grad or rotation_matrix.requires_grad):
+        return _RotateVolumeFn.apply(volume, rotation_matrix)
+    return _rotate_volume_nograd(volume, rotation_matrix, padding_mode)
+
+
+def _shared_volume(volume: torch.Tensor) -> bool:
+    """The stride-0 expand of one volume over the batch (what the reference passes): read once, never materialised."""
+    return bool(volume.shape[0] > 1 and volume.stride(0) == 0 and volume[0].is_contiguous())
+
+
+@torch.no_grad()
+def rotate_volume_rotation_grad(volume: torch.Tensor, rotation_matrix: torch.Tensor, grad_out: torch.Tensor) -> torch.Tensor:
+    """``d <grad_out, rotate_volume(volume, R)> / d R`` as ``(N,3,3)``: what torch autograd returns for ``rotation_matrix``
+    through utils.rotate_volume (``ahv_rotate_volume_rotation_grad_f32``, include/ahv.h has the formula and the
+    conventions).  ``volume (N,C,D,H,W)`` may be a stride-0 expand of one volume; ``grad_out`` is ``(N,C,D,H,W)``.  One
+    workgroup per hypothesis and no atomics: a row is the same bits whatever N or the cut into calls are."""
+    if volume.dim() != 5:
+        raise RuntimeError("volume must be 5-D (N,C,D,H,W), got %s" % (tuple(volume.shape),))
+    if rotation_matrix.dim() != 3 or tuple(rotation_matrix.shape[1:]) != (3, 3):
+        raise RuntimeError("rotation_matrix must be (N,3,3), got %s" % (tuple(rotation_matrix.shape),))
+    N, C, D, H, W = volume.shape
+    if rotation_matrix.shape[0] != N:
+        raise RuntimeError("Expected volume and rotation_matrix to have the same batch size, got %d and %d"
+                           % (N, rotation_matrix.shape[0]))
+    if tuple(grad_out.shape) != (N, C, D, H, W):
+        raise RuntimeError("grad_out must have the rotated volumes' shape %s, got %s" % ((N, C, D, H, W), tuple(grad_out.shape)))
+    dev = _need_gpu(volume, rotation_matrix, grad_out)
+    volume = volume.detach()
+    if _shared_volume(volume):
+        src, stride = volume[0], 0
+    else:
+        src = volume.contiguous()
+        stride = C * D * H * W
+    R = rotation_matrix.detach().contiguous()
+    g = grad_out.detach().contiguous()
+    out = torch.empty((N, 3, 3), dtype=torch.float32, device=dev)
+    _call(dev, "ahv_rotate_volume_rotation_grad_f32", g.data_ptr(), src.data_ptr(), stride, R.data_ptr(), N, C, D, H, W,
+          out.data_ptr())
+    return out
 
 
 @torch.no_grad()
@@ -382,37 +434,47 @@ def score_hypotheses_backward(vol_src: torch.Tensor, feat_tgt: torch.Tensor, R: 
 
 
 class _RotateVolumeFn(torch.autograd.Function):
-    """Differentiable ``rotate_volume`` (w.r.t. the volume): HIP gather forward, HIP scatter adjoint.  A stride-0
-    batch (``v[None].expand(N, ...)``) is read once in the forward; its gradient is accumulated into ONE volume on
-    the device.  Autograd's expand-backward then sums the N rows of what this function returns, so row 0 carries
-    that volume and the other rows are zero (exact; no division by N)."""
+    """Differentiable ``rotate_volume``: HIP gather forward, HIP scatter adjoint for the volume, HIP gather for the
+    rotations (``rotate_volume_rotation_grad``).  A stride-0 batch (``v[None].expand(N, ...)``) is read once in the
+    forward; its gradient is accumulated into ONE volume on the device.  Autograd's expand-backward then sums the N rows of
+    what this function returns, so row 0 carries that volume and the other rows are zero (exact; no division by N).
+    The volume is saved only when the rotations need a gradient (a shared one as its 32 KB base)."""
 
     @staticmethod
     def forward(ctx, volume, rotation_matrix):
         out = _rotate_volume_nograd(volume, rotation_matrix)
-        N = volume.shape[0]
-        ctx.shared = bool(N > 1 and volume.stride(0) == 0 and volume[0].is_contiguous())
+        ctx.shared = _shared_volume(volume)
         ctx.vshape = tuple(volume.shape)
-        ctx.save_for_backward(rotation_matrix.detach().contiguous())
+        if ctx.needs_input_grad[1]:
+            v = volume.detach()
+            ctx.save_for_backward(rotation_matrix.detach().contiguous(), v[0] if ctx.shared else v.contiguous())
+        else:
+            ctx.save_for_backward(rotation_matrix.detach().contiguous())
         return out
 
     @staticmethod
     def backward(ctx, grad_out):
-        (R,) = ctx.saved_tensors
+        R = ctx.saved_tensors[0]
         N, C, D, H, W = ctx.vshape
         g = grad_out.contiguous()
         dev = g.device
+        g_R = None
+        if ctx.needs_input_grad[1]:
+            vol = ctx.saved_tensors[1]
+            g_R = rotate_volume_rotation_grad(vol[None].expand(N, -1, -1, -1, -1) if ctx.shared else vol, R, g)
+        if not ctx.needs_input_grad[0]:
+            return None, g_R
         if ctx.shared:
             gv = torch.empty((1, C, D, H, W), dtype=torch.float32, device=dev)
             _call(dev, "ahv_rotate_volume_backward_f32", g.data_ptr(), 0, R.data_ptr(), N, C, D, H, W, gv.data_ptr())
             # the expand's backward sums over the batch: put the whole sum in row 0
             full = torch.zeros((N, C, D, H, W), dtype=torch.float32, device=dev)
             full[0] = gv[0]
-            return full, None
+            return full, g_R
         gv = torch.empty((N, C, D, H, W), dtype=torch.float32, device=dev)
         _call(dev, "ahv_rotate_volume_backward_f32", g.data_ptr(), C * D * H * W, R.data_ptr(), N, C, D, H, W,
               gv.data_ptr())
-        return gv, None
+        return gv, g_R
 
 
 class _ScoreFn(torch.autograd.Function):

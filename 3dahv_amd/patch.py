@@ -48,12 +48,20 @@ calls = {"forward_2d3d_hip": 0, "forward_2d3d_reference": 0, "forward_3d2d_infer
 def _hip_rotate_volume(volume, rotation_matrix, padding_mode="zeros"):
     """``utils.rotate_volume`` (utils.py:113-131).  The evaluation loop's call -- a stride-0 expand of one detached volume --
     comes back deferred (``deferred.DeferredHypotheses``: same shape, dtype, device; materialised by the kernel below the
-    moment anything but the recognised score chain touches it); every other call runs ``ops.rotate_volume`` at once."""
+    moment anything but the recognised score chain touches it); every other call runs ``ops.rotate_volume`` at once, or
+    ``ops.rotate_volume_autograd`` when autograd is recording and the rotations require grad (never deferred)."""
     if _defer and padding_mode == "zeros":
         d = deferred.defer_rotate_volume(volume, rotation_matrix, allow_grad=True)
         if d is not None:
             calls["rotate_volume_deferred"] += 1
             return d
+    import torch
+    if torch.is_grad_enabled() and rotation_matrix.requires_grad:
+        # the reference's affine_grid + grid_sample back-propagate into the matrices too: the form with both edges.
+        # (The key appears in ``calls`` with the first such call: a run that never takes this path reports the keys it
+        # always did.)
+        calls["rotate_volume_autograd"] = calls.get("rotate_volume_autograd", 0) + 1
+        return ops.rotate_volume_autograd(volume, rotation_matrix, padding_mode)
     calls["rotate_volume_kernel"] += 1
     return ops.rotate_volume(volume, rotation_matrix, padding_mode)
 
