@@ -118,6 +118,12 @@ SIGNATURES["ahv_resample_workspace_bytes"] = (ctypes.c_size_t, [_int, _i64])
 # (scores, B, N, beta, M, u: DEVICE floats or NULL, idx, workspace, workspace_bytes, flags, stream)
 SIGNATURES["ahv_resample_f32"] = (_int, [_vp, _int, _i64, ctypes.c_float, _i64, _vp, _vp, _vp, ctypes.c_size_t, _u32, _vp])
 SIGNATURES["ahv_compose_rotations_indexed_f32"] = (_int, [_vp, _vp, _i64, _i64, _vp, _i64, _int, _vp, _vp])
+# (idx or NULL, R, r_batch_stride, N, best_key or NULL, M, n_fresh, B, seed, step: DEVICE int64, sigma_rad, max_angle_rad, out,
+#  omega or NULL, stream)
+SIGNATURES["ahv_diffuse_rotations_f32"] = (_int, [_vp, _vp, _i64, _i64, _vp, _i64, _i64, _int, ctypes.c_uint64, _vp, ctypes.c_float,
+                                                  ctypes.c_float, _vp, _vp, _vp])
+# (seed, step: DEVICE int64, B, u: DEVICE floats, stream)
+SIGNATURES["ahv_track_advance"] = (_int, [ctypes.c_uint64, _vp, _int, _vp, _vp])
 
 # measurement / developer entry points (include/ahv_diag.h): not part of the drop-in boundary
 DIAG_SIGNATURES = {

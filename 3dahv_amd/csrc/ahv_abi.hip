@@ -52,6 +52,9 @@ hipError_t launch_compose_rotations_indexed(const int64_t*, const float*, int64_
                                             hipStream_t);
 hipError_t launch_random_rotations(uint64_t, uint64_t, int64_t, float*, hipStream_t);
 hipError_t launch_so3_grid(int64_t, int64_t, int64_t, float*, hipStream_t);
+hipError_t launch_diffuse_rotations(const int64_t*, const float*, int64_t, int64_t, const int64_t*, int64_t, int64_t, int, uint64_t,
+                                    const int64_t*, float, float, float*, float*, hipStream_t);
+hipError_t launch_track_advance(uint64_t, int64_t*, int, float*, hipStream_t);
 hipError_t launch_score_backward(const float*, const float*, const float*, int64_t, const float*, const float*,
                                  const float*, int, int64_t, const float*, float*, float*, float*, float*, float*,
                                  float*, float*, int, hipStream_t, bool);
@@ -945,6 +948,38 @@ int ahv_compose_rotations_indexed_f32(const int64_t* idx, const float* R, int64_
     if (N == 0) return fail(AHV_EINVAL, "compose_rotations_indexed: empty rotation set");
     hipError_t e = ahv::launch_compose_rotations_indexed(idx, R, r_batch_stride, N, D, M, B, out, static_cast<hipStream_t>(stream));
     if (e != hipSuccess) return hip_fail("compose_rotations_indexed: launch", e);
+    return AHV_OK;
+}
+
+// ---- pose tracking: the predict step and the start of a step ----------------------------------------------------
+int ahv_diffuse_rotations_f32(const int64_t* idx, const float* R, int64_t r_batch_stride, int64_t N, const int64_t* best_key,
+                              int64_t M, int64_t n_fresh, int B, uint64_t seed, const int64_t* step, float sigma_rad,
+                              float max_angle_rad, float* out, float* omega, void* stream)
+{
+    if (!R || !out || !step) return fail(AHV_EINVAL, "diffuse_rotations: null pointer (R, out and step are required)");
+    if (M < 1 || M >= (int64_t)1 << 31) return fail(AHV_EINVAL, "diffuse_rotations: M = %lld outside 1..2^31-1", (long long)M);
+    if (N < 1) return fail(AHV_EINVAL, "diffuse_rotations: empty rotation set (N = %lld)", (long long)N);
+    if (n_fresh < 0 || n_fresh > M)
+        return fail(AHV_EINVAL, "diffuse_rotations: n_fresh = %lld outside 0..M = %lld", (long long)n_fresh, (long long)M);
+    if (B < 1 || B > 65535) return fail(AHV_EINVAL, "diffuse_rotations: B = %d outside 1..65535", B);
+    if (r_batch_stride != 0 && r_batch_stride != N * 9)
+        return fail(AHV_EINVAL, "diffuse_rotations: r_batch_stride %lld must be 0 or N*9", (long long)r_batch_stride);
+    if (!(sigma_rad >= 0.0f && sigma_rad < __builtin_inff()))
+        return fail(AHV_EINVAL, "diffuse_rotations: sigma = %g must be finite and >= 0", (double)sigma_rad);
+    if (!(max_angle_rad >= 0.0f && max_angle_rad < __builtin_inff()))
+        return fail(AHV_EINVAL, "diffuse_rotations: max_angle = %g must be finite and >= 0 (0: no limit)", (double)max_angle_rad);
+    hipError_t e = ahv::launch_diffuse_rotations(idx, R, r_batch_stride, N, best_key, M, n_fresh, B, seed, step, sigma_rad,
+                                                 max_angle_rad, out, omega, static_cast<hipStream_t>(stream));
+    if (e != hipSuccess) return hip_fail("diffuse_rotations: launch", e);
+    return AHV_OK;
+}
+
+int ahv_track_advance(uint64_t seed, int64_t* step, int B, float* u, void* stream)
+{
+    if (!step || !u) return fail(AHV_EINVAL, "track_advance: null pointer");
+    if (B < 1 || B > 65535) return fail(AHV_EINVAL, "track_advance: B = %d outside 1..65535", B);
+    hipError_t e = ahv::launch_track_advance(seed, step, B, u, static_cast<hipStream_t>(stream));
+    if (e != hipSuccess) return hip_fail("track_advance: launch", e);
     return AHV_OK;
 }
 

@@ -540,14 +540,18 @@ __device__ __forceinline__ void philox4x32_10(unsigned (&c)[4], unsigned k0, uns
     }
 }
 
-__global__ __launch_bounds__(256) void random_rotations_kernel(unsigned long long seed, unsigned long long offset, long N,
-                                                               float* __restrict__ out)
+// (qr, qi, qj, qk) of any norm > 0 -> the nine matrix entries at o
+__device__ __forceinline__ void quaternion_matrix(float qr, float qi, float qj, float qk, float* __restrict__ o)
 {
-    const long n = (long)blockIdx.x * 256 + threadIdx.x;
-    if (n >= N) return;
-    const unsigned long long ctr = offset + (unsigned long long)n;
-    unsigned c[4] = {(unsigned)ctr, (unsigned)(ctr >> 32), 0x3D4148u, 0u};
-    philox4x32_10(c, (unsigned)seed, (unsigned)(seed >> 32));
+    const float t = 2.0f / fmaxf(qr * qr + qi * qi + qj * qj + qk * qk, 1e-30f);
+    o[0] = 1.0f - t * (qj * qj + qk * qk); o[1] = t * (qi * qj - qk * qr);        o[2] = t * (qi * qk + qj * qr);
+    o[3] = t * (qi * qj + qk * qr);        o[4] = 1.0f - t * (qi * qi + qk * qk); o[5] = t * (qj * qk - qi * qr);
+    o[6] = t * (qi * qk - qj * qr);        o[7] = t * (qj * qk + qi * qr);        o[8] = 1.0f - t * (qi * qi + qj * qj);
+}
+
+// Four uniforms of one Philox block -> two Box-Muller pairs (g0, g1), (g2, g3): standard normal, independent.
+__device__ __forceinline__ void box_muller4(const unsigned (&c)[4], float& g0, float& g1, float& g2, float& g3)
+{
     // uniforms in (0,1]: never log(0)
     const float u0 = ((float)(c[0] >> 8) + 1.0f) * (1.0f / 16777216.0f), u1 = (float)(c[1] >> 8) * (1.0f / 16777216.0f);
     const float u2 = ((float)(c[2] >> 8) + 1.0f) * (1.0f / 16777216.0f), u3 = (float)(c[3] >> 8) * (1.0f / 16777216.0f);
@@ -555,12 +559,127 @@ __global__ __launch_bounds__(256) void random_rotations_kernel(unsigned long lon
     float s0, c0, s1, c1;
     sincosf(6.28318530717958647692f * u1, &s0, &c0);
     sincosf(6.28318530717958647692f * u3, &s1, &c1);
-    const float qr = r0 * c0, qi = r0 * s0, qj = r1 * c1, qk = r1 * s1;
-    const float t = 2.0f / fmaxf(qr * qr + qi * qi + qj * qj + qk * qk, 1e-30f);
-    float* o = out + n * 9;
-    o[0] = 1.0f - t * (qj * qj + qk * qk); o[1] = t * (qi * qj - qk * qr);        o[2] = t * (qi * qk + qj * qr);
-    o[3] = t * (qi * qj + qk * qr);        o[4] = 1.0f - t * (qi * qi + qk * qk); o[5] = t * (qj * qk - qi * qr);
-    o[6] = t * (qi * qk - qj * qr);        o[7] = t * (qj * qk + qi * qr);        o[8] = 1.0f - t * (qi * qi + qj * qj);
+    g0 = r0 * c0; g1 = r0 * s0; g2 = r1 * c1; g3 = r1 * s1;
+}
+
+// Rotation `ctr` of the Haar stream of `seed`: what ahv_random_rotations_f32 writes for offset + n = ctr, bit for bit
+// (random_rotations_kernel and the fresh slots of diffuse_rotations_kernel both call it).
+__device__ __noinline__ void haar_rotation(unsigned long long seed, unsigned long long ctr, float* __restrict__ o)
+{
+    unsigned c[4] = {(unsigned)ctr, (unsigned)(ctr >> 32), 0x3D4148u, 0u};
+    philox4x32_10(c, (unsigned)seed, (unsigned)(seed >> 32));
+    float qr, qi, qj, qk;
+    box_muller4(c, qr, qi, qj, qk);
+    quaternion_matrix(qr, qi, qj, qk, o);
+}
+
+__global__ __launch_bounds__(256) void random_rotations_kernel(unsigned long long seed, unsigned long long offset, long N,
+                                                               float* __restrict__ out)
+{
+    const long n = (long)blockIdx.x * 256 + threadIdx.x;
+    if (n >= N) return;
+    haar_rotation(seed, offset + (unsigned long long)n, out + n * 9);
+}
+
+// ---------------------------------------------------------------------------------
+// Particle-filter predict step (ahv_diffuse_rotations_f32, include/ahv.h): one thread per slot (b, j) of the new set.
+//   elite  j == 0 with a key: R[b][decode(key_b)] copied bit for bit
+//   fresh  j >= M - n_fresh: rotation (step B + b) M + j of the Haar stream of seed ^ kFreshSeed
+//   else   R[b][idx[b][j]] exp([w]x), w = sigma z clipped to max_angle, composed as unit quaternions and normalised, so that
+//          a set fed back for thousands of steps stays on SO(3)
+// The noise block of a slot is Philox(key = seed, counter = (j, b | step[47:32] << 16, kDiffuseTag, step[31:0])): a function of
+// (seed, step mod 2^48, b, j) alone, and never a block of the Haar stream (word 2 differs).  `step` is read on the device.
+// ---------------------------------------------------------------------------------
+constexpr unsigned long long kFreshSeed = 0x9E3779B97F4A7C15ull;
+constexpr unsigned kDiffuseTag = 0x444946u, kAdvanceTag = 0x414456u;
+
+__global__ __launch_bounds__(256) void diffuse_rotations_kernel(const long long* __restrict__ idx, const float* __restrict__ R,
+                                                                long r_batch_stride, long N, const key_t* __restrict__ best_key,
+                                                                long M, long n_fresh, unsigned long long seed,
+                                                                const long long* __restrict__ step, float sigma, float max_angle,
+                                                                float* __restrict__ out, float* __restrict__ omega)
+{
+    const long j = (long)blockIdx.x * 256 + threadIdx.x;
+    if (j >= M) return;
+    const long b = blockIdx.y;
+    const unsigned long long t = (unsigned long long)*step;
+    const long i = b * M + j;
+    float* o = out + i * 9;
+    float w0 = 0.0f, w1 = 0.0f, w2 = 0.0f;
+    if (j == 0 && best_key) {
+        const key_t key = best_key[b];
+        long n = key_index(key);
+        n = (key == kKeyEmpty || n < 0 || n >= N) ? 0 : n;  // as compose_rotations_topk_kernel: stay in bounds
+        const float* r = R + b * r_batch_stride + n * 9;
+#pragma unroll
+        for (int k = 0; k < 9; ++k) o[k] = r[k];
+    } else if (j >= M - n_fresh) {
+        haar_rotation(seed ^ kFreshSeed, (t * (unsigned long long)gridDim.y + (unsigned long long)b) * (unsigned long long)M + (unsigned long long)j, o);
+    } else {
+        long n = idx ? (long)idx[i] : j % N;
+        n = (n < 0 || n >= N) ? 0 : n;  // -1 (a sample without a finite score) or a foreign list: stay in bounds
+        const float* r = R + b * r_batch_stride + n * 9;
+        const float r00 = r[0], r01 = r[1], r02 = r[2], r10 = r[3], r11 = r[4], r12 = r[5], r20 = r[6], r21 = r[7], r22 = r[8];
+        unsigned c[4] = {(unsigned)j, (unsigned)b | ((unsigned)(t >> 32) << 16), kDiffuseTag, (unsigned)t};
+        philox4x32_10(c, (unsigned)seed, (unsigned)(seed >> 32));
+        float z0, z1, z2, z3;
+        box_muller4(c, z0, z1, z2, z3);
+        w0 = sigma * z0; w1 = sigma * z1; w2 = sigma * z2;
+        float a = sqrtf(w0 * w0 + w1 * w1 + w2 * w2);
+        // The clip leaves 2^-21 of room on both sides of the comparison, so that the rounded vector's exact norm stays <= max_angle.
+        if (max_angle > 0.0f && a * 1.00000048f > max_angle) {
+            const float s = (max_angle / a) * 0.99999952f;
+            w0 *= s; w1 *= s; w2 *= s;
+            a = sqrtf(w0 * w0 + w1 * w1 + w2 * w2);
+        }
+        // q(w) = (cos a/2, sin(a/2) w / a); sin(a/2) / a -> 1/2 - a^2/48 as a -> 0
+        float sh, ch;
+        sincosf(0.5f * a, &sh, &ch);
+        const float kq = a < 1e-3f ? 0.5f - a * a * (1.0f / 48.0f) : sh / a;
+        const float dr = ch, di = kq * w0, dj = kq * w1, dk = kq * w2;
+        // q(R) by Shepperd's branch: divide by the largest of the four components
+        float qr, qi, qj, qk;
+        const float tr = r00 + r11 + r22;
+        if (tr > 0.0f) {
+            const float s = 2.0f * sqrtf(tr + 1.0f);
+            qr = 0.25f * s; qi = (r21 - r12) / s; qj = (r02 - r20) / s; qk = (r10 - r01) / s;
+        } else if (r00 > r11 && r00 > r22) {
+            const float s = 2.0f * sqrtf(1.0f + r00 - r11 - r22);
+            qr = (r21 - r12) / s; qi = 0.25f * s; qj = (r01 + r10) / s; qk = (r02 + r20) / s;
+        } else if (r11 > r22) {
+            const float s = 2.0f * sqrtf(1.0f + r11 - r00 - r22);
+            qr = (r02 - r20) / s; qi = (r01 + r10) / s; qj = 0.25f * s; qk = (r12 + r21) / s;
+        } else {
+            const float s = 2.0f * sqrtf(1.0f + r22 - r00 - r11);
+            qr = (r10 - r01) / s; qi = (r02 + r20) / s; qj = (r12 + r21) / s; qk = 0.25f * s;
+        }
+        // Hamilton product q(R) q(w): the matrix of a product is the product of the matrices, R exp([w]x)
+        float pr = qr * dr - qi * di - qj * dj - qk * dk;
+        float pi = qr * di + qi * dr + qj * dk - qk * dj;
+        float pj = qr * dj - qi * dk + qj * dr + qk * di;
+        float pk = qr * dk + qi * dj - qj * di + qk * dr;
+        const float inv = 1.0f / sqrtf(fmaxf(pr * pr + pi * pi + pj * pj + pk * pk, 1e-30f));
+        pr *= inv; pi *= inv; pj *= inv; pk *= inv;
+        quaternion_matrix(pr, pi, pj, pk, o);
+    }
+    if (omega) {
+        float* w = omega + i * 3;
+        w[0] = w0; w[1] = w1; w[2] = w2;
+    }
+}
+
+// Start of a tracker step (ahv_track_advance): u[b] of step t + 1, then the counter itself.  One workgroup: the barrier
+// orders every read of *step before the one write.
+__global__ __launch_bounds__(256) void track_advance_kernel(unsigned long long seed, long long* step, int B, float* __restrict__ u)
+{
+    const unsigned long long t1 = (unsigned long long)*step + 1ull;
+    for (int b = threadIdx.x; b < B; b += 256) {
+        unsigned c[4] = {(unsigned)b, (unsigned)(t1 >> 32), kAdvanceTag, (unsigned)t1};
+        philox4x32_10(c, (unsigned)seed, (unsigned)(seed >> 32));
+        u[b] = (float)(c[0] >> 8) * (1.0f / 16777216.0f);  // 24 bits: [0, 1)
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) *step = (long long)t1;
 }
 
 // Super-Fibonacci SO(3) grid (Alexa, CVPR 2022): point i of n is the quaternion
@@ -666,6 +785,24 @@ hipError_t launch_random_rotations(uint64_t seed, uint64_t offset, int64_t N, fl
 {
     hipLaunchKernelGGL(random_rotations_kernel, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, stream,
                        (unsigned long long)seed, (unsigned long long)offset, (long)N, out);
+    return hipGetLastError();
+}
+
+hipError_t launch_diffuse_rotations(const int64_t* idx, const float* R, int64_t r_batch_stride, int64_t N, const int64_t* best_key,
+                                    int64_t M, int64_t n_fresh, int B, uint64_t seed, const int64_t* step, float sigma,
+                                    float max_angle, float* out, float* omega, hipStream_t stream)
+{
+    hipLaunchKernelGGL(diffuse_rotations_kernel, dim3((unsigned)((M + 255) / 256), (unsigned)B), dim3(256), 0, stream,
+                       reinterpret_cast<const long long*>(idx), R, (long)r_batch_stride, (long)N,
+                       reinterpret_cast<const key_t*>(best_key), (long)M, (long)n_fresh, (unsigned long long)seed,
+                       reinterpret_cast<const long long*>(step), sigma, max_angle, out, omega);
+    return hipGetLastError();
+}
+
+hipError_t launch_track_advance(uint64_t seed, int64_t* step, int B, float* u, hipStream_t stream)
+{
+    hipLaunchKernelGGL(track_advance_kernel, dim3(1), dim3(256), 0, stream, (unsigned long long)seed,
+                       reinterpret_cast<long long*>(step), B, u);
     return hipGetLastError();
 }
 

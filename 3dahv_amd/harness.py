@@ -233,6 +233,53 @@ def evaluate_category(cfg, model, sequences: Iterable[dict], num_frames: int = 2
     return (errors, details) if return_details else errors
 
 
+@torch.no_grad()
+def track_sequence(model, item: dict, tracker, ref: int = 0, proposals: Optional[torch.Tensor] = None, device=None,
+                   encoder_fn: Optional[Callable] = None, row_vector_R: bool = False) -> dict:
+    """Track ONE sequence with a ``track.PoseTracker`` (batch 1).  ``item`` is what ``SyntheticSequences`` or
+    ``co3d.Co3dSequences`` yields.  Frame ``ref`` is the reference view; every other frame is tracked in order: per frame the
+    encoder runs on (reference, frame) -- ``encoder_fn`` or ``model.forward_features`` for ``layer4`` inputs, else ``model`` --,
+    the first tracked frame goes to ``tracker.init`` with the hypotheses ``proposals (N0,3,3)`` (default: 4 096 Haar rotations,
+    seed 0) and the rest to ``tracker.step``.
+    Ground truth of frame t: ``R_t R_ref^-1``, which reads ``item["R"]`` as absolute rotations acting on column vectors (the
+    convention of ``ops.verify_views``).  ``Co3dSequences`` yields the raw annotation, which acts on ROW vectors, and
+    ``evaluate_category`` compares a model trained on it with ``R_src^T R_tgt``: pass ``row_vector_R=True`` for such items and
+    the ground truth is ``R_ref^T R_t``, the same quantity ``evaluate_category`` uses for the pair (ref, t).
+    Returns ``{"frames": [t, ...], "R_map" (F,3,3), "score" (F,), "err" (F,) degrees}`` as host tensors, one row per tracked
+    frame; the results stay on the device and this function synchronises with the host ONCE, at the end (a tracker with
+    ``use_graph=True`` synchronises on its own while it captures, on its second and third step)."""
+    if tracker.B != 1:
+        raise RuntimeError("track_sequence tracks one sequence: the tracker must have batch = 1, got %d" % tracker.B)
+    if device is None:
+        device = tracker.W1.device
+    device = torch.device(device)
+    n = int(item["n"])
+    if not 0 <= ref < n:
+        raise RuntimeError("ref = %d outside the sequence's %d frames" % (ref, n))
+    if "get_data" in item:   # lazy source (co3d.Co3dSequences): decode every frame of the sequence
+        item = dict(item, **item["get_data"](np.arange(n)))
+    uses_l4 = "layer4" in item
+    frames = (item["layer4"] if uses_l4 else item["image"]).to(device=device, dtype=torch.float32)
+    rots = item["R"].to(device=device, dtype=torch.float32)
+    embed = (encoder_fn or model.forward_features) if uses_l4 else model
+    if proposals is None:
+        proposals = random_rotations(4096, generator=torch.Generator().manual_seed(0))
+    proposals = proposals.to(device)
+    order = [t for t in range(n) if t != ref]
+    R_map, score, err = [], [], []
+    for k, t in enumerate(order):
+        vol_src, vol_tgt = embed(frames[ref:ref + 1], frames[t:t + 1])
+        res = tracker.init(vol_src, vol_tgt, proposals) if k == 0 else tracker.step(vol_src, vol_tgt)
+        R_gt = rots[ref].transpose(0, 1) @ rots[t] if row_vector_R else rots[t] @ rots[ref].transpose(0, 1)
+        R_map.append(res.R_map[0].clone())          # (the tracker's outputs are buffers it reuses two steps later)
+        score.append(res.score[0].clone())
+        err.append(geodesic_deg(res.R_map, R_gt[None])[0])
+    if not order:
+        return {"frames": [], "R_map": torch.zeros(0, 3, 3), "score": torch.zeros(0), "err": torch.zeros(0)}
+    packed = torch.cat([torch.stack(R_map).reshape(-1, 9), torch.stack(score)[:, None], torch.stack(err)[:, None]], dim=1).cpu()
+    return {"frames": order, "R_map": packed[:, :9].reshape(-1, 3, 3), "score": packed[:, 9], "err": packed[:, 10]}
+
+
 def evaluate_pairwise(cfg, model, categories: Dict[str, Iterable[dict]], num_frames: int = 2, print_results=True,
                       **kw):
     """Counterpart of ``evaluate_pairwise`` (test_co3d.py:157-198)."""

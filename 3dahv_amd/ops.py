@@ -19,6 +19,7 @@ from __future__ import annotations
 import collections
 import contextvars
 import math
+import struct
 
 import torch
 
@@ -296,12 +297,14 @@ def score_plan(B: int, N: int, no_teams: bool = False, split_f16: bool = False, 
 def verify_pair(vol_src: torch.Tensor, vol_tgt: torch.Tensor, R: torch.Tensor, W1: torch.Tensor, W2: torch.Tensor,
                 b2: torch.Tensor, n_offset: int = 0, want_scores: bool = True, best_key: torch.Tensor | None = None,
                 reset_best: bool | None = None, split_f16: bool | None = None, want_feat_tgt: bool = False,
-                clock_stamps: torch.Tensor | None = None, no_teams: bool = False, spare_cus: int = 0):
+                clock_stamps: torch.Tensor | None = None, no_teams: bool = False, spare_cus: int = 0,
+                scores_out: torch.Tensor | None = None):
     """The whole per-pair verify step of test_co3d.py:137-145 behind ONE entry point (``ahv_verify_pair_f32``):
     ``forward_3d2d(vol_tgt)`` is built inside the scoring launch instead of in a launch of its own.  Arguments as
     ``score_hypotheses`` with the target VOLUME ``vol_tgt (B,16,8,8,8)`` in place of ``feat_tgt``.  Returns
     ``(scores (B,N) or None, best_key (B,) int64)`` and, with ``want_feat_tgt``, the target features ``(B,32,64)`` as
     third element (always materialised for the split-f16 kernel, which runs forward_3d2d as a launch of its own).
+    ``scores_out``: a contiguous float32 ``(B,N)`` tensor to write the scores to instead of a fresh one.
     Inference only (no autograd edge): with autograd recording and an input that requires grad it REFUSES (the check runs
     before the no_grad block -- as a decorator the block hid the recording state from the check, round 4) -- use
     ``forward_3d2d`` + ``score_hypotheses``, which carry the HIP backward."""
@@ -315,12 +318,12 @@ def verify_pair(vol_src: torch.Tensor, vol_tgt: torch.Tensor, R: torch.Tensor, W
             feat = torch.empty((vol_src.shape[0], 32, 64), dtype=torch.float32, device=vol_src.device)
         scores, key = _score_hypotheses_nograd(vol_src, vol_tgt, R, W1, W2, b2, n_offset, want_scores, best_key, reset_best,
                                                split, clock_stamps, no_teams=no_teams, spare_cus=spare_cus,
-                                               tgt_is_volume=True, feat_tgt_out=feat)
+                                               tgt_is_volume=True, feat_tgt_out=feat, scores_out=scores_out)
     return (scores, key, feat) if want_feat_tgt else (scores, key)
 
 
 def _score_hypotheses_nograd(vol_src, feat_tgt, R, W1, W2, b2, n_offset, want_scores, best_key, reset_best, split_f16,
-                             clock_stamps, no_teams=False, spare_cus=0, tgt_is_volume=False, feat_tgt_out=None):
+                             clock_stamps, no_teams=False, spare_cus=0, tgt_is_volume=False, feat_tgt_out=None, scores_out=None):
     if vol_src.dim() != 5 or tuple(vol_src.shape[1:]) != _VOL:
         raise RuntimeError("vol_src must be (B,16,8,8,8), got %s" % (tuple(vol_src.shape),))
     B = vol_src.shape[0]
@@ -335,7 +338,14 @@ def _score_hypotheses_nograd(vol_src, feat_tgt, R, W1, W2, b2, n_offset, want_sc
     dev = _need_gpu(vol_src, feat_tgt, R, W1, W2, b2)
     W1, W2, b2 = _head(W1, W2, b2)
     vs, ft, Rc = vol_src.detach().contiguous(), feat_tgt.detach().contiguous(), R.detach().contiguous()
-    scores = torch.empty((B, N), dtype=torch.float32, device=dev) if want_scores else None
+    scores = None
+    if want_scores and scores_out is not None:
+        if (scores_out.dtype != torch.float32 or tuple(scores_out.shape) != (B, N) or not scores_out.is_contiguous()
+                or scores_out.device != dev):
+            raise RuntimeError("scores_out must be a contiguous float32 (B,N) = %s tensor on %s" % ((B, N), dev))
+        scores = scores_out
+    elif want_scores:
+        scores = torch.empty((B, N), dtype=torch.float32, device=dev)
     if best_key is None:
         best_key = torch.empty((B,), dtype=torch.int64, device=dev)
         reset_best = True
@@ -570,18 +580,25 @@ def reset_best(best_key: torch.Tensor) -> torch.Tensor:
 
 
 @torch.no_grad()
-def select_rotation(best_key: torch.Tensor, R: torch.Tensor, n_offset: int = 0, reset_key: bool = False):
+def select_rotation(best_key: torch.Tensor, R: torch.Tensor, n_offset: int = 0, reset_key: bool = False, out=None):
     """(best_score (B,), best_idx (B,) global int64, R_pred (B,3,3)) in ONE launch:
     ``pred_sim, pred_index = torch.max(...)``; ``proposals[pred_index]`` (test_co3d.py:145-146).
-    ``reset_key``: hand ``best_key`` back EMPTY (AHV_SELECT_RESET_KEY), ready for the next step's scorer."""
+    ``reset_key``: hand ``best_key`` back EMPTY (AHV_SELECT_RESET_KEY), ready for the next step's scorer.
+    ``out``: ``(score, idx, R_pred)`` tensors of those shapes to write to (then nothing is allocated)."""
     B = best_key.numel()
     _need_gpu(R)
     N, rstride = _rot_layout(R, B)
     Rc = R.detach().contiguous()
     dev = Rc.device
-    score = torch.empty((B,), dtype=torch.float32, device=dev)
-    idx = torch.empty((B,), dtype=torch.int64, device=dev)
-    R_out = torch.empty((B, 3, 3), dtype=torch.float32, device=dev)
+    if out is not None:
+        score, idx, R_out = out
+        for t, dt, shape in ((score, torch.float32, (B,)), (idx, torch.int64, (B,)), (R_out, torch.float32, (B, 3, 3))):
+            if t.dtype != dt or tuple(t.shape) != shape or not t.is_contiguous() or t.device != dev:
+                raise RuntimeError("out must be (score (B,) float32, idx (B,) int64, R_pred (B,3,3) float32), contiguous, on %s" % dev)
+    else:
+        score = torch.empty((B,), dtype=torch.float32, device=dev)
+        idx = torch.empty((B,), dtype=torch.int64, device=dev)
+        R_out = torch.empty((B, 3, 3), dtype=torch.float32, device=dev)
     _call(dev, "ahv_select_rotation_f32", best_key.data_ptr(), Rc.data_ptr(), rstride, n_offset, N, B,
           R_out.data_ptr(), score.data_ptr(), idx.data_ptr(), _lib.AHV_SELECT_RESET_KEY if reset_key else 0)
     return score, idx, R_out
@@ -1089,6 +1106,122 @@ def verify_pair_resampled(vol_src: torch.Tensor, vol_tgt: torch.Tensor, R: torch
     s2, key2 = score_hypotheses(vol_src, f_tgt, R_fine, W1, W2, b2, want_scores=True)
     score, idx, R_pred = select_rotation(key2, R_fine)
     return ResampledVerify(score, idx, R_pred, draws, s2, R_fine, s1, key1)
+
+
+# ---- pose tracking ---------------------------------------------------------------------------------------------------
+# The two device pieces of a particle-filter step (``ahv_track_advance`` / ``ahv_diffuse_rotations_f32``, include/ahv.h):
+# advance -> ``resample`` (u) -> ``diffuse_rotations`` (reads the advanced counter) -> the scorer.  ``track.PoseTracker`` is the
+# filter built on them.
+
+def _step_counter(step, dev=None) -> torch.Tensor:
+    if not isinstance(step, torch.Tensor) or step.dtype != torch.int64 or step.numel() != 1:
+        raise RuntimeError("step must be an int64 tensor of ONE element on the device (it is read, and advanced, there)")
+    if not step.is_cuda:
+        raise RuntimeError("3dahv_amd ops run on the GPU only (no CPU fallback); got a tensor on %s" % step.device)
+    if dev is not None and step.device != dev:
+        raise RuntimeError("Expected all tensors to be on the same device, found %s and %s" % (dev, step.device))
+    return step
+
+
+def _angle_rad(deg, what: str, allow_none: bool = False) -> float:
+    """Degrees -> radians rounded to fp32 (what the entry point takes); finite and >= 0."""
+    if deg is None and allow_none:
+        return 0.0
+    d = float(deg)
+    if not (d >= 0.0 and math.isfinite(d)):
+        raise RuntimeError("%s = %r must be finite and >= 0" % (what, deg))
+    try:
+        return struct.unpack("f", struct.pack("f", math.radians(d)))[0]
+    except OverflowError:
+        raise RuntimeError("%s = %r does not fit a float32" % (what, deg)) from None
+
+
+@torch.no_grad()
+def track_advance(step: torch.Tensor, seed: int, batch: int, u: torch.Tensor | None = None) -> torch.Tensor:
+    """Start of a tracker step (``ahv_track_advance``, one tiny launch): reads ``t = step[0]`` ON THE DEVICE, writes the
+    resampling offsets ``u (batch,)`` float32 in [0, 1) -- a function of ``(seed, t + 1, b)`` -- and then ``step[0] = t + 1``.
+    ``step``: an int64 tensor of one element on the device.  Returns ``u`` (pass one to allocate nothing): it goes to
+    ``resample(..., u=u)`` as it is."""
+    step = _step_counter(step)
+    B = int(batch)
+    if not 1 <= B <= 65535:
+        raise RuntimeError("batch = %d outside 1..65535" % B)
+    dev = step.device
+    if u is None:
+        u = torch.empty((B,), dtype=torch.float32, device=dev)
+    elif (not isinstance(u, torch.Tensor) or u.dtype != torch.float32 or tuple(u.shape) != (B,) or not u.is_contiguous()
+          or u.device != dev):
+        raise RuntimeError("u must be a contiguous float32 tensor (B,) = (%d,) on %s" % (B, dev))
+    _call(dev, "ahv_track_advance", int(seed) & (2**64 - 1), step.data_ptr(), B, u.data_ptr())
+    return u
+
+
+@torch.no_grad()
+def diffuse_rotations(R: torch.Tensor, idx: torch.Tensor | None = None, m: int | None = None, sigma_deg: float = 3.0,
+                      step: torch.Tensor | None = None, seed: int = 0, best_key: torch.Tensor | None = None, n_fresh: int = 0,
+                      max_angle_deg: float | None = None, out: torch.Tensor | None = None, want_omega: bool = False,
+                      omega_out: torch.Tensor | None = None):
+    """Predict step of a particle filter (``ahv_diffuse_rotations_f32``, one launch): the next particle set ``(B,M,3,3)`` from
+    ``R (N,3,3)`` / ``(B,N,3,3)``.  Slot j of sample b is ``R[idx[b,j]] exp([w]x)`` with ``w = sigma z`` fresh Gaussian noise
+    (``idx (B,M)`` int64 from ``resample``; None: ``j mod N`` with ``m`` slots, default N), composed as unit quaternions and
+    normalised.  ``best_key (B,)`` given: slot 0 is the elite, ``R[decode(key)]`` bit for bit.  The last ``n_fresh`` slots are
+    fresh Haar rotations: ``random_rotations`` at seed ``seed ^ 0x9E3779B97F4A7C15`` and offset ``(step B + b) M + j``.
+    ``step``: the int64 device counter ``track_advance`` moves (read on the device: a replayed graph draws new noise); the noise
+    of a slot is a function of ``(seed, step, b, j)`` alone.  ``max_angle_deg``: ``|w|`` is clipped to it (None: no limit).
+    B comes from ``idx``, a per-sample ``R`` or ``best_key``, else 1.  ``want_omega``: also return ``w (B,M,3)`` as applied
+    (zeros in elite and fresh slots), into ``omega_out`` (float32 ``(B,M,3)``) when one is given.  ``out`` and ``omega_out``
+    must not overlap ``R``: a slot reads any row of it.  Returns ``out`` or ``(out, omega)``."""
+    _need_gpu(R)
+    dev = R.device
+    if step is None:
+        raise RuntimeError("step is required: an int64 tensor of ONE element on the device")
+    step = _step_counter(step, dev)
+    if idx is not None:
+        if not isinstance(idx, torch.Tensor) or idx.dim() != 2 or idx.dtype != torch.int64 or not idx.is_contiguous():
+            raise RuntimeError("idx must be a contiguous (B,M) int64 tensor")
+        if idx.device != dev:
+            raise RuntimeError("Expected all tensors to be on the same device, found %s and %s" % (dev, idx.device))
+        B = idx.shape[0]
+        if m is not None and int(m) != idx.shape[1]:
+            raise RuntimeError("m = %d disagrees with idx %s" % (int(m), tuple(idx.shape)))
+        M = idx.shape[1]
+    else:
+        B = R.shape[0] if R.dim() == 4 else (best_key.numel() if best_key is not None else 1)
+        M = None
+    N, rstride = _rot_layout(R, B)
+    if N < 1:
+        raise RuntimeError("R holds no rotation (N = 0)")
+    M = _draws((N if m is None else m) if M is None else M)
+    if not 1 <= B <= 65535:
+        raise RuntimeError("B = %d outside 1..65535" % B)
+    n_fresh = int(n_fresh)
+    if not 0 <= n_fresh <= M:
+        raise RuntimeError("n_fresh = %d outside 0..M = %d" % (n_fresh, M))
+    sigma = _angle_rad(sigma_deg, "sigma_deg")
+    max_angle = _angle_rad(max_angle_deg, "max_angle_deg", allow_none=True)
+    if best_key is not None and (not isinstance(best_key, torch.Tensor) or best_key.dtype != torch.int64
+                                 or best_key.numel() != B or best_key.device != dev or not best_key.is_contiguous()):
+        raise RuntimeError("best_key must be a contiguous int64 tensor of B = %d elements on %s" % (B, dev))
+    if out is None:
+        out = torch.empty((B, M, 3, 3), dtype=torch.float32, device=dev)
+    elif tuple(out.shape) != (B, M, 3, 3) or not out.is_contiguous() or out.dtype != torch.float32 or out.device != dev:
+        raise RuntimeError("out must be a contiguous float32 (B, M, 3, 3) = %s tensor on %s" % ((B, M, 3, 3), dev))
+    omega = omega_out
+    if omega is not None:
+        if (not isinstance(omega, torch.Tensor) or tuple(omega.shape) != (B, M, 3) or not omega.is_contiguous()
+                or omega.dtype != torch.float32 or omega.device != dev):
+            raise RuntimeError("omega_out must be a contiguous float32 (B, M, 3) = %s tensor on %s" % ((B, M, 3), dev))
+    elif want_omega:
+        omega = torch.empty((B, M, 3), dtype=torch.float32, device=dev)
+    Rc = R.detach().contiguous()
+    r_lo, r_hi = Rc.data_ptr(), Rc.data_ptr() + 4 * Rc.numel()
+    for name, t in (("out", out), ("omega_out", omega)):
+        if t is not None and t.data_ptr() < r_hi and r_lo < t.data_ptr() + 4 * t.numel():
+            raise RuntimeError("%s must not overlap R (a slot reads any row of R)" % name)
+    _call(dev, "ahv_diffuse_rotations_f32", idx.data_ptr() if idx is not None else None, Rc.data_ptr(), rstride, N,
+          best_key.data_ptr() if best_key is not None else None, M, n_fresh, B, int(seed) & (2**64 - 1), step.data_ptr(), sigma,
+          max_angle, out.data_ptr(), omega.data_ptr() if omega is not None else None)
+    return (out, omega) if omega is not None else out
 
 
 # ---- multi-view verification ---------------------------------------------------------------------------------------

@@ -1,0 +1,199 @@
+"""Pose tracking over a frame sequence: a particle filter on SO(3) whose step stays on the device.
+
+Build-defined: the reference scores every image pair from scratch against 50 000 random rotations (test_co3d.py:106,137-146).
+A video is frame after frame of one object, so the pose posterior of one frame is the prior of the next.  ``PoseTracker`` keeps
+M pose particles per sample.  Per frame it
+
+1. ``track_advance``       moves the device step counter and draws the resampling offsets ``u``,
+2. ``resample``            draws M particles in proportion to the previous frame's posterior (systematic draws),
+3. ``diffuse_rotations``   moves each by a small random rotation (fresh noise generated on the device from the counter), keeps
+                           the previous arg-max untouched in slot 0 (the elite) and fills the last ``n_fresh`` slots with new
+                           Haar rotations (re-acquisition after a lost track),
+4. ``verify_pair``         scores the set against the new frame (the fused scorer, scores kept),
+5. ``select_rotation``     reports the MAP pose,
+
+and with ``posterior=True`` ``pose_posterior`` with the MAP pose as the single anchor: the mass within ``mode_angle_deg`` of it,
+the mean pose, the spread and the entropy.  Everything between two frames is device memory the tracker owns; the trajectory is a
+function of (seed, inputs) alone.
+
+One rank: a particle set is a few hundred to a few thousand rotations, there is nothing to shard.  With an initialised process
+group every rank runs the same tracker on the same inputs and computes the same bytes; no collective is issued.
+Not built: a motion model (constant velocity -- the predict step is a random walk), sigma adapted from the entropy, and the
+tracker inside the multi-view path (``ops.verify_views``).
+"""
+from __future__ import annotations
+
+import collections
+from typing import Optional
+
+import torch
+
+from . import ops
+from .dist import KEY_EMPTY
+
+TrackStep = collections.namedtuple(
+    "TrackStep", ["score", "idx", "R_map", "particles", "scores", "draws", "R_mean", "spread_deg", "mode_mass", "entropy",
+                  "reacquired"])
+
+
+class PoseTracker:
+    """``backend`` provides ``track_advance, resample, diffuse_rotations, verify_pair, select_rotation`` (and ``pose_posterior``
+    with ``posterior=True``) with the signatures of ``3dahv_amd.ops`` -- the default and the only product backend: HIP kernels,
+    no CPU path; CPU tests inject an oracle-backed object to execute the control flow.
+
+    ``init(vol_src, vol_tgt, R_init)`` scores the hypotheses ``R_init (N0,3,3)`` / ``(B,N0,3,3)`` (eagerly); they, with their
+    scores, are the particle set the first step draws from.  ``step(vol_src, vol_tgt)`` is the sequence of the module
+    docstring: ``vol_src`` is the reference view's volume, ``vol_tgt`` the frame's.  Both return a ``TrackStep``: ``score (B,)``,
+    ``idx (B,)`` (the winner's slot) and ``R_map (B,3,3)``; ``particles (B,M,3,3)``, ``scores (B,M)`` and ``draws (B,M)`` (the
+    previous set's indices the slots were drawn from; None for ``init``); with ``posterior``: ``R_mean (B,3,3)``, ``spread_deg``,
+    ``mode_mass`` and ``entropy`` (B,), else None; ``reacquired (B,)`` bool, true when the winner sits in a fresh slot.
+
+    The tracker owns every buffer of a step, ping-pong: two particle sets, two score rows, two keys, two output sets, the draw
+    list, the workspaces, ``u`` and the step counter.  A step reads one half and writes the other, so a ``TrackStep`` stays
+    valid until the step after the next one.  After the first step a step allocates nothing (``posterior=True``: the
+    ``pose_posterior`` outputs are that op's own).
+    Slot 0 carries the previous arg-max bit for bit and a score is a function of (volumes, weights, R) alone, so on an
+    unchanged frame the reported score never decreases.
+
+    ``use_graph=True`` (HIP backend only; refused with a ``backend`` or on the CPU): the first step after ``init`` reads the N0-sized set and runs eagerly; the two halves of
+    the ping-pong are then captured as one hipGraph each, by the second and the third step, and every later step replays the
+    graph of its half.  Each graph is the linear chain of the step's launches.  The two capturing steps synchronise with the
+    host (a capture starts from an idle device); no other step does.  The step counter lives on the device and is
+    moved there, so a replay draws new noise.  The static input volumes are ``.buffers``: write the frame's volumes there and
+    call ``step()`` with no arguments to replay with no staging copy."""
+
+    def __init__(self, W1: torch.Tensor, W2: torch.Tensor, b2: torch.Tensor, particles: int, sigma_deg: float = 3.0,
+                 n_fresh: int = 0, temperature: float = 0.02, max_angle_deg: Optional[float] = None, batch: int = 1,
+                 seed: int = 0, posterior: bool = False, mode_angle_deg: float = 15.0, use_graph: bool = False, backend=None):
+        dev = W1.device
+        self.ops = ops if backend is None else backend
+        self.W1, self.W2, self.b2 = W1, W2, b2
+        self.M, self.B = int(particles), int(batch)
+        if not 1 <= self.M < (1 << 31):
+            raise RuntimeError("particles = %d outside 1..2^31-1" % self.M)
+        if not 1 <= self.B <= 65535:
+            raise RuntimeError("batch = %d outside 1..65535" % self.B)
+        self.n_fresh = int(n_fresh)
+        if not 0 <= self.n_fresh <= self.M:
+            raise RuntimeError("n_fresh = %d outside 0..particles = %d" % (self.n_fresh, self.M))
+        self.sigma_deg = float(sigma_deg)
+        self.max_angle_deg = None if max_angle_deg is None else float(max_angle_deg)
+        ops._angle_rad(self.sigma_deg, "sigma_deg")   # raises unless finite and >= 0
+        ops._angle_rad(self.max_angle_deg, "max_angle_deg", allow_none=True)
+        self.temperature = float(temperature)
+        ops.inverse_temperature(self.temperature)     # raises unless finite and > 0
+        self.seed = int(seed)
+        self.posterior = bool(posterior)
+        self.mode_angle_deg = float(mode_angle_deg)
+        if self.posterior:
+            ops.min_trace(self.mode_angle_deg)        # raises outside (0, 180)
+        hip = backend is None and dev.type == "cuda"
+        if use_graph and not hip:
+            raise RuntimeError("use_graph=True needs the HIP backend on a GPU (backend=None, weights on the device)")
+        self.use_graph = bool(use_graph)
+        B, M = self.B, self.M
+        f = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)
+        self._R = [f(B, M, 3, 3) for _ in range(2)]
+        self._scores = [f(B, M) for _ in range(2)]
+        self._keys = [torch.full((B,), KEY_EMPTY, dtype=torch.int64, device=dev) for _ in range(2)]
+        self._sel = [(f(B), torch.empty((B,), dtype=torch.int64, device=dev), f(B, 3, 3)) for _ in range(2)]
+        self._reacq = [torch.zeros((B,), dtype=torch.bool, device=dev) for _ in range(2)]
+        self._draws = torch.full((B, M), -1, dtype=torch.int64, device=dev)
+        self._u = f(B)
+        self._step = torch.zeros((1,), dtype=torch.int64, device=dev)
+        self._ws = ops.resample_workspace(B, M, dev) if hip else None      # steady state: draws from an M-sized set
+        self._ws0 = None                                                   # first step: draws from the N0-sized set
+        self._pstate = ops.pose_posterior_state(B, 1, dev) if hip and self.posterior else None
+        self._pws = ops.pose_posterior_workspace(B, M, 1, dev) if hip and self.posterior else None
+        self._cur = None      # (R, scores, key) of the set the next step draws from
+        self._n = 0           # steps since init
+        self._static = None
+        self._graphs = {}     # half of the ping-pong -> (captured graph, its TrackStep)
+
+    @property
+    def buffers(self):
+        """The static input volumes ``(vol_src, vol_tgt)`` of the captured step (allocated on first use)."""
+        if self._static is None:
+            self._static = tuple(torch.zeros((self.B, 16, 8, 8, 8), dtype=torch.float32, device=self.W1.device) for _ in range(2))
+        return self._static
+
+    @property
+    def step_counter(self) -> torch.Tensor:
+        """The int64 device counter (one element): 0 after ``init``, moved by one per step ON THE DEVICE."""
+        return self._step
+
+    def _posterior(self, scores, R, R_map, state=None, workspace=None):
+        if not self.posterior:
+            return None, None, None, None
+        p = self.ops.pose_posterior(scores, R, self.temperature, anchors=R_map[:, None], min_angle_deg=self.mode_angle_deg,
+                                    state=state, workspace=workspace, reset=True if state is not None else None)
+        return p.R_mean, p.spread_deg, p.mode_prob[:, 0], p.entropy
+
+    @torch.no_grad()
+    def init(self, vol_src: torch.Tensor, vol_tgt: torch.Tensor, R_init: torch.Tensor) -> TrackStep:
+        """Score ``R_init (N0,3,3)`` / ``(B,N0,3,3)`` on the pair: the set, with its scores, that the first step draws from.
+        Restarts the step counter at 0, so a trajectory is a function of (seed, inputs)."""
+        o = self.ops
+        if R_init.dim() not in (3, 4) or tuple(R_init.shape[-2:]) != (3, 3) or (R_init.dim() == 4 and R_init.shape[0] != self.B):
+            raise RuntimeError("R_init must be (N0,3,3) or (B,N0,3,3) with B = %d, got %s" % (self.B, tuple(R_init.shape)))
+        if vol_src.shape[0] != self.B:
+            raise RuntimeError("the tracker was built for batch = %d, got volumes %s" % (self.B, tuple(vol_src.shape)))
+        R0 = R_init.detach().clone(memory_format=torch.contiguous_format)   # the first step reads it: keep a copy of our own
+        scores, key = o.verify_pair(vol_src, vol_tgt, R0, self.W1, self.W2, self.b2, want_scores=True)
+        score, idx, R_map = o.select_rotation(key, R0)
+        n0 = R0.shape[-3]
+        if self.ops is ops and R0.is_cuda and (self._ws0 is None or self._ws0_n != n0):
+            self._ws0, self._ws0_n = ops.resample_workspace(self.B, n0, R0.device), n0
+        self._step.zero_()
+        self._cur, self._n = (R0, scores, key), 0
+        post = self._posterior(scores, R0, R_map)
+        return TrackStep(score, idx, R_map, R0, scores, None, *post, torch.zeros_like(idx, dtype=torch.bool))
+
+    def _run(self, vol_src, vol_tgt, p: int) -> TrackStep:
+        """One step into half ``p`` of the buffers; runs eagerly or under capture."""
+        o = self.ops
+        R_prev, s_prev, key_prev = self._cur
+        ws = self._ws if R_prev.shape[-3] == self.M and R_prev is self._R[1 - p] else self._ws0
+        u = o.track_advance(self._step, self.seed, self.B, u=self._u)
+        draws = o.resample(s_prev, self.M, self.temperature, u=u, out=self._draws, workspace=ws)
+        R = o.diffuse_rotations(R_prev, idx=draws, sigma_deg=self.sigma_deg, step=self._step, seed=self.seed, best_key=key_prev,
+                                n_fresh=self.n_fresh, max_angle_deg=self.max_angle_deg, out=self._R[p])
+        scores, key = o.verify_pair(vol_src, vol_tgt, R, self.W1, self.W2, self.b2, want_scores=True, best_key=self._keys[p],
+                                    reset_best=True, scores_out=self._scores[p])
+        score, idx, R_map = o.select_rotation(key, R, out=self._sel[p])
+        # the winner sits in a fresh slot (slot 0 is the elite even when every slot is fresh)
+        reacq = torch.ge(idx, max(self.M - self.n_fresh, 1), out=self._reacq[p])
+        post = self._posterior(scores, R, R_map, self._pstate, self._pws)
+        return TrackStep(score, idx, R_map, R, scores, draws, *post, reacq)
+
+    @torch.no_grad()
+    def step(self, vol_src: Optional[torch.Tensor] = None, vol_tgt: Optional[torch.Tensor] = None) -> TrackStep:
+        """Advance the filter by one frame.  Called with no volumes it runs on ``self.buffers`` as they are."""
+        if self._cur is None:
+            raise RuntimeError("call init(vol_src, vol_tgt, R_init) before the first step")
+        if (vol_src is None) != (vol_tgt is None):
+            raise RuntimeError("pass both volumes or neither")
+        n = self._n + 1
+        p = n & 1
+        if not self.use_graph or n == 1:
+            if vol_src is None:
+                vol_src, vol_tgt = self.buffers
+            out = self._run(vol_src, vol_tgt, p)
+        else:
+            static = self.buffers
+            if vol_src is not None and vol_src.data_ptr() != static[0].data_ptr():
+                static[0].copy_(vol_src)
+            if vol_tgt is not None and vol_tgt.data_ptr() != static[1].data_ptr():
+                static[1].copy_(vol_tgt)
+            if p not in self._graphs:
+                # No warm-up run: the eager first step has issued every launch of the chain once, and a warm-up here would
+                # move the filter (the counter, the sets).  Capture records the step; the replay below runs it.
+                torch.cuda.synchronize()
+                graph = torch.cuda.CUDAGraph()
+                with torch.cuda.graph(graph):
+                    captured = self._run(static[0], static[1], p)
+                self._graphs[p] = (graph, captured)
+            graph, out = self._graphs[p]
+            graph.replay()
+        self._cur, self._n = (self._R[p], self._scores[p], self._keys[p]), n
+        return out
