@@ -122,6 +122,10 @@ SIGNATURES["ahv_compose_rotations_indexed_f32"] = (_int, [_vp, _vp, _i64, _i64, 
 #  omega or NULL, stream)
 SIGNATURES["ahv_diffuse_rotations_f32"] = (_int, [_vp, _vp, _i64, _i64, _vp, _i64, _i64, _int, ctypes.c_uint64, _vp, ctypes.c_float,
                                                   ctypes.c_float, _vp, _vp, _vp])
+# (idx or NULL, R, r_batch_stride, V or NULL, v_batch_stride, N, best_key or NULL, M, n_fresh, B, seed, step: DEVICE int64,
+#  sigma_rad, sigma_vel_rad, damping, max_angle_rad, max_speed_rad, coast, out, vel_out, omega or NULL, stream)
+SIGNATURES["ahv_predict_rotations_f32"] = (_int, [_vp, _vp, _i64, _vp, _i64, _i64, _vp, _i64, _i64, _int, ctypes.c_uint64, _vp]
+                                           + [ctypes.c_float] * 5 + [_int, _vp, _vp, _vp, _vp])
 # (seed, step: DEVICE int64, B, u: DEVICE floats, stream)
 SIGNATURES["ahv_track_advance"] = (_int, [ctypes.c_uint64, _vp, _int, _vp, _vp])
 

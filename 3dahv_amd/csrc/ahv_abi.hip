@@ -54,6 +54,9 @@ hipError_t launch_random_rotations(uint64_t, uint64_t, int64_t, float*, hipStrea
 hipError_t launch_so3_grid(int64_t, int64_t, int64_t, float*, hipStream_t);
 hipError_t launch_diffuse_rotations(const int64_t*, const float*, int64_t, int64_t, const int64_t*, int64_t, int64_t, int, uint64_t,
                                     const int64_t*, float, float, float*, float*, hipStream_t);
+hipError_t launch_predict_rotations(const int64_t*, const float*, int64_t, const float*, int64_t, int64_t, const int64_t*, int64_t,
+                                    int64_t, int, uint64_t, const int64_t*, float, float, float, float, float, int, float*, float*,
+                                    float*, hipStream_t);
 hipError_t launch_track_advance(uint64_t, int64_t*, int, float*, hipStream_t);
 hipError_t launch_score_backward(const float*, const float*, const float*, int64_t, const float*, const float*,
                                  const float*, int, int64_t, const float*, float*, float*, float*, float*, float*,
@@ -971,6 +974,39 @@ int ahv_diffuse_rotations_f32(const int64_t* idx, const float* R, int64_t r_batc
     hipError_t e = ahv::launch_diffuse_rotations(idx, R, r_batch_stride, N, best_key, M, n_fresh, B, seed, step, sigma_rad,
                                                  max_angle_rad, out, omega, static_cast<hipStream_t>(stream));
     if (e != hipSuccess) return hip_fail("diffuse_rotations: launch", e);
+    return AHV_OK;
+}
+
+int ahv_predict_rotations_f32(const int64_t* idx, const float* R, int64_t r_batch_stride, const float* V, int64_t v_batch_stride,
+                              int64_t N, const int64_t* best_key, int64_t M, int64_t n_fresh, int B, uint64_t seed,
+                              const int64_t* step, float sigma_rad, float sigma_vel_rad, float damping, float max_angle_rad,
+                              float max_speed_rad, int coast, float* out, float* vel_out, float* omega, void* stream)
+{
+    const auto angle = [](float a) { return a >= 0.0f && a < __builtin_inff(); };
+    if (!R || !out || !vel_out || !step)
+        return fail(AHV_EINVAL, "predict_rotations: null pointer (R, out, vel_out and step are required)");
+    if (M < 1 || M >= (int64_t)1 << 31) return fail(AHV_EINVAL, "predict_rotations: M = %lld outside 1..2^31-1", (long long)M);
+    if (N < 1) return fail(AHV_EINVAL, "predict_rotations: empty rotation set (N = %lld)", (long long)N);
+    if (n_fresh < 0 || n_fresh > M)
+        return fail(AHV_EINVAL, "predict_rotations: n_fresh = %lld outside 0..M = %lld", (long long)n_fresh, (long long)M);
+    if (B < 1 || B > 65535) return fail(AHV_EINVAL, "predict_rotations: B = %d outside 1..65535", B);
+    if (r_batch_stride != 0 && r_batch_stride != N * 9)
+        return fail(AHV_EINVAL, "predict_rotations: r_batch_stride %lld must be 0 or N*9", (long long)r_batch_stride);
+    if (v_batch_stride != 0 && v_batch_stride != N * 3)
+        return fail(AHV_EINVAL, "predict_rotations: v_batch_stride %lld must be 0 or N*3", (long long)v_batch_stride);
+    if (!angle(sigma_rad)) return fail(AHV_EINVAL, "predict_rotations: sigma = %g must be finite and >= 0", (double)sigma_rad);
+    if (!angle(sigma_vel_rad))
+        return fail(AHV_EINVAL, "predict_rotations: sigma_vel = %g must be finite and >= 0", (double)sigma_vel_rad);
+    if (!(damping >= 0.0f && damping <= 1.0f))
+        return fail(AHV_EINVAL, "predict_rotations: damping = %g outside [0, 1]", (double)damping);
+    if (!angle(max_angle_rad))
+        return fail(AHV_EINVAL, "predict_rotations: max_angle = %g must be finite and >= 0 (0: no limit)", (double)max_angle_rad);
+    if (!angle(max_speed_rad))
+        return fail(AHV_EINVAL, "predict_rotations: max_speed = %g must be finite and >= 0 (0: no limit)", (double)max_speed_rad);
+    hipError_t e = ahv::launch_predict_rotations(idx, R, r_batch_stride, V, v_batch_stride, N, best_key, M, n_fresh, B, seed, step,
+                                                 sigma_rad, sigma_vel_rad, damping, max_angle_rad, max_speed_rad, coast != 0, out,
+                                                 vel_out, omega, static_cast<hipStream_t>(stream));
+    if (e != hipSuccess) return hip_fail("predict_rotations: launch", e);
     return AHV_OK;
 }
 

@@ -668,6 +668,130 @@ __global__ __launch_bounds__(256) void diffuse_rotations_kernel(const long long*
     }
 }
 
+// ---------------------------------------------------------------------------------
+// Constant-velocity predict step (ahv_predict_rotations_f32, include/ahv.h): a particle is (R, v), v its body-frame rotation
+// vector per frame.  One thread per slot (b, j), as diffuse_rotations_kernel; slot classes in this precedence:
+//   elite  j == 0 with a key: R and v of row decode(key_b) copied bit for bit
+//   coast  j == 1 with a key and `coast`: R_n exp([v_n]x), no noise -- the constant-velocity prediction of the previous arg-max
+//   fresh  j >= M - n_fresh: the Haar rotation diffuse_rotations_kernel writes for the same (seed, step, b, j), v = 0
+//   else   v' = damping v_i + sigma_vel y (clipped to max_speed), w = v' + sigma z (the second term clipped to max_angle),
+//          out = R_i exp([w]x) composed as unit quaternions and normalised, exactly as diffuse_rotations_kernel does
+// z is the block diffuse_rotations_kernel draws (third counter word kDiffuseTag), y a second block (kVelocityTag).
+// The composition is a copy of diffuse_rotations_kernel's on purpose: that kernel's instructions are pinned, so
+// nothing is factored out of it.
+// ---------------------------------------------------------------------------------
+constexpr unsigned kVelocityTag = 0x56454Cu;
+
+// Scales (x, y, z) so that its norm is <= limit (limit > 0; 0 means no limit) and returns the norm of the result.  2^-21 of
+// room on both sides of the comparison: the rounded vector's exact norm stays <= limit.  A NaN norm is left alone.
+__device__ __forceinline__ float clip_norm(float& x, float& y, float& z, float limit)
+{
+    float a = sqrtf(x * x + y * y + z * z);
+    if (limit > 0.0f && a * 1.00000048f > limit) {
+        const float s = (limit / a) * 0.99999952f;
+        x *= s; y *= s; z *= s;
+        a = sqrtf(x * x + y * y + z * z);
+    }
+    return a;
+}
+
+__global__ __launch_bounds__(256) void predict_rotations_kernel(const long long* __restrict__ idx, const float* __restrict__ R,
+                                                                long r_batch_stride, const float* __restrict__ V,
+                                                                long v_batch_stride, long N, const key_t* __restrict__ best_key,
+                                                                long M, long n_fresh, unsigned long long seed,
+                                                                const long long* __restrict__ step, float sigma, float sigma_vel,
+                                                                float damping, float max_angle, float max_speed, int coast,
+                                                                float* __restrict__ out, float* __restrict__ vel_out,
+                                                                float* __restrict__ omega)
+{
+    const long j = (long)blockIdx.x * 256 + threadIdx.x;
+    if (j >= M) return;
+    const long b = blockIdx.y;
+    const unsigned long long t = (unsigned long long)*step;
+    const long i = b * M + j;
+    float* o = out + i * 9;
+    float w0 = 0.0f, w1 = 0.0f, w2 = 0.0f, v0 = 0.0f, v1 = 0.0f, v2 = 0.0f;
+    const bool elite = best_key && j == 0, coasting = best_key && j == 1 && coast;
+    if (!elite && !coasting && j >= M - n_fresh) {
+        haar_rotation(seed ^ kFreshSeed, (t * (unsigned long long)gridDim.y + (unsigned long long)b) * (unsigned long long)M + (unsigned long long)j, o);
+    } else {
+        long n;
+        if (elite || coasting) {
+            const key_t key = best_key[b];
+            n = key_index(key);
+            n = (key == kKeyEmpty || n < 0 || n >= N) ? 0 : n;  // as diffuse_rotations_kernel: stay in bounds
+        } else {
+            n = idx ? (long)idx[i] : j % N;
+            n = (n < 0 || n >= N) ? 0 : n;
+        }
+        const float* r = R + b * r_batch_stride + n * 9;
+        if (V) {
+            const float* v = V + b * v_batch_stride + n * 3;
+            v0 = v[0]; v1 = v[1]; v2 = v[2];
+        }
+        if (elite) {
+#pragma unroll
+            for (int k = 0; k < 9; ++k) o[k] = r[k];
+        } else {
+            const float r00 = r[0], r01 = r[1], r02 = r[2], r10 = r[3], r11 = r[4], r12 = r[5], r20 = r[6], r21 = r[7], r22 = r[8];
+            if (coasting) {
+                w0 = v0; w1 = v1; w2 = v2;
+            } else {
+                const unsigned cb = (unsigned)b | ((unsigned)(t >> 32) << 16);
+                unsigned c[4] = {(unsigned)j, cb, kVelocityTag, (unsigned)t};
+                philox4x32_10(c, (unsigned)seed, (unsigned)(seed >> 32));
+                float y0, y1, y2, y3;
+                box_muller4(c, y0, y1, y2, y3);
+                v0 = fmaf(damping, v0, sigma_vel * y0); v1 = fmaf(damping, v1, sigma_vel * y1); v2 = fmaf(damping, v2, sigma_vel * y2);
+                clip_norm(v0, v1, v2, max_speed);
+                c[0] = (unsigned)j; c[1] = cb; c[2] = kDiffuseTag; c[3] = (unsigned)t;
+                philox4x32_10(c, (unsigned)seed, (unsigned)(seed >> 32));
+                float z0, z1, z2, z3;
+                box_muller4(c, z0, z1, z2, z3);
+                float p0 = sigma * z0, p1 = sigma * z1, p2 = sigma * z2;
+                clip_norm(p0, p1, p2, max_angle);
+                w0 = v0 + p0; w1 = v1 + p1; w2 = v2 + p2;
+            }
+            const float a = sqrtf(w0 * w0 + w1 * w1 + w2 * w2);
+            // q(w) = (cos a/2, sin(a/2) w / a); sin(a/2) / a -> 1/2 - a^2/48 as a -> 0
+            float sh, ch;
+            sincosf(0.5f * a, &sh, &ch);
+            const float kq = a < 1e-3f ? 0.5f - a * a * (1.0f / 48.0f) : sh / a;
+            const float dr = ch, di = kq * w0, dj = kq * w1, dk = kq * w2;
+            // q(R) by Shepperd's branch: divide by the largest of the four components
+            float qr, qi, qj, qk;
+            const float tr = r00 + r11 + r22;
+            if (tr > 0.0f) {
+                const float s = 2.0f * sqrtf(tr + 1.0f);
+                qr = 0.25f * s; qi = (r21 - r12) / s; qj = (r02 - r20) / s; qk = (r10 - r01) / s;
+            } else if (r00 > r11 && r00 > r22) {
+                const float s = 2.0f * sqrtf(1.0f + r00 - r11 - r22);
+                qr = (r21 - r12) / s; qi = 0.25f * s; qj = (r01 + r10) / s; qk = (r02 + r20) / s;
+            } else if (r11 > r22) {
+                const float s = 2.0f * sqrtf(1.0f + r11 - r00 - r22);
+                qr = (r02 - r20) / s; qi = (r01 + r10) / s; qj = 0.25f * s; qk = (r12 + r21) / s;
+            } else {
+                const float s = 2.0f * sqrtf(1.0f + r22 - r00 - r11);
+                qr = (r10 - r01) / s; qi = (r02 + r20) / s; qj = (r12 + r21) / s; qk = 0.25f * s;
+            }
+            // Hamilton product q(R) q(w): the matrix of a product is the product of the matrices, R exp([w]x)
+            float pr = qr * dr - qi * di - qj * dj - qk * dk;
+            float pi = qr * di + qi * dr + qj * dk - qk * dj;
+            float pj = qr * dj - qi * dk + qj * dr + qk * di;
+            float pk = qr * dk + qi * dj - qj * di + qk * dr;
+            const float inv = 1.0f / sqrtf(fmaxf(pr * pr + pi * pi + pj * pj + pk * pk, 1e-30f));
+            pr *= inv; pi *= inv; pj *= inv; pk *= inv;
+            quaternion_matrix(pr, pi, pj, pk, o);
+        }
+    }
+    float* vo = vel_out + i * 3;
+    vo[0] = v0; vo[1] = v1; vo[2] = v2;
+    if (omega) {
+        float* w = omega + i * 3;
+        w[0] = w0; w[1] = w1; w[2] = w2;
+    }
+}
+
 // Start of a tracker step (ahv_track_advance): u[b] of step t + 1, then the counter itself.  One workgroup: the barrier
 // orders every read of *step before the one write.
 __global__ __launch_bounds__(256) void track_advance_kernel(unsigned long long seed, long long* step, int B, float* __restrict__ u)
@@ -796,6 +920,20 @@ hipError_t launch_diffuse_rotations(const int64_t* idx, const float* R, int64_t 
                        reinterpret_cast<const long long*>(idx), R, (long)r_batch_stride, (long)N,
                        reinterpret_cast<const key_t*>(best_key), (long)M, (long)n_fresh, (unsigned long long)seed,
                        reinterpret_cast<const long long*>(step), sigma, max_angle, out, omega);
+    return hipGetLastError();
+}
+
+hipError_t launch_predict_rotations(const int64_t* idx, const float* R, int64_t r_batch_stride, const float* V,
+                                    int64_t v_batch_stride, int64_t N, const int64_t* best_key, int64_t M, int64_t n_fresh, int B,
+                                    uint64_t seed, const int64_t* step, float sigma, float sigma_vel, float damping,
+                                    float max_angle, float max_speed, int coast, float* out, float* vel_out, float* omega,
+                                    hipStream_t stream)
+{
+    hipLaunchKernelGGL(predict_rotations_kernel, dim3((unsigned)((M + 255) / 256), (unsigned)B), dim3(256), 0, stream,
+                       reinterpret_cast<const long long*>(idx), R, (long)r_batch_stride, V, (long)v_batch_stride, (long)N,
+                       reinterpret_cast<const key_t*>(best_key), (long)M, (long)n_fresh, (unsigned long long)seed,
+                       reinterpret_cast<const long long*>(step), sigma, sigma_vel, damping, max_angle, max_speed, coast, out,
+                       vel_out, omega);
     return hipGetLastError();
 }
 

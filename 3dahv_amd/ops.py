@@ -1224,6 +1224,105 @@ def diffuse_rotations(R: torch.Tensor, idx: torch.Tensor | None = None, m: int |
     return (out, omega) if omega is not None else out
 
 
+def _unit_interval(x, what: str) -> float:
+    d = float(x)
+    if not 0.0 <= d <= 1.0:      # (false for NaN)
+        raise RuntimeError("%s = %r must lie in [0, 1]" % (what, x))
+    return d
+
+
+@torch.no_grad()
+def predict_rotations(R: torch.Tensor, V: torch.Tensor | None = None, idx: torch.Tensor | None = None, m: int | None = None,
+                      sigma_deg: float = 3.0, sigma_vel_deg: float = 1.0, damping: float = 1.0, step: torch.Tensor | None = None,
+                      seed: int = 0, best_key: torch.Tensor | None = None, coast: bool = True, n_fresh: int = 0,
+                      max_angle_deg: float | None = None, max_speed_deg: float | None = None, out: torch.Tensor | None = None,
+                      vel_out: torch.Tensor | None = None, want_omega: bool = False, omega_out: torch.Tensor | None = None):
+    """Predict step with a constant-velocity motion model (``ahv_predict_rotations_f32``, one launch).  A particle is ``(R, v)``,
+    ``v`` its body-frame rotation vector per frame: ``V (N,3)`` / ``(B,N,3)`` float32, or None for all zeros (a freshly scored
+    set).  Slot j of sample b, with ``i = idx[b,j]``: ``v' = damping v_i + sigma_vel y`` (``|v'|`` clipped to ``max_speed_deg``),
+    ``R_out = R_i exp([v' + w]x)`` with ``w = sigma z`` the noise ``diffuse_rotations`` draws for the same ``(seed, step, b, j)``
+    (clipped to ``max_angle_deg``) and ``y`` a second, independent draw; composed as unit quaternions and normalised.
+    ``best_key (B,)`` given: slot 0 is the elite, ``R`` and ``v`` of row ``decode(key)`` bit for bit, and with ``coast`` slot 1 is
+    that row moved by its own velocity with no noise, ``R_n exp([v_n]x)``.  The last ``n_fresh`` slots are the Haar rotations
+    ``diffuse_rotations`` writes there, with zero velocity.  Other arguments as ``diffuse_rotations``; B comes from ``idx``, a
+    per-sample ``R`` or ``V``, or ``best_key``, else 1.  ``out`` / ``omega_out`` must not overlap ``R`` and ``vel_out`` must not
+    overlap ``V``.  Returns ``(R_out (B,M,3,3), V_out (B,M,3))``, with ``want_omega`` / ``omega_out`` also the total rotation
+    vector applied ``(B,M,3)`` (``v' + w``; ``v_n`` in the coast slot, zeros in elite and fresh slots)."""
+    _need_gpu(R)
+    dev = R.device
+    if step is None:
+        raise RuntimeError("step is required: an int64 tensor of ONE element on the device")
+    step = _step_counter(step, dev)
+    if V is not None:
+        if not isinstance(V, torch.Tensor) or V.dim() not in (2, 3) or V.shape[-1] != 3:
+            raise RuntimeError("V must be (N,3) or (B,N,3), got %s" % (tuple(V.shape) if isinstance(V, torch.Tensor) else type(V),))
+        _need_gpu(R, V)
+    if idx is not None:
+        if not isinstance(idx, torch.Tensor) or idx.dim() != 2 or idx.dtype != torch.int64 or not idx.is_contiguous():
+            raise RuntimeError("idx must be a contiguous (B,M) int64 tensor")
+        if idx.device != dev:
+            raise RuntimeError("Expected all tensors to be on the same device, found %s and %s" % (dev, idx.device))
+        B = idx.shape[0]
+        if m is not None and int(m) != idx.shape[1]:
+            raise RuntimeError("m = %d disagrees with idx %s" % (int(m), tuple(idx.shape)))
+        M = idx.shape[1]
+    else:
+        B = (R.shape[0] if R.dim() == 4 else V.shape[0] if V is not None and V.dim() == 3
+             else best_key.numel() if best_key is not None else 1)
+        M = None
+    N, rstride = _rot_layout(R, B)
+    if N < 1:
+        raise RuntimeError("R holds no rotation (N = 0)")
+    vstride = 0
+    if V is not None:
+        if tuple(V.shape) == (B, N, 3):
+            vstride = 3 * N
+        elif tuple(V.shape) != (N, 3):
+            raise RuntimeError("V must be (N,3) or (B,N,3) with B = %d, N = %d, got %s" % (B, N, tuple(V.shape)))
+    M = _draws((N if m is None else m) if M is None else M)
+    if not 1 <= B <= 65535:
+        raise RuntimeError("B = %d outside 1..65535" % B)
+    n_fresh = int(n_fresh)
+    if not 0 <= n_fresh <= M:
+        raise RuntimeError("n_fresh = %d outside 0..M = %d" % (n_fresh, M))
+    sigma = _angle_rad(sigma_deg, "sigma_deg")
+    sigma_vel = _angle_rad(sigma_vel_deg, "sigma_vel_deg")
+    damping = _unit_interval(damping, "damping")
+    max_angle = _angle_rad(max_angle_deg, "max_angle_deg", allow_none=True)
+    max_speed = _angle_rad(max_speed_deg, "max_speed_deg", allow_none=True)
+    if best_key is not None and (not isinstance(best_key, torch.Tensor) or best_key.dtype != torch.int64
+                                 or best_key.numel() != B or best_key.device != dev or not best_key.is_contiguous()):
+        raise RuntimeError("best_key must be a contiguous int64 tensor of B = %d elements on %s" % (B, dev))
+
+    def _output(t, name, shape, wanted=True):
+        if t is None:
+            return torch.empty(shape, dtype=torch.float32, device=dev) if wanted else None
+        if (not isinstance(t, torch.Tensor) or tuple(t.shape) != shape or not t.is_contiguous() or t.dtype != torch.float32
+                or t.device != dev):
+            raise RuntimeError("%s must be a contiguous float32 %s = %s tensor on %s"
+                               % (name, "(B, M, 3, 3)" if len(shape) == 4 else "(B, M, 3)", shape, dev))
+        return t
+
+    out = _output(out, "out", (B, M, 3, 3))
+    vel_out = _output(vel_out, "vel_out", (B, M, 3))
+    omega = _output(omega_out, "omega_out", (B, M, 3), wanted=want_omega)
+    Rc = R.detach().contiguous()
+    Vc = V.detach().contiguous() if V is not None else None
+    outputs = (("out", out), ("vel_out", vel_out), ("omega_out", omega))
+    for src, what in ((Rc, "R"), (Vc, "V")):
+        if src is None:
+            continue
+        lo, hi = src.data_ptr(), src.data_ptr() + 4 * src.numel()
+        for name, t in outputs:
+            if t is not None and t.data_ptr() < hi and lo < t.data_ptr() + 4 * t.numel():
+                raise RuntimeError("%s must not overlap %s (a slot reads any row of %s)" % (name, what, what))
+    _call(dev, "ahv_predict_rotations_f32", idx.data_ptr() if idx is not None else None, Rc.data_ptr(), rstride,
+          Vc.data_ptr() if Vc is not None else None, vstride, N, best_key.data_ptr() if best_key is not None else None, M,
+          n_fresh, B, int(seed) & (2**64 - 1), step.data_ptr(), sigma, sigma_vel, damping, max_angle, max_speed,
+          1 if coast else 0, out.data_ptr(), vel_out.data_ptr(), omega.data_ptr() if omega is not None else None)
+    return (out, vel_out, omega) if omega is not None else (out, vel_out)
+
+
 # ---- multi-view verification ---------------------------------------------------------------------------------------
 # V posed reference views of one object (absolute rotations A_v), one query whose absolute rotation is wanted, N hypotheses Q_n
 # of it: view v sees hypothesis n as R_{v,n} = Q_n A_v^T (gt_src_2_tgt_R = R_tgt R_src^-1), and the per-view scores are fused

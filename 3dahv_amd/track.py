@@ -8,7 +8,10 @@ M pose particles per sample.  Per frame it
 2. ``resample``            draws M particles in proportion to the previous frame's posterior (systematic draws),
 3. ``diffuse_rotations``   moves each by a small random rotation (fresh noise generated on the device from the counter), keeps
                            the previous arg-max untouched in slot 0 (the elite) and fills the last ``n_fresh`` slots with new
-                           Haar rotations (re-acquisition after a lost track),
+                           Haar rotations (re-acquisition after a lost track); with ``motion="constant_velocity"`` the step is
+                           ``predict_rotations`` instead: every particle carries a velocity (a body-frame rotation vector per
+                           frame) that is resampled with it, perturbed and applied before the noise, and slot 1 is the previous
+                           arg-max moved by its own velocity (``coast``),
 4. ``verify_pair``         scores the set against the new frame (the fused scorer, scores kept),
 5. ``select_rotation``     reports the MAP pose,
 
@@ -18,8 +21,10 @@ function of (seed, inputs) alone.
 
 One rank: a particle set is a few hundred to a few thousand rotations, there is nothing to shard.  With an initialised process
 group every rank runs the same tracker on the same inputs and computes the same bytes; no collective is issued.
-Not built: a motion model (constant velocity -- the predict step is a random walk), sigma adapted from the entropy, and the
-tracker inside the multi-view path (``ops.verify_views``).
+The random walk (``motion="walk"``, the default) holds a pose that moves about sigma per frame; a pose that moves steadily
+faster needs ``motion="constant_velocity"``: the particles whose velocity matches the motion are the ones that score, so the
+filter learns the velocity from the scores alone.
+Not built: sigma adapted from the entropy, and the tracker inside the multi-view path (``ops.verify_views``).
 """
 from __future__ import annotations
 
@@ -52,6 +57,12 @@ class PoseTracker:
     list, the workspaces, ``u`` and the step counter.  A step reads one half and writes the other, so a ``TrackStep`` stays
     valid until the step after the next one.  After the first step a step allocates nothing (``posterior=True``: the
     ``pose_posterior`` outputs are that op's own).
+
+    ``motion="constant_velocity"`` (``backend`` then also provides ``predict_rotations``): the tracker owns two more ping-pong
+    buffers ``(B,M,3)``, the particles' velocities, ``.velocities`` after a step (valid as long as that step's particles).  The
+    first step after ``init`` starts from zero velocities.  ``sigma_vel_deg`` is the scale of the velocity noise per frame,
+    ``damping`` in [0, 1] multiplies the velocity each frame, ``max_speed_deg`` limits ``|v|`` (None: no limit) and ``coast``
+    gives slot 1 to the previous arg-max moved by its own velocity with no noise; ``reacquired`` then starts behind that slot.
     Slot 0 carries the previous arg-max bit for bit and a score is a function of (volumes, weights, R) alone, so on an
     unchanged frame the reported score never decreases.
 
@@ -64,7 +75,9 @@ class PoseTracker:
 
     def __init__(self, W1: torch.Tensor, W2: torch.Tensor, b2: torch.Tensor, particles: int, sigma_deg: float = 3.0,
                  n_fresh: int = 0, temperature: float = 0.02, max_angle_deg: Optional[float] = None, batch: int = 1,
-                 seed: int = 0, posterior: bool = False, mode_angle_deg: float = 15.0, use_graph: bool = False, backend=None):
+                 seed: int = 0, posterior: bool = False, mode_angle_deg: float = 15.0, use_graph: bool = False, backend=None,
+                 motion: str = "walk", sigma_vel_deg: float = 1.0, damping: float = 1.0, max_speed_deg: Optional[float] = None,
+                 coast: bool = True):
         dev = W1.device
         self.ops = ops if backend is None else backend
         self.W1, self.W2, self.b2 = W1, W2, b2
@@ -80,6 +93,14 @@ class PoseTracker:
         self.max_angle_deg = None if max_angle_deg is None else float(max_angle_deg)
         ops._angle_rad(self.sigma_deg, "sigma_deg")   # raises unless finite and >= 0
         ops._angle_rad(self.max_angle_deg, "max_angle_deg", allow_none=True)
+        if motion not in ("walk", "constant_velocity"):
+            raise RuntimeError("motion = %r: expected 'walk' or 'constant_velocity'" % (motion,))
+        self.motion = motion
+        self.sigma_vel_deg, self.damping, self.coast = float(sigma_vel_deg), float(damping), bool(coast)
+        self.max_speed_deg = None if max_speed_deg is None else float(max_speed_deg)
+        ops._angle_rad(self.sigma_vel_deg, "sigma_vel_deg")
+        ops._angle_rad(self.max_speed_deg, "max_speed_deg", allow_none=True)
+        ops._unit_interval(self.damping, "damping")
         self.temperature = float(temperature)
         ops.inverse_temperature(self.temperature)     # raises unless finite and > 0
         self.seed = int(seed)
@@ -94,6 +115,8 @@ class PoseTracker:
         B, M = self.B, self.M
         f = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)
         self._R = [f(B, M, 3, 3) for _ in range(2)]
+        self._V = [torch.zeros((B, M, 3), dtype=torch.float32, device=dev) for _ in range(2)] if motion != "walk" else None
+        self._vel = None      # the velocities of the set the next step draws from (None: zeros)
         self._scores = [f(B, M) for _ in range(2)]
         self._keys = [torch.full((B,), KEY_EMPTY, dtype=torch.int64, device=dev) for _ in range(2)]
         self._sel = [(f(B), torch.empty((B,), dtype=torch.int64, device=dev), f(B, 3, 3)) for _ in range(2)]
@@ -122,6 +145,12 @@ class PoseTracker:
         """The int64 device counter (one element): 0 after ``init``, moved by one per step ON THE DEVICE."""
         return self._step
 
+    @property
+    def velocities(self) -> Optional[torch.Tensor]:
+        """``(B,M,3)`` float32: the velocities of the current particles (``motion="constant_velocity"``, after a step); None
+        after ``init`` (the scored set has none) and with ``motion="walk"``."""
+        return self._vel
+
     def _posterior(self, scores, R, R_map, state=None, workspace=None):
         if not self.posterior:
             return None, None, None, None
@@ -145,7 +174,7 @@ class PoseTracker:
         if self.ops is ops and R0.is_cuda and (self._ws0 is None or self._ws0_n != n0):
             self._ws0, self._ws0_n = ops.resample_workspace(self.B, n0, R0.device), n0
         self._step.zero_()
-        self._cur, self._n = (R0, scores, key), 0
+        self._cur, self._n, self._vel = (R0, scores, key), 0, None
         post = self._posterior(scores, R0, R_map)
         return TrackStep(score, idx, R_map, R0, scores, None, *post, torch.zeros_like(idx, dtype=torch.bool))
 
@@ -156,13 +185,21 @@ class PoseTracker:
         ws = self._ws if R_prev.shape[-3] == self.M and R_prev is self._R[1 - p] else self._ws0
         u = o.track_advance(self._step, self.seed, self.B, u=self._u)
         draws = o.resample(s_prev, self.M, self.temperature, u=u, out=self._draws, workspace=ws)
-        R = o.diffuse_rotations(R_prev, idx=draws, sigma_deg=self.sigma_deg, step=self._step, seed=self.seed, best_key=key_prev,
-                                n_fresh=self.n_fresh, max_angle_deg=self.max_angle_deg, out=self._R[p])
+        first = 1
+        if self.motion == "walk":
+            R = o.diffuse_rotations(R_prev, idx=draws, sigma_deg=self.sigma_deg, step=self._step, seed=self.seed,
+                                    best_key=key_prev, n_fresh=self.n_fresh, max_angle_deg=self.max_angle_deg, out=self._R[p])
+        else:
+            R, _ = o.predict_rotations(R_prev, self._vel, idx=draws, sigma_deg=self.sigma_deg, sigma_vel_deg=self.sigma_vel_deg,
+                                       damping=self.damping, step=self._step, seed=self.seed, best_key=key_prev, coast=self.coast,
+                                       n_fresh=self.n_fresh, max_angle_deg=self.max_angle_deg, max_speed_deg=self.max_speed_deg,
+                                       out=self._R[p], vel_out=self._V[p])
+            first = 2 if self.coast else 1
         scores, key = o.verify_pair(vol_src, vol_tgt, R, self.W1, self.W2, self.b2, want_scores=True, best_key=self._keys[p],
                                     reset_best=True, scores_out=self._scores[p])
         score, idx, R_map = o.select_rotation(key, R, out=self._sel[p])
-        # the winner sits in a fresh slot (slot 0 is the elite even when every slot is fresh)
-        reacq = torch.ge(idx, max(self.M - self.n_fresh, 1), out=self._reacq[p])
+        # the winner sits in a fresh slot (slot 0 is the elite, and slot 1 the coasting one, even when every slot is fresh)
+        reacq = torch.ge(idx, max(self.M - self.n_fresh, first), out=self._reacq[p])
         post = self._posterior(scores, R, R_map, self._pstate, self._pws)
         return TrackStep(score, idx, R_map, R, scores, draws, *post, reacq)
 
@@ -196,4 +233,6 @@ class PoseTracker:
             graph, out = self._graphs[p]
             graph.replay()
         self._cur, self._n = (self._R[p], self._scores[p], self._keys[p]), n
+        if self._V is not None:
+            self._vel = self._V[p]
         return out
