@@ -128,6 +128,11 @@ SIGNATURES["ahv_predict_rotations_f32"] = (_int, [_vp, _vp, _i64, _vp, _i64, _i6
                                            + [ctypes.c_float] * 5 + [_int, _vp, _vp, _vp, _vp])
 # (seed, step: DEVICE int64, B, u: DEVICE floats, stream)
 SIGNATURES["ahv_track_advance"] = (_int, [ctypes.c_uint64, _vp, _int, _vp, _vp])
+# (R_cur, scores, V_cur or NULL, step: DEVICE int64, first_step, B, M, H, beta, sigma_rad, jump, damping, hist_R, hist_P or NULL,
+#  hist_delta, hist_back, stream)
+SIGNATURES["ahv_smooth_step_f32"] = (_int, [_vp, _vp, _vp, _vp, _i64, _int, _i64, _i64] + [ctypes.c_float] * 4 + [_vp] * 5)
+# (hist_R, hist_delta, hist_back, step: DEVICE int64, first_step, B, M, H, F, path_idx, path_R, stream)
+SIGNATURES["ahv_smooth_backtrace_f32"] = (_int, [_vp, _vp, _vp, _vp, _i64, _int, _i64, _i64, _i64, _vp, _vp, _vp])
 
 # measurement / developer entry points (include/ahv_diag.h): not part of the drop-in boundary
 DIAG_SIGNATURES = {

@@ -58,6 +58,10 @@ hipError_t launch_predict_rotations(const int64_t*, const float*, int64_t, const
                                     int64_t, int, uint64_t, const int64_t*, float, float, float, float, float, int, float*, float*,
                                     float*, hipStream_t);
 hipError_t launch_track_advance(uint64_t, int64_t*, int, float*, hipStream_t);
+hipError_t launch_smooth_step(const float*, const float*, const float*, const int64_t*, int64_t, int, int64_t, int64_t, float, float,
+                              float, float, float*, float*, float*, int32_t*, hipStream_t);
+hipError_t launch_smooth_backtrace(const float*, const float*, const int32_t*, const int64_t*, int64_t, int, int64_t, int64_t,
+                                   int64_t, int64_t*, float*, hipStream_t);
 hipError_t launch_score_backward(const float*, const float*, const float*, int64_t, const float*, const float*,
                                  const float*, int, int64_t, const float*, float*, float*, float*, float*, float*,
                                  float*, float*, int, hipStream_t, bool);
@@ -1016,6 +1020,50 @@ int ahv_track_advance(uint64_t seed, int64_t* step, int B, float* u, void* strea
     if (B < 1 || B > 65535) return fail(AHV_EINVAL, "track_advance: B = %d outside 1..65535", B);
     hipError_t e = ahv::launch_track_advance(seed, step, B, u, static_cast<hipStream_t>(stream));
     if (e != hipSuccess) return hip_fail("track_advance: launch", e);
+    return AHV_OK;
+}
+
+// ---- pose tracking: trajectory smoothing over the particle history ---------------------------------------------------
+static int smooth_sizes(const char* who, int B, int64_t M, int64_t H)
+{
+    if (M < 1 || M >= (int64_t)1 << 31) return fail(AHV_EINVAL, "%s: M = %lld outside 1..2^31-1", who, (long long)M);
+    if (B < 1 || B > 65535) return fail(AHV_EINVAL, "%s: B = %d outside 1..65535", who, B);
+    if (H < 2 || H >= (int64_t)1 << 31) return fail(AHV_EINVAL, "%s: H = %lld outside 2..2^31-1", who, (long long)H);
+    return AHV_OK;
+}
+
+int ahv_smooth_step_f32(const float* R_cur, const float* scores, const float* V_cur, const int64_t* step, int64_t first_step, int B,
+                        int64_t M, int64_t H, float beta, float sigma_rad, float jump, float damping, float* hist_R, float* hist_P,
+                        float* hist_delta, int32_t* hist_back, void* stream)
+{
+    if (int rc = smooth_sizes("smooth_step", B, M, H)) return rc;
+    if (!R_cur || !scores || !step || !hist_R || !hist_delta || !hist_back)
+        return fail(AHV_EINVAL, "smooth_step: null pointer (R_cur, scores, step, hist_R, hist_delta and hist_back are required)");
+    if ((V_cur != nullptr) != (hist_P != nullptr))
+        return fail(AHV_EINVAL, "smooth_step: V_cur and hist_P go together (both or neither)");
+    if (!(beta > 0.0f && beta < __builtin_inff())) return fail(AHV_EINVAL, "smooth_step: beta = %g must be finite and > 0", (double)beta);
+    // 1 / (4 sigma^2) is the kernel's factor: it has to fit a float
+    const double inv4s2 = 1.0 / (4.0 * (double)sigma_rad * (double)sigma_rad);
+    if (!(sigma_rad > 0.0f && sigma_rad < __builtin_inff() && inv4s2 < 3.0e38))
+        return fail(AHV_EINVAL, "smooth_step: sigma = %g must be finite and > 0, with 1/(4 sigma^2) inside a float", (double)sigma_rad);
+    if (!(jump >= 0.0f)) return fail(AHV_EINVAL, "smooth_step: jump = %g must be >= 0 (+inf: no floor)", (double)jump);
+    if (!(damping >= 0.0f && damping <= 1.0f)) return fail(AHV_EINVAL, "smooth_step: damping = %g outside [0, 1]", (double)damping);
+    hipError_t e = ahv::launch_smooth_step(R_cur, scores, V_cur, step, first_step, B, M, H, beta, (float)inv4s2, jump, damping, hist_R,
+                                           hist_P, hist_delta, hist_back, static_cast<hipStream_t>(stream));
+    if (e != hipSuccess) return hip_fail("smooth_step: launch", e);
+    return AHV_OK;
+}
+
+int ahv_smooth_backtrace_f32(const float* hist_R, const float* hist_delta, const int32_t* hist_back, const int64_t* step,
+                             int64_t first_step, int B, int64_t M, int64_t H, int64_t F, int64_t* path_idx, float* path_R,
+                             void* stream)
+{
+    if (int rc = smooth_sizes("smooth_backtrace", B, M, H)) return rc;
+    if (F < 1 || F > H) return fail(AHV_EINVAL, "smooth_backtrace: F = %lld outside 1..H = %lld", (long long)F, (long long)H);
+    if (!hist_R || !hist_delta || !hist_back || !step || !path_idx || !path_R) return fail(AHV_EINVAL, "smooth_backtrace: null pointer");
+    hipError_t e = ahv::launch_smooth_backtrace(hist_R, hist_delta, hist_back, step, first_step, B, M, H, F, path_idx, path_R,
+                                                static_cast<hipStream_t>(stream));
+    if (e != hipSuccess) return hip_fail("smooth_backtrace: launch", e);
     return AHV_OK;
 }
 

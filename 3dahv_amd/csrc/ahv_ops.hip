@@ -677,9 +677,46 @@ __global__ __launch_bounds__(256) void diffuse_rotations_kernel(const long long*
 //   else   v' = damping v_i + sigma_vel y (clipped to max_speed), w = v' + sigma z (the second term clipped to max_angle),
 //          out = R_i exp([w]x) composed as unit quaternions and normalised, exactly as diffuse_rotations_kernel does
 // z is the block diffuse_rotations_kernel draws (third counter word kDiffuseTag), y a second block (kVelocityTag).
-// The composition is a copy of diffuse_rotations_kernel's on purpose: that kernel's instructions are pinned, so
-// nothing is factored out of it.
+// The composition is compose_rotation_vector below, shared with smooth_step_kernel: the sequence of diffuse_rotations_kernel,
+// which keeps its own copy on purpose -- that kernel's instructions are pinned, so nothing is factored out of it.
 // ---------------------------------------------------------------------------------
+__device__ __forceinline__ bool finite_f(float x) { return fabsf(x) < __builtin_inff(); }  // false for NaN
+
+// o = M(normalise(q(r) q(w))), the matrix of r exp([w]x), composed as unit quaternions and normalised.
+__device__ __forceinline__ void compose_rotation_vector(const float (&r)[9], float w0, float w1, float w2, float* __restrict__ o)
+{
+    const float a = sqrtf(w0 * w0 + w1 * w1 + w2 * w2);
+    // q(w) = (cos a/2, sin(a/2) w / a); sin(a/2) / a -> 1/2 - a^2/48 as a -> 0
+    float sh, ch;
+    sincosf(0.5f * a, &sh, &ch);
+    const float kq = a < 1e-3f ? 0.5f - a * a * (1.0f / 48.0f) : sh / a;
+    const float dr = ch, di = kq * w0, dj = kq * w1, dk = kq * w2;
+    // q(R) by Shepperd's branch: divide by the largest of the four components
+    float qr, qi, qj, qk;
+    const float tr = r[0] + r[4] + r[8];
+    if (tr > 0.0f) {
+        const float s = 2.0f * sqrtf(tr + 1.0f);
+        qr = 0.25f * s; qi = (r[7] - r[5]) / s; qj = (r[2] - r[6]) / s; qk = (r[3] - r[1]) / s;
+    } else if (r[0] > r[4] && r[0] > r[8]) {
+        const float s = 2.0f * sqrtf(1.0f + r[0] - r[4] - r[8]);
+        qr = (r[7] - r[5]) / s; qi = 0.25f * s; qj = (r[1] + r[3]) / s; qk = (r[2] + r[6]) / s;
+    } else if (r[4] > r[8]) {
+        const float s = 2.0f * sqrtf(1.0f + r[4] - r[0] - r[8]);
+        qr = (r[2] - r[6]) / s; qi = (r[1] + r[3]) / s; qj = 0.25f * s; qk = (r[5] + r[7]) / s;
+    } else {
+        const float s = 2.0f * sqrtf(1.0f + r[8] - r[0] - r[4]);
+        qr = (r[3] - r[1]) / s; qi = (r[2] + r[6]) / s; qj = (r[5] + r[7]) / s; qk = 0.25f * s;
+    }
+    // Hamilton product q(R) q(w): the matrix of a product is the product of the matrices, R exp([w]x)
+    float pr = qr * dr - qi * di - qj * dj - qk * dk;
+    float pi = qr * di + qi * dr + qj * dk - qk * dj;
+    float pj = qr * dj - qi * dk + qj * dr + qk * di;
+    float pk = qr * dk + qi * dj - qj * di + qk * dr;
+    const float inv = 1.0f / sqrtf(fmaxf(pr * pr + pi * pi + pj * pj + pk * pk, 1e-30f));
+    pr *= inv; pi *= inv; pj *= inv; pk *= inv;
+    quaternion_matrix(pr, pi, pj, pk, o);
+}
+
 constexpr unsigned kVelocityTag = 0x56454Cu;
 
 // Scales (x, y, z) so that its norm is <= limit (limit > 0; 0 means no limit) and returns the norm of the result.  2^-21 of
@@ -752,36 +789,8 @@ __global__ __launch_bounds__(256) void predict_rotations_kernel(const long long*
                 clip_norm(p0, p1, p2, max_angle);
                 w0 = v0 + p0; w1 = v1 + p1; w2 = v2 + p2;
             }
-            const float a = sqrtf(w0 * w0 + w1 * w1 + w2 * w2);
-            // q(w) = (cos a/2, sin(a/2) w / a); sin(a/2) / a -> 1/2 - a^2/48 as a -> 0
-            float sh, ch;
-            sincosf(0.5f * a, &sh, &ch);
-            const float kq = a < 1e-3f ? 0.5f - a * a * (1.0f / 48.0f) : sh / a;
-            const float dr = ch, di = kq * w0, dj = kq * w1, dk = kq * w2;
-            // q(R) by Shepperd's branch: divide by the largest of the four components
-            float qr, qi, qj, qk;
-            const float tr = r00 + r11 + r22;
-            if (tr > 0.0f) {
-                const float s = 2.0f * sqrtf(tr + 1.0f);
-                qr = 0.25f * s; qi = (r21 - r12) / s; qj = (r02 - r20) / s; qk = (r10 - r01) / s;
-            } else if (r00 > r11 && r00 > r22) {
-                const float s = 2.0f * sqrtf(1.0f + r00 - r11 - r22);
-                qr = (r21 - r12) / s; qi = 0.25f * s; qj = (r01 + r10) / s; qk = (r02 + r20) / s;
-            } else if (r11 > r22) {
-                const float s = 2.0f * sqrtf(1.0f + r11 - r00 - r22);
-                qr = (r02 - r20) / s; qi = (r01 + r10) / s; qj = 0.25f * s; qk = (r12 + r21) / s;
-            } else {
-                const float s = 2.0f * sqrtf(1.0f + r22 - r00 - r11);
-                qr = (r10 - r01) / s; qi = (r02 + r20) / s; qj = (r12 + r21) / s; qk = 0.25f * s;
-            }
-            // Hamilton product q(R) q(w): the matrix of a product is the product of the matrices, R exp([w]x)
-            float pr = qr * dr - qi * di - qj * dj - qk * dk;
-            float pi = qr * di + qi * dr + qj * dk - qk * dj;
-            float pj = qr * dj - qi * dk + qj * dr + qk * di;
-            float pk = qr * dk + qi * dj - qj * di + qk * dr;
-            const float inv = 1.0f / sqrtf(fmaxf(pr * pr + pi * pi + pj * pj + pk * pk, 1e-30f));
-            pr *= inv; pi *= inv; pj *= inv; pk *= inv;
-            quaternion_matrix(pr, pi, pj, pk, o);
+            const float rr[9] = {r00, r01, r02, r10, r11, r12, r20, r21, r22};
+            compose_rotation_vector(rr, w0, w1, w2, o);
         }
     }
     float* vo = vel_out + i * 3;
@@ -804,6 +813,206 @@ __global__ __launch_bounds__(256) void track_advance_kernel(unsigned long long s
     }
     __syncthreads();
     if (threadIdx.x == 0) *step = (long long)t1;
+}
+
+// ---------------------------------------------------------------------------------
+// Trajectory smoothing over the particle history (ahv_smooth_step_f32 / ahv_smooth_backtrace_f32, include/ahv.h): a Viterbi
+// recursion over the particle sets of the last H frames, kept in a ring the caller owns, and the backtrace.
+//
+// Step: a workgroup owns kSmoothSucc = 16 successors j of one sample and splits the predecessors 16 ways: lane l of wave w
+// holds successor l mod 16 (the nine entries of R_j in registers) and belongs to group g = 4 w + l / 16.  The predecessors (the
+// previous slot's predicted poses and deltas) go through LDS in tiles of 256 rows of 12 floats (nine entries, delta_i - m, two
+// of padding: three 16-byte reads).  Thread k stages row k of a tile -- loaded into registers while the tile before is being
+// walked -- and group g walks rows g, 16 + g, ..., 240 + g: the four groups of a wave read four adjacent rows, 192 contiguous
+// bytes, so the reads of a 16-lane group broadcast and the four do not share a bank.  A group meets its rows in increasing i
+// and keeps (max, first index); the 16 partial results of a successor are merged by (larger value, then lower index), four by
+// lane shuffles and the waves' in LDS.  Every c_ij is one expression, evaluated once, and (max, lowest index) does not depend
+// on the order: the bytes do not depend on the split.  At M = 4 096 that is 256 workgroups, one per CU, 256 pairs per lane.
+// A row whose delta is not finite, and a row past the end of the set, is staged with NaN in place of delta_i - m: its c_ij is
+// NaN, which no comparison selects, as is the c_ij of a NaN matrix.  The workgroup reads the previous slot only and writes its
+// own rows of the current slot.
+// ---------------------------------------------------------------------------------
+constexpr int kSmoothSucc = 16, kSmoothTile = 256, kSmoothRow = 12;
+
+// (value, index) merge of the Viterbi maximum: the larger value, then the lower index.
+__device__ __forceinline__ void merge_first_max(float& v, int& i, float ov, int oi)
+{
+    if (ov > v || (ov == v && oi < i)) { v = ov; i = oi; }
+}
+
+__global__ __launch_bounds__(256) void smooth_step_kernel(const float* __restrict__ R_cur, const float* __restrict__ scores,
+                                                          const float* __restrict__ V_cur, const long long* __restrict__ step,
+                                                          long long first_step, int M, long long H, float beta, float inv4s2,
+                                                          float jump, float damping, float* __restrict__ hist_R,
+                                                          float* __restrict__ hist_P, float* __restrict__ hist_delta,
+                                                          int* __restrict__ hist_back)
+{
+    __shared__ __attribute__((aligned(16))) float tile[kSmoothTile * kSmoothRow];
+    __shared__ float part_v[4][kSmoothSucc];
+    __shared__ int part_i[4][kSmoothSucc];
+    __shared__ float wave_max[4];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int succ = lane & (kSmoothSucc - 1), group = 4 * wave + (lane >> 4);
+    const long b = blockIdx.y, nb = gridDim.y;
+    const long long t = *step;
+    const long slot = (long)(((t % H) + H) % H), prev = (long)((((t - 1) % H) + H) % H);  // int64: t may be past 2^32
+    const long row_cur = (slot * nb + b) * (long)M, row_prev = (prev * nb + b) * (long)M;
+    const int j0 = blockIdx.x * kSmoothSucc;
+    const int rows = min(kSmoothSucc, M - j0);
+    const bool live = succ < rows;
+    const int j = j0 + (live ? succ : 0);
+    const float* rc = R_cur + (b * (long)M + j) * 9;
+
+    // hist_R[slot]: this workgroup's rows, bit for bit
+    if (tid < rows * 9) hist_R[(row_cur + j0) * 9 + tid] = R_cur[(b * (long)M + j0) * 9 + tid];
+    float r[9];
+#pragma unroll
+    for (int k = 0; k < 9; ++k) r[k] = rc[k];
+
+    // m: the largest finite delta of the previous slot (every workgroup of the sample finds the same one)
+    bool has_prev = t > first_step;
+    float m = -__builtin_inff();
+    if (has_prev) {
+        for (long i = tid; i < M; i += 256) {
+            const float d = hist_delta[row_prev + i];
+            if (finite_f(d)) m = fmaxf(m, d);
+        }
+#pragma unroll
+        for (int s = 32; s >= 1; s >>= 1) m = fmaxf(m, __shfl_xor(m, s, 64));
+        if (lane == 0) wave_max[wave] = m;
+        __syncthreads();
+        m = fmaxf(fmaxf(wave_max[0], wave_max[1]), fmaxf(wave_max[2], wave_max[3]));
+        has_prev = finite_f(m);
+    }
+
+    float best = -__builtin_inff();
+    int best_i = -1;
+    if (has_prev) {
+        const float neg_jump = -jump;
+        const float* P = hist_P ? hist_P : hist_R;
+        // this thread's row of a tile: nine entries and delta_i - m, NaN for a dead row and past the end
+        float stage[10];
+        const auto load_row = [&](long i) {
+#pragma unroll
+            for (int k = 0; k < 9; ++k) stage[k] = 0.0f;
+            stage[9] = __builtin_nanf("");
+            if (i < M) {
+                const float* src = P + (row_prev + i) * 9;
+#pragma unroll
+                for (int k = 0; k < 9; ++k) stage[k] = src[k];
+                const float v = hist_delta[row_prev + i];
+                if (finite_f(v)) stage[9] = v - m;
+            }
+        };
+        load_row(tid);
+        for (long i0 = 0; i0 < M; i0 += kSmoothTile) {
+            __syncthreads();  // the previous tile has been read by every wave
+            f32x4* dst = reinterpret_cast<f32x4*>(tile + tid * kSmoothRow);
+            dst[0] = f32x4{stage[0], stage[1], stage[2], stage[3]};
+            dst[1] = f32x4{stage[4], stage[5], stage[6], stage[7]};
+            dst[2] = f32x4{stage[8], stage[9], 0.0f, 0.0f};
+            __syncthreads();
+            if (i0 + kSmoothTile < M) load_row(i0 + kSmoothTile + tid);  // in flight while this tile is walked
+#pragma unroll 4
+            for (int p = 0; p < kSmoothTile / 16; ++p) {
+                const int row = 16 * p + group;
+                const f32x4 a = *reinterpret_cast<const f32x4*>(tile + row * kSmoothRow);
+                const f32x4 c = *reinterpret_cast<const f32x4*>(tile + row * kSmoothRow + 4);
+                const f32x4 d = *reinterpret_cast<const f32x4*>(tile + row * kSmoothRow + 8);
+                // ||P_i - R_j||_F^2 from the nine differences (3 - tr cancels for the near pairs that decide the maximum)
+                const float e0 = a[0] - r[0], e1 = a[1] - r[1], e2 = a[2] - r[2], e3 = a[3] - r[3], e4 = c[0] - r[4];
+                const float e5 = c[1] - r[5], e6 = c[2] - r[6], e7 = c[3] - r[7], e8 = d[0] - r[8];
+                float q = e0 * e0;
+                q = fmaf(e1, e1, q); q = fmaf(e2, e2, q); q = fmaf(e3, e3, q); q = fmaf(e4, e4, q);
+                q = fmaf(e5, e5, q); q = fmaf(e6, e6, q); q = fmaf(e7, e7, q); q = fmaf(e8, e8, q);
+                const float w = -(q * inv4s2);
+                const float cij = d[1] + (w < neg_jump ? neg_jump : w);  // (a NaN w stays NaN: fmaxf would drop it)
+                if (cij > best) { best = cij; best_i = (int)i0 + row; }
+            }
+        }
+        // the four groups of a wave (lanes succ, succ + 16, + 32, + 48), then the four waves
+#pragma unroll
+        for (int s = 16; s <= 32; s <<= 1) merge_first_max(best, best_i, __shfl_xor(best, s, 64), __shfl_xor(best_i, s, 64));
+        if (lane < kSmoothSucc) { part_v[wave][lane] = best; part_i[wave][lane] = best_i; }
+        __syncthreads();
+    }
+
+    if (tid < kSmoothSucc && live) {
+        if (has_prev) {
+#pragma unroll
+            for (int w = 1; w < 4; ++w) merge_first_max(best, best_i, part_v[w][lane], part_i[w][lane]);
+        }
+        const float s = scores[b * (long)M + j];
+        float delta = -__builtin_inff();
+        int back = -1;
+        if (finite_f(s)) {
+            delta = beta * s;
+            if (best_i >= 0) { delta += best; back = best_i; }
+        }
+        hist_delta[row_cur + j] = delta;
+        hist_back[row_cur + j] = back;
+    }
+    if (hist_P && wave == 1 && lane < kSmoothSucc && live) {
+        const float* v = V_cur + (b * (long)M + j) * 3;
+        compose_rotation_vector(r, damping * v[0], damping * v[1], damping * v[2], hist_P + (row_cur + j) * 9);
+    }
+}
+
+// Backtrace: one workgroup per sample walks t, t - 1, ... over F <= H frames and writes the outputs oldest first.  The index
+// carried to the frame before is back[j]; with none carried (the start, or behind a break) the frame's first arg-max over its
+// finite deltas is taken by the whole workgroup.  `carry` is the same in every thread, so the barriers are uniform.
+__global__ __launch_bounds__(256) void smooth_backtrace_kernel(const float* __restrict__ hist_R, const float* __restrict__ hist_delta,
+                                                               const int* __restrict__ hist_back, const long long* __restrict__ step,
+                                                               long long first_step, int M, long long H, int F,
+                                                               long long* __restrict__ path_idx, float* __restrict__ path_R)
+{
+    __shared__ float part_v[4];
+    __shared__ int part_i[4];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const long b = blockIdx.x, nb = gridDim.x;
+    const long long t = *step;
+    int carry = -1;
+    for (int k = 0; k < F; ++k) {
+        const long long tk = t - k;
+        const long o = b * (long)F + (F - 1 - k);
+        long row = 0;
+        if (tk < first_step) {
+            carry = -1;  // never recorded
+        } else {
+            row = ((long)(((tk % H) + H) % H) * nb + b) * (long)M;
+            if (carry < 0) {
+                float v = -__builtin_inff();
+                int vi = -1;
+                for (long i = tid; i < M; i += 256) {
+                    const float d = hist_delta[row + i];
+                    if (finite_f(d) && (vi < 0 || d > v)) { v = d; vi = (int)i; }
+                }
+#pragma unroll
+                for (int s = 32; s >= 1; s >>= 1) {
+                    const float ov = __shfl_xor(v, s, 64);
+                    const int oi = __shfl_xor(vi, s, 64);
+                    if (oi >= 0 && (vi < 0 || ov > v || (ov == v && oi < vi))) { v = ov; vi = oi; }
+                }
+                if (lane == 0) { part_v[wave] = v; part_i[wave] = vi; }
+                __syncthreads();
+                v = part_v[0]; vi = part_i[0];
+#pragma unroll
+                for (int w = 1; w < 4; ++w) {
+                    const float ov = part_v[w];
+                    const int oi = part_i[w];
+                    if (oi >= 0 && (vi < 0 || ov > v || (ov == v && oi < vi))) { v = ov; vi = oi; }
+                }
+                __syncthreads();  // part_* are free for the next break
+                carry = vi;
+            }
+        }
+        if (tid == 0) path_idx[o] = carry;
+        if (tid < 9) path_R[o * 9 + tid] = carry >= 0 ? hist_R[(row + carry) * 9 + tid] : (tid % 4 == 0 ? 1.0f : 0.0f);
+        if (carry >= 0) {
+            const int nxt = hist_back[row + carry];
+            carry = (nxt >= 0 && nxt < M) ? nxt : -1;  // a ring the step did not write: stay in bounds
+        }
+    }
 }
 
 // Super-Fibonacci SO(3) grid (Alexa, CVPR 2022): point i of n is the quaternion
@@ -941,6 +1150,26 @@ hipError_t launch_track_advance(uint64_t seed, int64_t* step, int B, float* u, h
 {
     hipLaunchKernelGGL(track_advance_kernel, dim3(1), dim3(256), 0, stream, (unsigned long long)seed,
                        reinterpret_cast<long long*>(step), B, u);
+    return hipGetLastError();
+}
+
+hipError_t launch_smooth_step(const float* R_cur, const float* scores, const float* V_cur, const int64_t* step, int64_t first_step,
+                              int B, int64_t M, int64_t H, float beta, float inv4s2, float jump, float damping, float* hist_R,
+                              float* hist_P, float* hist_delta, int32_t* hist_back, hipStream_t stream)
+{
+    hipLaunchKernelGGL(smooth_step_kernel, dim3((unsigned)((M + kSmoothSucc - 1) / kSmoothSucc), (unsigned)B), dim3(256), 0, stream,
+                       R_cur, scores, V_cur, reinterpret_cast<const long long*>(step), (long long)first_step, (int)M, (long long)H,
+                       beta, inv4s2, jump, damping, hist_R, hist_P, hist_delta, reinterpret_cast<int*>(hist_back));
+    return hipGetLastError();
+}
+
+hipError_t launch_smooth_backtrace(const float* hist_R, const float* hist_delta, const int32_t* hist_back, const int64_t* step,
+                                   int64_t first_step, int B, int64_t M, int64_t H, int64_t F, int64_t* path_idx, float* path_R,
+                                   hipStream_t stream)
+{
+    hipLaunchKernelGGL(smooth_backtrace_kernel, dim3((unsigned)B), dim3(256), 0, stream, hist_R, hist_delta,
+                       reinterpret_cast<const int*>(hist_back), reinterpret_cast<const long long*>(step), (long long)first_step,
+                       (int)M, (long long)H, (int)F, reinterpret_cast<long long*>(path_idx), path_R);
     return hipGetLastError();
 }
 

@@ -235,7 +235,7 @@ def evaluate_category(cfg, model, sequences: Iterable[dict], num_frames: int = 2
 
 @torch.no_grad()
 def track_sequence(model, item: dict, tracker, ref: int = 0, proposals: Optional[torch.Tensor] = None, device=None,
-                   encoder_fn: Optional[Callable] = None, row_vector_R: bool = False) -> dict:
+                   encoder_fn: Optional[Callable] = None, row_vector_R: bool = False, smoothed: bool = False) -> dict:
     """Track ONE sequence with a ``track.PoseTracker`` (batch 1).  ``item`` is what ``SyntheticSequences`` or
     ``co3d.Co3dSequences`` yields.  Frame ``ref`` is the reference view; every other frame is tracked in order: per frame the
     encoder runs on (reference, frame) -- ``encoder_fn`` or ``model.forward_features`` for ``layer4`` inputs, else ``model`` --,
@@ -247,7 +247,10 @@ def track_sequence(model, item: dict, tracker, ref: int = 0, proposals: Optional
     the ground truth is ``R_ref^T R_t``, the same quantity ``evaluate_category`` uses for the pair (ref, t).
     Returns ``{"frames": [t, ...], "R_map" (F,3,3), "score" (F,), "err" (F,) degrees}`` as host tensors, one row per tracked
     frame; the results stay on the device and this function synchronises with the host ONCE, at the end (a tracker with
-    ``use_graph=True`` synchronises on its own while it captures, on its second and third step)."""
+    ``use_graph=True`` synchronises on its own while it captures, on its second and third step).
+    ``smoothed=True`` (a tracker built with ``history``): the result also has ``"smoothed"``, the MAP trajectory over the
+    tracker's history at the end of the sequence -- ``{"frames", "idx" (F',), "R" (F',3,3), "err" (F',)}`` for the last
+    ``F' = min(steps, history)`` tracked frames (the frame given to ``init`` is not recorded); it costs a second host copy."""
     if tracker.B != 1:
         raise RuntimeError("track_sequence tracks one sequence: the tracker must have batch = 1, got %d" % tracker.B)
     if device is None:
@@ -266,7 +269,7 @@ def track_sequence(model, item: dict, tracker, ref: int = 0, proposals: Optional
         proposals = random_rotations(4096, generator=torch.Generator().manual_seed(0))
     proposals = proposals.to(device)
     order = [t for t in range(n) if t != ref]
-    R_map, score, err = [], [], []
+    R_map, score, err, truth = [], [], [], []
     for k, t in enumerate(order):
         vol_src, vol_tgt = embed(frames[ref:ref + 1], frames[t:t + 1])
         res = tracker.init(vol_src, vol_tgt, proposals) if k == 0 else tracker.step(vol_src, vol_tgt)
@@ -274,10 +277,20 @@ def track_sequence(model, item: dict, tracker, ref: int = 0, proposals: Optional
         R_map.append(res.R_map[0].clone())          # (the tracker's outputs are buffers it reuses two steps later)
         score.append(res.score[0].clone())
         err.append(geodesic_deg(res.R_map, R_gt[None])[0])
+        truth.append(R_gt)
     if not order:
         return {"frames": [], "R_map": torch.zeros(0, 3, 3), "score": torch.zeros(0), "err": torch.zeros(0)}
     packed = torch.cat([torch.stack(R_map).reshape(-1, 9), torch.stack(score)[:, None], torch.stack(err)[:, None]], dim=1).cpu()
-    return {"frames": order, "R_map": packed[:, :9].reshape(-1, 3, 3), "score": packed[:, 9], "err": packed[:, 10]}
+    out = {"frames": order, "R_map": packed[:, :9].reshape(-1, 3, 3), "score": packed[:, 9], "err": packed[:, 10]}
+    if smoothed:
+        if len(order) < 2:
+            out["smoothed"] = {"frames": [], "idx": torch.zeros(0, dtype=torch.int64), "R": torch.zeros(0, 3, 3), "err": torch.zeros(0)}
+        else:
+            path = tracker.smoothed()
+            n_s = path.R.shape[1]
+            s_err = geodesic_deg(path.R[0], torch.stack(truth[-n_s:]))
+            out["smoothed"] = {"frames": order[-n_s:], "idx": path.idx[0].cpu(), "R": path.R[0].cpu(), "err": s_err.cpu()}
+    return out
 
 
 def evaluate_pairwise(cfg, model, categories: Dict[str, Iterable[dict]], num_frames: int = 2, print_results=True,

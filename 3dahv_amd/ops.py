@@ -1323,6 +1323,119 @@ def predict_rotations(R: torch.Tensor, V: torch.Tensor | None = None, idx: torch
     return (out, vel_out, omega) if omega is not None else (out, vel_out)
 
 
+# ---- trajectory smoothing ------------------------------------------------------------------------------------------
+# MAP sequence estimation over the particle history (``ahv_smooth_step_f32`` / ``ahv_smooth_backtrace_f32``, include/ahv.h): a
+# Viterbi step per frame into a ring of H frames, and the backtrace that reads the path out of it.
+
+SmoothHistory = collections.namedtuple("SmoothHistory", ["R", "P", "delta", "back"])
+SmoothedPath = collections.namedtuple("SmoothedPath", ["idx", "R"])
+
+
+def smooth_history(B: int, M: int, H: int, device, velocities: bool = False) -> SmoothHistory:
+    """The ring of ``smooth_step``: ``R (H,B,M,3,3)`` float32, ``P`` the same shape with ``velocities`` (the predicted poses),
+    else None, ``delta (H,B,M)`` float32 and ``back (H,B,M)`` int32.  Not initialised: a step at ``first_step`` reads none of
+    it, and ``smooth_backtrace`` never looks behind ``first_step``."""
+    B, M, H = int(B), _draws(M), int(H)
+    if not 1 <= B <= 65535:
+        raise RuntimeError("B = %d outside 1..65535" % B)
+    if not 2 <= H < (1 << 31):
+        raise RuntimeError("H = %d outside 2..2^31-1 (a frame and its predecessors live in different slots)" % H)
+    f = lambda *shape: torch.empty(shape, dtype=torch.float32, device=device)
+    return SmoothHistory(f(H, B, M, 3, 3), f(H, B, M, 3, 3) if velocities else None, f(H, B, M),
+                         torch.empty((H, B, M), dtype=torch.int32, device=device))
+
+
+def _smooth_ring(history):
+    """``(H, B, M, dev)`` of a ``SmoothHistory`` after checking its tensors against each other."""
+    if not isinstance(history, SmoothHistory) or not isinstance(history.R, torch.Tensor) or history.R.dim() != 5:
+        raise RuntimeError("history must be the SmoothHistory of smooth_history()")
+    H, B, M = history.R.shape[:3]
+    dev = _need_gpu(history.R, history.delta) if history.P is None else _need_gpu(history.R, history.P, history.delta)
+    for name, t, shape, dtype in (("R", history.R, (H, B, M, 3, 3), torch.float32), ("P", history.P, (H, B, M, 3, 3), torch.float32),
+                                  ("delta", history.delta, (H, B, M), torch.float32), ("back", history.back, (H, B, M), torch.int32)):
+        if t is None and name == "P":
+            continue
+        if (not isinstance(t, torch.Tensor) or tuple(t.shape) != shape or t.dtype != dtype or not t.is_contiguous()
+                or t.device != dev):
+            raise RuntimeError("history.%s must be a contiguous %s tensor %s on %s" % (name, dtype, shape, dev))
+    if not (1 <= M < (1 << 31) and 1 <= B <= 65535 and 2 <= H < (1 << 31)):
+        raise RuntimeError("history of H = %d, B = %d, M = %d: outside H >= 2, 1 <= B <= 65535, 1 <= M < 2^31" % (H, B, M))
+    return H, B, M, dev
+
+
+def _jump(jump) -> float:
+    j = float(jump)
+    if not j >= 0.0:      # (false for NaN; +inf is allowed: no floor)
+        raise RuntimeError("jump = %r must be >= 0 (+inf: no floor)" % (jump,))
+    return j
+
+
+@torch.no_grad()
+def smooth_step(history: SmoothHistory, R: torch.Tensor, scores: torch.Tensor, step: torch.Tensor, temperature: float,
+                sigma_deg: float, jump: float = 8.0, V: torch.Tensor | None = None, damping: float = 1.0,
+                first_step: int = 1) -> SmoothHistory:
+    """One Viterbi step of the trajectory smoother (``ahv_smooth_step_f32``, one launch): records the frame's particle set
+    ``R (B,M,3,3)`` and ``scores (B,M)`` into slot ``t mod H`` of ``history``, ``t = step[0]`` read ON THE DEVICE (the counter
+    ``track_advance`` moved, so a replayed graph records into a new slot).  With predecessors (``t > first_step``) particle j gets
+    ``delta_j = s_j / T + max_i [(delta_i - m) + max(-|P_i - R_j|_F^2 / (4 sigma^2), -jump)]`` and ``back_j``, the first i that
+    attains it; ``P_i`` is the pose predecessor i predicts for this frame: ``R_i exp(damping v_i)`` with velocities ``V (B,M,3)``
+    (the ring then has ``P``: ``smooth_history(..., velocities=True)``), else ``R_i``.  ``sigma_deg > 0`` is the scale of the
+    transition (-theta^2 / (2 sigma^2) for a small angle theta) and ``jump`` the price of an arbitrary jump (+inf: none).  A
+    particle whose score is not finite is dead (``delta = -inf``, ``back = -1``).  No allocation, no host synchronisation.
+    Returns ``history``."""
+    H, B, M, dev = _smooth_ring(history)
+    _need_gpu(history.R, R, scores)
+    step = _step_counter(step, dev)
+    if tuple(R.shape) != (B, M, 3, 3) or tuple(scores.shape) != (B, M):
+        raise RuntimeError("R must be (B,M,3,3) = %s and scores (B,M) = %s, got %s and %s"
+                           % ((B, M, 3, 3), (B, M), tuple(R.shape), tuple(scores.shape)))
+    if (V is not None) != (history.P is not None):
+        raise RuntimeError("V and history.P go together: smooth_history(..., velocities=True) for a tracker with velocities")
+    if V is not None:
+        _need_gpu(history.R, V)
+        if tuple(V.shape) != (B, M, 3):
+            raise RuntimeError("V must be (B,M,3) = %s, got %s" % ((B, M, 3), tuple(V.shape)))
+    beta = inverse_temperature(temperature)
+    sigma = _angle_rad(sigma_deg, "sigma_deg")
+    if not (sigma > 0.0 and 1.0 / (4.0 * sigma * sigma) < 3.0e38):
+        raise RuntimeError("sigma_deg = %r must be > 0 (and 1 / (4 sigma^2) must fit a float32)" % (sigma_deg,))
+    jump = _jump(jump)
+    damping = _unit_interval(damping, "damping")
+    Rc, sc = R.detach().contiguous(), scores.detach().contiguous()
+    Vc = V.detach().contiguous() if V is not None else None
+    _call(dev, "ahv_smooth_step_f32", Rc.data_ptr(), sc.data_ptr(), Vc.data_ptr() if Vc is not None else None, step.data_ptr(),
+          int(first_step), B, M, H, beta, sigma, jump, damping, history.R.data_ptr(),
+          history.P.data_ptr() if history.P is not None else None, history.delta.data_ptr(), history.back.data_ptr())
+    return history
+
+
+@torch.no_grad()
+def smooth_backtrace(history: SmoothHistory, step: torch.Tensor, frames: int | None = None, first_step: int = 1,
+                     out: SmoothedPath | None = None) -> SmoothedPath:
+    """The MAP path over the newest ``frames`` (default H, at most H) recorded frames (``ahv_smooth_backtrace_f32``, one launch,
+    one workgroup per sample): ``SmoothedPath(idx (B,F) int64, R (B,F,3,3))``, oldest first, the last column the frame of
+    ``t = step[0]`` (read on the device).  ``idx[b,f]`` is the particle the path takes in that frame's set and ``R`` its pose;
+    a frame before ``first_step``, and a frame without a finite delta, gives -1 and the identity, and the path restarts behind
+    such a break.  ``out``: a ``SmoothedPath`` to write into (allocates nothing)."""
+    H, B, M, dev = _smooth_ring(history)
+    step = _step_counter(step, dev)
+    F = H if frames is None else int(frames)
+    if not 1 <= F <= H:
+        raise RuntimeError("frames = %d outside 1..H = %d" % (F, H))
+    if out is None:
+        out = SmoothedPath(torch.empty((B, F), dtype=torch.int64, device=dev), torch.empty((B, F, 3, 3), dtype=torch.float32, device=dev))
+    else:
+        idx, Rp = out
+        if (not isinstance(idx, torch.Tensor) or tuple(idx.shape) != (B, F) or idx.dtype != torch.int64 or not idx.is_contiguous()
+                or idx.device != dev or not isinstance(Rp, torch.Tensor) or tuple(Rp.shape) != (B, F, 3, 3)
+                or Rp.dtype != torch.float32 or not Rp.is_contiguous() or Rp.device != dev):
+            raise RuntimeError("out must be SmoothedPath(int64 (B,F) = %s, float32 (B,F,3,3)), contiguous, on %s" % ((B, F), dev))
+        out = SmoothedPath(idx, Rp)
+    _call(dev, "ahv_smooth_backtrace_f32", history.R.data_ptr(), history.delta.data_ptr(), history.back.data_ptr(), step.data_ptr(),
+          int(first_step), B, M, H, F, out.idx.data_ptr(), out.R.data_ptr())
+    return out
+
+
 # ---- multi-view verification ---------------------------------------------------------------------------------------
 # V posed reference views of one object (absolute rotations A_v), one query whose absolute rotation is wanted, N hypotheses Q_n
 # of it: view v sees hypothesis n as R_{v,n} = Q_n A_v^T (gt_src_2_tgt_R = R_tgt R_src^-1), and the per-view scores are fused

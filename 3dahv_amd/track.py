@@ -24,11 +24,19 @@ group every rank runs the same tracker on the same inputs and computes the same 
 The random walk (``motion="walk"``, the default) holds a pose that moves about sigma per frame; a pose that moves steadily
 faster needs ``motion="constant_velocity"``: the particles whose velocity matches the motion are the ones that score, so the
 filter learns the velocity from the scores alone.
-Not built: sigma adapted from the entropy, and the tracker inside the multi-view path (``ops.verify_views``).
+Per frame the tracker reports the arg-max of that frame's own scores, which is wrong on a frame that is not a good view of
+the object (occluded, blurred, a cut to something else).  ``history=H`` keeps the particle sets and scores of the last H frames
+in a ring and runs one Viterbi step per frame over it (``smooth_step``, after ``verify_pair``): MAP sequence estimation over
+the particle history (Godsill, Doucet and West 2001).  ``smoothed()`` backtraces the most probable trajectory; a frame whose
+scores disagree with its neighbours is bridged by the motion prior, or left by paying ``smooth_jump``.  Smoothing observes and
+never steers: every ``TrackStep`` is the same bytes with and without it.
+Not built: sigma adapted from the entropy, the tracker inside the multi-view path (``ops.verify_views``), forward-backward
+marginal smoothing, and the velocity-noise term of the constant-velocity transition (the smoother's transition is pose-only).
 """
 from __future__ import annotations
 
 import collections
+import math
 from typing import Optional
 
 import torch
@@ -66,6 +74,16 @@ class PoseTracker:
     Slot 0 carries the previous arg-max bit for bit and a score is a function of (volumes, weights, R) alone, so on an
     unchanged frame the reported score never decreases.
 
+    ``history=H >= 2`` (``backend`` then also provides ``smooth_step`` and ``smooth_backtrace``): the tracker owns a ring of H
+    frames (``ops.smooth_history``) and every step ends with ``smooth_step`` on the step's particles and scores -- with the
+    constant-velocity model also its velocities and the damping, so that a transition is measured from the pose a particle
+    predicts.  ``smooth_sigma_deg`` is the scale of the transition (None: ``sigma_deg``, and sqrt(sigma_deg^2 + sigma_vel_deg^2)
+    with ``motion="constant_velocity"``), ``smooth_jump`` the price, in nats, of an arbitrary jump.  ``smoothed(frames)`` returns
+    the ``SmoothedPath(idx (B,F), R (B,F,3,3))`` over the last ``min(frames, steps since init, H)`` frames, oldest first: the
+    fixed-lag pose of frame t - L is ``path.R[:, -1 - L]``.  ``init`` restarts the counter, which hides every older slot; the
+    set ``init`` scores is not recorded (the first frame of the path is the first ``step``).  ``history=0``: none of this, the
+    calls of a step are the previous ones.
+
     ``use_graph=True`` (HIP backend only; refused with a ``backend`` or on the CPU): the first step after ``init`` reads the N0-sized set and runs eagerly; the two halves of
     the ping-pong are then captured as one hipGraph each, by the second and the third step, and every later step replays the
     graph of its half.  Each graph is the linear chain of the step's launches.  The two capturing steps synchronise with the
@@ -77,7 +95,7 @@ class PoseTracker:
                  n_fresh: int = 0, temperature: float = 0.02, max_angle_deg: Optional[float] = None, batch: int = 1,
                  seed: int = 0, posterior: bool = False, mode_angle_deg: float = 15.0, use_graph: bool = False, backend=None,
                  motion: str = "walk", sigma_vel_deg: float = 1.0, damping: float = 1.0, max_speed_deg: Optional[float] = None,
-                 coast: bool = True):
+                 coast: bool = True, history: int = 0, smooth_sigma_deg: Optional[float] = None, smooth_jump: float = 8.0):
         dev = W1.device
         self.ops = ops if backend is None else backend
         self.W1, self.W2, self.b2 = W1, W2, b2
@@ -103,6 +121,16 @@ class PoseTracker:
         ops._unit_interval(self.damping, "damping")
         self.temperature = float(temperature)
         ops.inverse_temperature(self.temperature)     # raises unless finite and > 0
+        self.history = int(history)
+        if self.history != 0 and not 2 <= self.history < (1 << 31):
+            raise RuntimeError("history = %d: 0 (no smoothing) or at least 2 frames" % self.history)
+        if self.history and not (hasattr(self.ops, "smooth_step") and hasattr(self.ops, "smooth_backtrace")):
+            raise RuntimeError("history = %d needs a backend that provides smooth_step and smooth_backtrace" % self.history)
+        if smooth_sigma_deg is None:
+            smooth_sigma_deg = self.sigma_deg if motion == "walk" else math.hypot(self.sigma_deg, self.sigma_vel_deg)
+        self.smooth_sigma_deg, self.smooth_jump = float(smooth_sigma_deg), ops._jump(smooth_jump)
+        if self.history and not ops._angle_rad(self.smooth_sigma_deg, "smooth_sigma_deg") > 0.0:
+            raise RuntimeError("smooth_sigma_deg = %r must be > 0" % (smooth_sigma_deg,))
         self.seed = int(seed)
         self.posterior = bool(posterior)
         self.mode_angle_deg = float(mode_angle_deg)
@@ -128,6 +156,8 @@ class PoseTracker:
         self._ws0 = None                                                   # first step: draws from the N0-sized set
         self._pstate = ops.pose_posterior_state(B, 1, dev) if hip and self.posterior else None
         self._pws = ops.pose_posterior_workspace(B, M, 1, dev) if hip and self.posterior else None
+        # the smoother's ring (any backend: plain tensors); after init the counter is 0 and the first step records frame 1
+        self._hist = ops.smooth_history(B, M, self.history, dev, velocities=motion != "walk") if self.history else None
         self._cur = None      # (R, scores, key) of the set the next step draws from
         self._n = 0           # steps since init
         self._static = None
@@ -201,7 +231,26 @@ class PoseTracker:
         # the winner sits in a fresh slot (slot 0 is the elite, and slot 1 the coasting one, even when every slot is fresh)
         reacq = torch.ge(idx, max(self.M - self.n_fresh, first), out=self._reacq[p])
         post = self._posterior(scores, R, R_map, self._pstate, self._pws)
+        if self._hist is not None:   # observes the step, changes none of its outputs
+            o.smooth_step(self._hist, R, scores, self._step, self.temperature, self.smooth_sigma_deg, jump=self.smooth_jump,
+                          V=self._V[p] if self._V is not None else None, damping=self.damping, first_step=1)
         return TrackStep(score, idx, R_map, R, scores, draws, *post, reacq)
+
+    @torch.no_grad()
+    def smoothed(self, frames: Optional[int] = None, out=None):
+        """The MAP trajectory over the last ``min(frames, steps since init, history)`` frames (``frames`` None: as many as there
+        are): ``ops.SmoothedPath(idx (B,F) int64, R (B,F,3,3))``, oldest first, the last column the current frame.  One launch,
+        no host synchronisation; ``out``: a ``SmoothedPath`` of that size to write into."""
+        if self._hist is None:
+            raise RuntimeError("smoothed() needs a tracker built with history >= 2")
+        if self._n < 1:
+            raise RuntimeError("smoothed() before the first step: nothing has been recorded since init")
+        F = min(self._n, self.history)
+        if frames is not None:
+            if int(frames) < 1:
+                raise RuntimeError("frames = %d must be at least 1" % int(frames))
+            F = min(F, int(frames))
+        return self.ops.smooth_backtrace(self._hist, self._step, frames=F, first_step=1, out=out)
 
     @torch.no_grad()
     def step(self, vol_src: Optional[torch.Tensor] = None, vol_tgt: Optional[torch.Tensor] = None) -> TrackStep:
