@@ -133,6 +133,10 @@ SIGNATURES["ahv_track_advance"] = (_int, [ctypes.c_uint64, _vp, _int, _vp, _vp])
 SIGNATURES["ahv_smooth_step_f32"] = (_int, [_vp, _vp, _vp, _vp, _i64, _int, _i64, _i64] + [ctypes.c_float] * 4 + [_vp] * 5)
 # (hist_R, hist_delta, hist_back, step: DEVICE int64, first_step, B, M, H, F, path_idx, path_R, stream)
 SIGNATURES["ahv_smooth_backtrace_f32"] = (_int, [_vp, _vp, _vp, _vp, _i64, _int, _i64, _i64, _i64, _vp, _vp, _vp])
+# (R_cur, scores, step: DEVICE int64, first_step, B, M, H, beta, sigma_rad, jump, hist_R, hist_P or NULL, hist_alpha, hist_emit, stream)
+SIGNATURES["ahv_marginal_step_f32"] = (_int, [_vp, _vp, _vp, _i64, _int, _i64, _i64] + [ctypes.c_float] * 3 + [_vp] * 5)
+# (hist_R, hist_P or NULL, hist_alpha, hist_emit, step: DEVICE int64, first_step, B, M, H, F, sigma_rad, jump, logw, idx, R, stream)
+SIGNATURES["ahv_marginal_smooth_f32"] = (_int, [_vp] * 5 + [_i64, _int, _i64, _i64, _i64, ctypes.c_float, ctypes.c_float] + [_vp] * 4)
 
 # measurement / developer entry points (include/ahv_diag.h): not part of the drop-in boundary
 DIAG_SIGNATURES = {

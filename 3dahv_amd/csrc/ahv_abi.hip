@@ -62,6 +62,10 @@ hipError_t launch_smooth_step(const float*, const float*, const float*, const in
                               float, float, float*, float*, float*, int32_t*, hipStream_t);
 hipError_t launch_smooth_backtrace(const float*, const float*, const int32_t*, const int64_t*, int64_t, int, int64_t, int64_t,
                                    int64_t, int64_t*, float*, hipStream_t);
+hipError_t launch_marginal_step(const float*, const float*, const int64_t*, int64_t, int, int64_t, int64_t, float, float, float,
+                                const float*, const float*, float*, float*, hipStream_t);
+hipError_t launch_marginal_smooth(const float*, const float*, const float*, const float*, const int64_t*, int64_t, int, int64_t,
+                                  int64_t, int64_t, float, float, float*, int64_t*, float*, hipStream_t);
 hipError_t launch_score_backward(const float*, const float*, const float*, int64_t, const float*, const float*,
                                  const float*, int, int64_t, const float*, float*, float*, float*, float*, float*,
                                  float*, float*, int, hipStream_t, bool);
@@ -1064,6 +1068,50 @@ int ahv_smooth_backtrace_f32(const float* hist_R, const float* hist_delta, const
     hipError_t e = ahv::launch_smooth_backtrace(hist_R, hist_delta, hist_back, step, first_step, B, M, H, F, path_idx, path_R,
                                                 static_cast<hipStream_t>(stream));
     if (e != hipSuccess) return hip_fail("smooth_backtrace: launch", e);
+    return AHV_OK;
+}
+
+// ---- pose tracking: forward-backward marginal smoothing over the same ring --------------------------------------------
+// sigma and jump as ahv_smooth_step_f32 checks them; *inv4s2 is the kernels' factor.
+static int marginal_transition(const char* who, float sigma_rad, float jump, float* inv4s2)
+{
+    const double k = 1.0 / (4.0 * (double)sigma_rad * (double)sigma_rad);
+    if (!(sigma_rad > 0.0f && sigma_rad < __builtin_inff() && k < 3.0e38))
+        return fail(AHV_EINVAL, "%s: sigma = %g must be finite and > 0, with 1/(4 sigma^2) inside a float", who, (double)sigma_rad);
+    if (!(jump >= 0.0f)) return fail(AHV_EINVAL, "%s: jump = %g must be >= 0 (+inf: no floor)", who, (double)jump);
+    *inv4s2 = (float)k;
+    return AHV_OK;
+}
+
+int ahv_marginal_step_f32(const float* R_cur, const float* scores, const int64_t* step, int64_t first_step, int B, int64_t M,
+                          int64_t H, float beta, float sigma_rad, float jump, const float* hist_R, const float* hist_P,
+                          float* hist_alpha, float* hist_emit, void* stream)
+{
+    if (int rc = smooth_sizes("marginal_step", B, M, H)) return rc;
+    if (!R_cur || !scores || !step || !hist_R || !hist_alpha || !hist_emit)
+        return fail(AHV_EINVAL, "marginal_step: null pointer (R_cur, scores, step, hist_R, hist_alpha and hist_emit are required)");
+    if (!(beta > 0.0f && beta < __builtin_inff())) return fail(AHV_EINVAL, "marginal_step: beta = %g must be finite and > 0", (double)beta);
+    float inv4s2;
+    if (int rc = marginal_transition("marginal_step", sigma_rad, jump, &inv4s2)) return rc;
+    hipError_t e = ahv::launch_marginal_step(R_cur, scores, step, first_step, B, M, H, beta, inv4s2, jump, hist_R, hist_P, hist_alpha,
+                                             hist_emit, static_cast<hipStream_t>(stream));
+    if (e != hipSuccess) return hip_fail("marginal_step: launch", e);
+    return AHV_OK;
+}
+
+int ahv_marginal_smooth_f32(const float* hist_R, const float* hist_P, const float* hist_alpha, const float* hist_emit,
+                            const int64_t* step, int64_t first_step, int B, int64_t M, int64_t H, int64_t F, float sigma_rad,
+                            float jump, float* logw, int64_t* idx, float* R, void* stream)
+{
+    if (int rc = smooth_sizes("marginal_smooth", B, M, H)) return rc;
+    if (F < 1 || F > H) return fail(AHV_EINVAL, "marginal_smooth: F = %lld outside 1..H = %lld", (long long)F, (long long)H);
+    if (!hist_R || !hist_alpha || !hist_emit || !step || !logw || !idx || !R)
+        return fail(AHV_EINVAL, "marginal_smooth: null pointer (only hist_P may be NULL)");
+    float inv4s2;
+    if (int rc = marginal_transition("marginal_smooth", sigma_rad, jump, &inv4s2)) return rc;
+    hipError_t e = ahv::launch_marginal_smooth(hist_R, hist_P, hist_alpha, hist_emit, step, first_step, B, M, H, F, inv4s2, jump, logw,
+                                               idx, R, static_cast<hipStream_t>(stream));
+    if (e != hipSuccess) return hip_fail("marginal_smooth: launch", e);
     return AHV_OK;
 }
 

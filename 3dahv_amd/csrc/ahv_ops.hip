@@ -1015,6 +1015,264 @@ __global__ __launch_bounds__(256) void smooth_backtrace_kernel(const float* __re
     }
 }
 
+// ---------------------------------------------------------------------------------
+// Marginal smoothing over the same ring (ahv_marginal_step_f32 / ahv_marginal_smooth_f32, include/ahv.h): the sum-product
+// recursions of the hidden-Markov model whose max-product recursion is smooth_step_kernel -- the same transition, the same
+// decomposition, log-sum-exp in place of max.  marginal_walk is the one pairwise pass of both directions: a workgroup owns
+// kSmoothSucc "owner" rows of one sample (nine entries in registers) and the "other" rows go through LDS in the tiles of
+// smooth_step_kernel, the tenth float of a row being the other row's log-weight minus the largest finite one, NaN for a dead
+// row and past the end.  A lane keeps a running (max, sum) pair over the rows of its group, met in increasing
+// index; a candidate that is NaN or -inf is skipped explicitly (expf(NaN) would poison the sum, where the Viterbi compare
+// never selected it).  The pairs merge as (max, sum) pairs in a fixed order: lanes 16 apart, lanes 32 apart, then waves 1, 2, 3
+// onto wave 0 in LDS.  The running maximum is the data's own, not a fixed offset: with jump = +inf and far clusters every
+// term may sit near -365 and still sum to a finite value.  Bitwise reproducible and independent of B; NOT independent of the
+// split (a sum, unlike a max, depends on the order), so the 16 x 16 split of the rows is part of the contract.
+//   forward   owners R_cur, others P/R and alpha of the previous slot: alpha_j = a_j + LSE_i[(alpha_i - m) + w_ij]
+//   backward  owners P/R of slot tau, others R and g = emit + beta of slot tau + 1: beta_i = LSE_j[w_ij + (g_j - m')]
+// ---------------------------------------------------------------------------------
+// One more term of a running log-sum-exp, sum = sum_k exp(x_k - mx), from (-inf, 0).  x is finite: the caller skips NaN and -inf.
+__device__ __forceinline__ void lse_add(float& mx, float& sum, float x)
+{
+    const float d = x - mx;  // +inf at the first term: e = 0, sum = 1
+    const float e = expf(-fabsf(d));
+    sum = d > 0.0f ? fmaf(sum, e, 1.0f) : sum + e;
+    mx = fmaxf(mx, x);
+}
+
+// (max, sum) merge; an empty side is (-inf, 0).
+__device__ __forceinline__ void lse_merge(float& mx, float& sum, float omx, float osum)
+{
+    const float nm = fmaxf(mx, omx);
+    if (nm > -__builtin_inff()) {
+        sum = sum * expf(mx - nm) + osum * expf(omx - nm);
+        mx = nm;
+    }
+}
+
+// The pairwise pass.  r: the owner row of this lane; other: the other slot's rows (nine floats each); the log-weight of other
+// row i is lw_a[i] + (lw_b ? lw_b[i] : 0), alive iff finite.  Returns whether any other row is alive (uniform over the
+// workgroup); then threads 0..15 hold the merged (mx, sum) of their owner, sum == 0 when no edge reaches it.
+__device__ __forceinline__ bool marginal_walk(const float (&r)[9], const float* __restrict__ other, const float* __restrict__ lw_a,
+                                              const float* __restrict__ lw_b, int M, float inv4s2, float jump, float* tile,
+                                              float (*part_m)[kSmoothSucc], float (*part_s)[kSmoothSucc], float* wave_max,
+                                              float& mx, float& sum)
+{
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int group = 4 * wave + (lane >> 4);
+    float m = -__builtin_inff();
+    for (long i = tid; i < M; i += 256) {
+        const float d = lw_a[i] + (lw_b ? lw_b[i] : 0.0f);
+        if (finite_f(d)) m = fmaxf(m, d);
+    }
+#pragma unroll
+    for (int s = 32; s >= 1; s >>= 1) m = fmaxf(m, __shfl_xor(m, s, 64));
+    if (lane == 0) wave_max[wave] = m;
+    __syncthreads();
+    m = fmaxf(fmaxf(wave_max[0], wave_max[1]), fmaxf(wave_max[2], wave_max[3]));
+    mx = -__builtin_inff();
+    sum = 0.0f;
+    if (!finite_f(m)) return false;
+
+    const float neg_jump = -jump;
+    float stage[10];
+    const auto load_row = [&](long i) {
+#pragma unroll
+        for (int k = 0; k < 9; ++k) stage[k] = 0.0f;
+        stage[9] = __builtin_nanf("");
+        if (i < M) {
+            const float* src = other + i * 9;
+#pragma unroll
+            for (int k = 0; k < 9; ++k) stage[k] = src[k];
+            const float v = lw_a[i] + (lw_b ? lw_b[i] : 0.0f);
+            if (finite_f(v)) stage[9] = v - m;
+        }
+    };
+    load_row(tid);
+    for (long i0 = 0; i0 < M; i0 += kSmoothTile) {
+        __syncthreads();  // the previous tile has been read by every wave
+        f32x4* dst = reinterpret_cast<f32x4*>(tile + tid * kSmoothRow);
+        dst[0] = f32x4{stage[0], stage[1], stage[2], stage[3]};
+        dst[1] = f32x4{stage[4], stage[5], stage[6], stage[7]};
+        dst[2] = f32x4{stage[8], stage[9], 0.0f, 0.0f};
+        __syncthreads();
+        if (i0 + kSmoothTile < M) load_row(i0 + kSmoothTile + tid);  // in flight while this tile is walked
+#pragma unroll 4
+        for (int p = 0; p < kSmoothTile / 16; ++p) {
+            const int row = 16 * p + group;
+            const f32x4 a = *reinterpret_cast<const f32x4*>(tile + row * kSmoothRow);
+            const f32x4 c = *reinterpret_cast<const f32x4*>(tile + row * kSmoothRow + 4);
+            const f32x4 d = *reinterpret_cast<const f32x4*>(tile + row * kSmoothRow + 8);
+            const float e0 = a[0] - r[0], e1 = a[1] - r[1], e2 = a[2] - r[2], e3 = a[3] - r[3], e4 = c[0] - r[4];
+            const float e5 = c[1] - r[5], e6 = c[2] - r[6], e7 = c[3] - r[7], e8 = d[0] - r[8];
+            float q = e0 * e0;
+            q = fmaf(e1, e1, q); q = fmaf(e2, e2, q); q = fmaf(e3, e3, q); q = fmaf(e4, e4, q);
+            q = fmaf(e5, e5, q); q = fmaf(e6, e6, q); q = fmaf(e7, e7, q); q = fmaf(e8, e8, q);
+            const float w = -(q * inv4s2);
+            const float x = d[1] + (w < neg_jump ? neg_jump : w);  // NaN for a dead row, a row past the end and a NaN matrix
+            if (x > -__builtin_inff()) lse_add(mx, sum, x);        // (false for NaN)
+        }
+    }
+    // the four groups of a wave (lanes succ, succ + 16, + 32, + 48), then the four waves
+#pragma unroll
+    for (int s = 16; s <= 32; s <<= 1) {
+        const float om = __shfl_xor(mx, s, 64), os = __shfl_xor(sum, s, 64);
+        // both lanes of a pair must compute the same bytes: the lower lane's pair first
+        if (lane & s) { float tm = om, ts = os; lse_merge(tm, ts, mx, sum); mx = tm; sum = ts; }
+        else lse_merge(mx, sum, om, os);
+    }
+    if (lane < kSmoothSucc) { part_m[wave][lane] = mx; part_s[wave][lane] = sum; }
+    __syncthreads();
+    if (tid < kSmoothSucc) {
+#pragma unroll
+        for (int w = 1; w < 4; ++w) lse_merge(mx, sum, part_m[w][lane], part_s[w][lane]);
+    }
+    return true;
+}
+
+// Forward step: alpha and emit of slot t mod H from the previous slot.  Reads hist_R / hist_P of slot t - 1 only.
+__global__ __launch_bounds__(256) void marginal_step_kernel(const float* __restrict__ R_cur, const float* __restrict__ scores,
+                                                            const long long* __restrict__ step, long long first_step, int M,
+                                                            long long H, float beta, float inv4s2, float jump,
+                                                            const float* __restrict__ hist_R, const float* __restrict__ hist_P,
+                                                            float* __restrict__ hist_alpha, float* __restrict__ hist_emit)
+{
+    __shared__ __attribute__((aligned(16))) float tile[kSmoothTile * kSmoothRow];
+    __shared__ float part_m[4][kSmoothSucc], part_s[4][kSmoothSucc], wave_max[4];
+    const int tid = threadIdx.x, succ = tid & (kSmoothSucc - 1);
+    const long b = blockIdx.y, nb = gridDim.y;
+    const long long t = *step;
+    const long slot = (long)(((t % H) + H) % H), prev = (long)((((t - 1) % H) + H) % H);
+    const long row_cur = (slot * nb + b) * (long)M, row_prev = (prev * nb + b) * (long)M;
+    const int j0 = blockIdx.x * kSmoothSucc;
+    const int rows = min(kSmoothSucc, M - j0);
+    const bool live = succ < rows;
+    const int j = j0 + (live ? succ : 0);
+    const float* rc = R_cur + (b * (long)M + j) * 9;
+    float r[9];
+#pragma unroll
+    for (int k = 0; k < 9; ++k) r[k] = rc[k];
+    float mx = -__builtin_inff(), sum = 0.0f;
+    bool has_prev = t > first_step;
+    if (has_prev)
+        has_prev = marginal_walk(r, (hist_P ? hist_P : hist_R) + row_prev * 9, hist_alpha + row_prev, nullptr, M, inv4s2, jump, tile,
+                                 part_m, part_s, wave_max, mx, sum);
+    if (tid < kSmoothSucc && live) {
+        const float s = scores[b * (long)M + j];
+        float emit = -__builtin_inff(), alpha = -__builtin_inff();
+        if (finite_f(s)) {
+            emit = beta * s;
+            if (!has_prev) alpha = emit;
+            else if (sum > 0.0f) alpha = emit + (mx + logf(sum));
+        }
+        hist_alpha[row_cur + j] = alpha;
+        hist_emit[row_cur + j] = emit;
+    }
+}
+
+// Backward step for frame tau = t - back, output column f = F - 1 - back: beta(tau) into logw[b][f] from slot tau + 1, whose
+// beta is logw[b][f + 1] (zero for the newest frame, back == 1).  A frame before first_step is left to the finish kernel.
+__global__ __launch_bounds__(256) void marginal_backward_kernel(const float* __restrict__ hist_R, const float* __restrict__ hist_P,
+                                                                const float* __restrict__ hist_emit,
+                                                                const long long* __restrict__ step, long long first_step, int M,
+                                                                long long H, int F, int back, float inv4s2, float jump,
+                                                                float* __restrict__ logw)
+{
+    __shared__ __attribute__((aligned(16))) float tile[kSmoothTile * kSmoothRow];
+    __shared__ float part_m[4][kSmoothSucc], part_s[4][kSmoothSucc], wave_max[4];
+    const int tid = threadIdx.x, succ = tid & (kSmoothSucc - 1);
+    const long b = blockIdx.y, nb = gridDim.y;
+    const long long tau = *step - back;
+    if (tau < first_step) return;  // the whole workgroup
+    const long slot = (long)(((tau % H) + H) % H), next = (long)((((tau + 1) % H) + H) % H);
+    const long row_own = (slot * nb + b) * (long)M, row_next = (next * nb + b) * (long)M;
+    const int f = F - 1 - back;
+    float* out = logw + (b * (long)F + f) * (long)M;
+    const float* beta_next = back == 1 ? nullptr : out + M;
+    const int j0 = blockIdx.x * kSmoothSucc;
+    const int rows = min(kSmoothSucc, M - j0);
+    const bool live = succ < rows;
+    const int j = j0 + (live ? succ : 0);
+    const float* rc = (hist_P ? hist_P : hist_R) + (row_own + j) * 9;
+    float r[9];
+#pragma unroll
+    for (int k = 0; k < 9; ++k) r[k] = rc[k];
+    float mx, sum;
+    const bool has_next = marginal_walk(r, hist_R + row_next * 9, hist_emit + row_next, beta_next, M, inv4s2, jump, tile, part_m,
+                                        part_s, wave_max, mx, sum);
+    if (tid < kSmoothSucc && live) out[j] = !has_next ? 0.0f : (sum > 0.0f ? mx + logf(sum) : -__builtin_inff());
+}
+
+// Finish: one workgroup per (sample, frame).  x_i = alpha_i + beta_i (beta = 0 in the newest frame), log gamma_i = x_i - LSE x
+// written over beta, the first arg-max of the written values and its pose.  Thread k sums rows k, k + 256, ... in increasing
+// order; the pairs merge lane by lane (xor 1, 2, ..., 32, the lower lane's pair first) and then wave by wave.
+__global__ __launch_bounds__(256) void marginal_finish_kernel(const float* __restrict__ hist_R, const float* __restrict__ hist_alpha,
+                                                              const long long* __restrict__ step, long long first_step, int M,
+                                                              long long H, int F, float* __restrict__ logw,
+                                                              long long* __restrict__ out_idx, float* __restrict__ out_R)
+{
+    __shared__ float part_m[4], part_s[4];
+    __shared__ int part_i[4];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int f = blockIdx.x;
+    const long b = blockIdx.y, nb = gridDim.y;
+    const long long tau = *step - (F - 1 - f);
+    const long o = b * (long)F + f;
+    float* lw = logw + o * (long)M;
+    const bool newest = f == F - 1;
+    const float ninf = -__builtin_inff();
+    long row = 0;
+    int best_i = -1;
+    if (tau >= first_step) {
+        row = ((long)(((tau % H) + H) % H) * nb + b) * (long)M;
+        float mx = ninf, sum = 0.0f;
+        for (long i = tid; i < M; i += 256) {
+            const float x = hist_alpha[row + i] + (newest ? 0.0f : lw[i]);
+            if (finite_f(x)) lse_add(mx, sum, x);
+        }
+#pragma unroll
+        for (int s = 1; s <= 32; s <<= 1) {
+            const float om = __shfl_xor(mx, s, 64), os = __shfl_xor(sum, s, 64);
+            if (lane & s) { float tm = om, ts = os; lse_merge(tm, ts, mx, sum); mx = tm; sum = ts; }
+            else lse_merge(mx, sum, om, os);
+        }
+        if (lane == 0) { part_m[wave] = mx; part_s[wave] = sum; }
+        __syncthreads();
+        mx = part_m[0]; sum = part_s[0];
+#pragma unroll
+        for (int w = 1; w < 4; ++w) lse_merge(mx, sum, part_m[w], part_s[w]);
+        __syncthreads();  // part_m is reused below
+        if (sum > 0.0f) {
+            const float log_z = mx + logf(sum);
+            float best = ninf;
+            for (long i = tid; i < M; i += 256) {
+                const float x = hist_alpha[row + i] + (newest ? 0.0f : lw[i]);
+                const float g = finite_f(x) ? x - log_z : ninf;
+                lw[i] = g;
+                if (g > best) { best = g; best_i = (int)i; }  // increasing i: the first one of this thread
+            }
+#pragma unroll
+            for (int s = 32; s >= 1; s >>= 1) {
+                const float ov = __shfl_xor(best, s, 64);
+                const int oi = __shfl_xor(best_i, s, 64);
+                if (oi >= 0 && (best_i < 0 || ov > best || (ov == best && oi < best_i))) { best = ov; best_i = oi; }
+            }
+            if (lane == 0) { part_m[wave] = best; part_i[wave] = best_i; }
+            __syncthreads();
+            best = part_m[0]; best_i = part_i[0];
+#pragma unroll
+            for (int w = 1; w < 4; ++w) {
+                const float ov = part_m[w];
+                const int oi = part_i[w];
+                if (oi >= 0 && (best_i < 0 || ov > best || (ov == best && oi < best_i))) { best = ov; best_i = oi; }
+            }
+        }
+    }
+    if (best_i < 0)
+        for (long i = tid; i < M; i += 256) lw[i] = ninf;
+    if (tid == 0) out_idx[o] = best_i;
+    if (tid < 9) out_R[o * 9 + tid] = best_i >= 0 ? hist_R[(row + best_i) * 9 + tid] : (tid % 4 == 0 ? 1.0f : 0.0f);
+}
+
 // Super-Fibonacci SO(3) grid (Alexa, CVPR 2022): point i of n is the quaternion
 // (sqrt(t) sin a, sqrt(t) cos a, sqrt(1-t) sin b, sqrt(1-t) cos b), t = (i + 1/2)/n, a = 2 pi (i + 1/2)/sqrt(2),
 // b = 2 pi (i + 1/2)/psi.  The angles reach 10^6 rad, so their turn fraction is taken in fp64 before sin/cos.
@@ -1170,6 +1428,36 @@ hipError_t launch_smooth_backtrace(const float* hist_R, const float* hist_delta,
     hipLaunchKernelGGL(smooth_backtrace_kernel, dim3((unsigned)B), dim3(256), 0, stream, hist_R, hist_delta,
                        reinterpret_cast<const int*>(hist_back), reinterpret_cast<const long long*>(step), (long long)first_step,
                        (int)M, (long long)H, (int)F, reinterpret_cast<long long*>(path_idx), path_R);
+    return hipGetLastError();
+}
+
+hipError_t launch_marginal_step(const float* R_cur, const float* scores, const int64_t* step, int64_t first_step, int B, int64_t M,
+                                int64_t H, float beta, float inv4s2, float jump, const float* hist_R, const float* hist_P,
+                                float* hist_alpha, float* hist_emit, hipStream_t stream)
+{
+    hipLaunchKernelGGL(marginal_step_kernel, dim3((unsigned)((M + kSmoothSucc - 1) / kSmoothSucc), (unsigned)B), dim3(256), 0, stream,
+                       R_cur, scores, reinterpret_cast<const long long*>(step), (long long)first_step, (int)M, (long long)H, beta,
+                       inv4s2, jump, hist_R, hist_P, hist_alpha, hist_emit);
+    return hipGetLastError();
+}
+
+// F - 1 backward launches (frames t - 1, t - 2, ...: each reads the beta the launch before wrote) and the finish, in stream
+// order: a linear chain under capture.
+hipError_t launch_marginal_smooth(const float* hist_R, const float* hist_P, const float* hist_alpha, const float* hist_emit,
+                                  const int64_t* step, int64_t first_step, int B, int64_t M, int64_t H, int64_t F, float inv4s2,
+                                  float jump, float* logw, int64_t* idx, float* R, hipStream_t stream)
+{
+    const dim3 grid((unsigned)((M + kSmoothSucc - 1) / kSmoothSucc), (unsigned)B);
+    for (int64_t back = 1; back < F; ++back) {
+        hipLaunchKernelGGL(marginal_backward_kernel, grid, dim3(256), 0, stream, hist_R, hist_P, hist_emit,
+                           reinterpret_cast<const long long*>(step), (long long)first_step, (int)M, (long long)H, (int)F, (int)back,
+                           inv4s2, jump, logw);
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return e;
+    }
+    hipLaunchKernelGGL(marginal_finish_kernel, dim3((unsigned)F, (unsigned)B), dim3(256), 0, stream, hist_R, hist_alpha,
+                       reinterpret_cast<const long long*>(step), (long long)first_step, (int)M, (long long)H, (int)F, logw,
+                       reinterpret_cast<long long*>(idx), R);
     return hipGetLastError();
 }
 

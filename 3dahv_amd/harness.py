@@ -235,7 +235,8 @@ def evaluate_category(cfg, model, sequences: Iterable[dict], num_frames: int = 2
 
 @torch.no_grad()
 def track_sequence(model, item: dict, tracker, ref: int = 0, proposals: Optional[torch.Tensor] = None, device=None,
-                   encoder_fn: Optional[Callable] = None, row_vector_R: bool = False, smoothed: bool = False) -> dict:
+                   encoder_fn: Optional[Callable] = None, row_vector_R: bool = False, smoothed: bool = False,
+                   marginals: bool = False) -> dict:
     """Track ONE sequence with a ``track.PoseTracker`` (batch 1).  ``item`` is what ``SyntheticSequences`` or
     ``co3d.Co3dSequences`` yields.  Frame ``ref`` is the reference view; every other frame is tracked in order: per frame the
     encoder runs on (reference, frame) -- ``encoder_fn`` or ``model.forward_features`` for ``layer4`` inputs, else ``model`` --,
@@ -250,7 +251,12 @@ def track_sequence(model, item: dict, tracker, ref: int = 0, proposals: Optional
     ``use_graph=True`` synchronises on its own while it captures, on its second and third step).
     ``smoothed=True`` (a tracker built with ``history``): the result also has ``"smoothed"``, the MAP trajectory over the
     tracker's history at the end of the sequence -- ``{"frames", "idx" (F',), "R" (F',3,3), "err" (F',)}`` for the last
-    ``F' = min(steps, history)`` tracked frames (the frame given to ``init`` is not recorded); it costs a second host copy."""
+    ``F' = min(steps, history)`` tracked frames (the frame given to ``init`` is not recorded); it costs a second host copy.
+    ``marginals=True`` (a tracker built with ``history`` and ``marginals=True``): the result also has ``"marginals"``, shaped
+    like ``"smoothed"`` from ``tracker.smoothed_marginals()`` -- ``idx`` and ``R`` the most probable particle of each frame's
+    smoothed marginal, ``err`` its error -- and, when the tracker's backend has ``pose_posterior``, ``"R_mean" (F',3,3)``,
+    ``"err_mean"``, ``"spread_deg"``, ``"mode_mass"`` and ``"entropy"`` (F',): the marginal-weighted mean pose and its error, the
+    spread, the mass within the tracker's ``mode_angle_deg`` of ``R`` and the entropy of the marginal."""
     if tracker.B != 1:
         raise RuntimeError("track_sequence tracks one sequence: the tracker must have batch = 1, got %d" % tracker.B)
     if device is None:
@@ -290,6 +296,26 @@ def track_sequence(model, item: dict, tracker, ref: int = 0, proposals: Optional
             n_s = path.R.shape[1]
             s_err = geodesic_deg(path.R[0], torch.stack(truth[-n_s:]))
             out["smoothed"] = {"frames": order[-n_s:], "idx": path.idx[0].cpu(), "R": path.R[0].cpu(), "err": s_err.cpu()}
+    if marginals:
+        with_post = hasattr(tracker.ops, "pose_posterior")
+        if len(order) < 2:
+            if not getattr(tracker, "marginals", False):
+                raise RuntimeError("marginals=True needs a tracker built with history >= 2 and marginals=True")
+            rec = {"frames": [], "idx": torch.zeros(0, dtype=torch.int64), "R": torch.zeros(0, 3, 3), "err": torch.zeros(0)}
+            if with_post:
+                rec.update(R_mean=torch.zeros(0, 3, 3), err_mean=torch.zeros(0), spread_deg=torch.zeros(0), mode_mass=torch.zeros(0),
+                           entropy=torch.zeros(0))
+        else:
+            got = tracker.smoothed_marginals(posterior=with_post)
+            marg = got[0] if with_post else got
+            n_s = marg.R.shape[1]
+            gt = torch.stack(truth[-n_s:])
+            rec = {"frames": order[-n_s:], "idx": marg.idx[0].cpu(), "R": marg.R[0].cpu(), "err": geodesic_deg(marg.R[0], gt).cpu()}
+            if with_post:
+                R_mean, spread, mass, entropy = got[1:]
+                rec.update(R_mean=R_mean[0].cpu(), err_mean=geodesic_deg(R_mean[0], gt).cpu(), spread_deg=spread[0].cpu(),
+                           mode_mass=mass[0].cpu(), entropy=entropy[0].cpu())
+        out["marginals"] = rec
     return out
 
 

@@ -1436,6 +1436,107 @@ def smooth_backtrace(history: SmoothHistory, step: torch.Tensor, frames: int | N
     return out
 
 
+# ---- marginal smoothing ----------------------------------------------------------------------------------------------
+# Forward-backward marginals over the ring of ``smooth_step`` (``ahv_marginal_step_f32`` / ``ahv_marginal_smooth_f32``,
+# include/ahv.h): the sum-product recursions of the same hidden-Markov model.  The output is a row of log-weights per frame,
+# which ``pose_posterior`` takes as it is at ``temperature=1``.
+
+MarginalHistory = collections.namedtuple("MarginalHistory", ["alpha", "emit"])
+SmoothedMarginals = collections.namedtuple("SmoothedMarginals", ["logw", "idx", "R"])
+
+
+def marginal_history(B: int, M: int, H: int, device) -> MarginalHistory:
+    """The forward ring of ``marginal_step`` beside a ``smooth_history(B, M, H)``: ``alpha`` and ``emit``, both ``(H,B,M)``
+    float32.  Not initialised: a step at ``first_step`` reads none of it and ``marginal_smooth`` never looks behind it."""
+    B, M, H = int(B), _draws(M), int(H)
+    if not 1 <= B <= 65535:
+        raise RuntimeError("B = %d outside 1..65535" % B)
+    if not 2 <= H < (1 << 31):
+        raise RuntimeError("H = %d outside 2..2^31-1 (a frame and its predecessors live in different slots)" % H)
+    return MarginalHistory(torch.empty((H, B, M), dtype=torch.float32, device=device),
+                           torch.empty((H, B, M), dtype=torch.float32, device=device))
+
+
+def _marginal_ring(history, marg):
+    """``(H, B, M, dev)`` of the two rings after checking them against each other."""
+    if not isinstance(marg, MarginalHistory):
+        raise RuntimeError("marg must be the MarginalHistory of marginal_history()")
+    H, B, M, dev = _smooth_ring(history)
+    for name, t in (("alpha", marg.alpha), ("emit", marg.emit)):
+        if (not isinstance(t, torch.Tensor) or tuple(t.shape) != (H, B, M) or t.dtype != torch.float32 or not t.is_contiguous()
+                or t.device != dev):
+            raise RuntimeError("marg.%s must be a contiguous float32 tensor %s on %s (the sizes of history)" % (name, (H, B, M), dev))
+    return H, B, M, dev
+
+
+def _transition_scale(sigma_deg, jump):
+    sigma = _angle_rad(sigma_deg, "sigma_deg")
+    if not (sigma > 0.0 and 1.0 / (4.0 * sigma * sigma) < 3.0e38):
+        raise RuntimeError("sigma_deg = %r must be > 0 (and 1 / (4 sigma^2) must fit a float32)" % (sigma_deg,))
+    return sigma, _jump(jump)
+
+
+@torch.no_grad()
+def marginal_step(history: SmoothHistory, marg: MarginalHistory, R: torch.Tensor, scores: torch.Tensor, step: torch.Tensor,
+                  temperature: float, sigma_deg: float, jump: float = 8.0, first_step: int = 1) -> MarginalHistory:
+    """The forward step of the marginal smoother (``ahv_marginal_step_f32``, one launch) for the frame ``R (B,M,3,3)``,
+    ``scores (B,M)`` and ``t = step[0]`` (read ON THE DEVICE): ``emit_j = s_j / T`` and
+    ``alpha_j = emit_j + logsumexp_i [(alpha_i - m) + max(-|P_i - R_j|_F^2 / (4 sigma^2), -jump)]`` into slot ``t mod H`` of
+    ``marg``; a restart (``alpha = emit``) at ``t <= first_step`` and behind a frame without a live particle; -inf for a particle
+    whose score is not finite.  It READS slot ``t - 1`` of ``history.P`` (``history.R`` without velocities) and of ``marg.alpha``:
+    ``smooth_step`` must have recorded the previous frame.  It WRITES slot ``t`` of ``marg`` only, so for one frame it may run
+    before or after that frame's ``smooth_step``.  Same ``temperature``, ``sigma_deg``, ``jump`` and ``first_step`` as the
+    ``smooth_step`` calls.  No allocation, no host synchronisation.  Returns ``marg``."""
+    H, B, M, dev = _marginal_ring(history, marg)
+    _need_gpu(history.R, R, scores)
+    step = _step_counter(step, dev)
+    if tuple(R.shape) != (B, M, 3, 3) or tuple(scores.shape) != (B, M):
+        raise RuntimeError("R must be (B,M,3,3) = %s and scores (B,M) = %s, got %s and %s"
+                           % ((B, M, 3, 3), (B, M), tuple(R.shape), tuple(scores.shape)))
+    beta = inverse_temperature(temperature)
+    sigma, jump = _transition_scale(sigma_deg, jump)
+    Rc, sc = R.detach().contiguous(), scores.detach().contiguous()
+    _call(dev, "ahv_marginal_step_f32", Rc.data_ptr(), sc.data_ptr(), step.data_ptr(), int(first_step), B, M, H, beta, sigma, jump,
+          history.R.data_ptr(), history.P.data_ptr() if history.P is not None else None, marg.alpha.data_ptr(), marg.emit.data_ptr())
+    return marg
+
+
+@torch.no_grad()
+def marginal_smooth(history: SmoothHistory, marg: MarginalHistory, step: torch.Tensor, sigma_deg: float, jump: float = 8.0,
+                    frames: int | None = None, first_step: int = 1, out: SmoothedMarginals | None = None) -> SmoothedMarginals:
+    """The smoothed marginals of the newest ``frames`` (default H, at most H) recorded frames (``ahv_marginal_smooth_f32``: the
+    backward recursion, ``frames - 1`` launches, and a finish launch, issued by one call): ``SmoothedMarginals(logw (B,F,M), idx
+    (B,F) int64, R (B,F,3,3))``, oldest first, the last column the frame of ``t = step[0]`` (read on the device).  ``logw[b,f]`` is
+    ``log gamma``, the log-probability that the trajectory passes through each particle of that frame given all F frames (-inf
+    for a dead particle; ``exp`` sums to 1) -- a score row for ``pose_posterior`` at ``temperature=1``; ``idx`` its first arg-max
+    and ``R`` that particle's pose.  A frame before ``first_step`` and a frame without a live particle give -inf, -1 and the
+    identity.  ``sigma_deg`` and ``jump`` as given to ``marginal_step``.  ``out``: a ``SmoothedMarginals`` to write into
+    (allocates nothing)."""
+    H, B, M, dev = _marginal_ring(history, marg)
+    step = _step_counter(step, dev)
+    F = H if frames is None else int(frames)
+    if not 1 <= F <= H:
+        raise RuntimeError("frames = %d outside 1..H = %d" % (F, H))
+    sigma, jump = _transition_scale(sigma_deg, jump)
+    if out is None:
+        out = SmoothedMarginals(torch.empty((B, F, M), dtype=torch.float32, device=dev),
+                                torch.empty((B, F), dtype=torch.int64, device=dev),
+                                torch.empty((B, F, 3, 3), dtype=torch.float32, device=dev))
+    else:
+        ok = isinstance(out, tuple) and len(out) == 3
+        for t, shape, dtype in zip(out if ok else (), ((B, F, M), (B, F), (B, F, 3, 3)), (torch.float32, torch.int64, torch.float32)):
+            ok = ok and (isinstance(t, torch.Tensor) and tuple(t.shape) == shape and t.dtype == dtype and t.is_contiguous()
+                         and t.device == dev)
+        if not ok:
+            raise RuntimeError("out must be SmoothedMarginals(float32 (B,F,M) = %s, int64 (B,F), float32 (B,F,3,3)), contiguous, on %s"
+                               % ((B, F, M), dev))
+        out = SmoothedMarginals(*out)
+    _call(dev, "ahv_marginal_smooth_f32", history.R.data_ptr(), history.P.data_ptr() if history.P is not None else None,
+          marg.alpha.data_ptr(), marg.emit.data_ptr(), step.data_ptr(), int(first_step), B, M, H, F, sigma, jump, out.logw.data_ptr(),
+          out.idx.data_ptr(), out.R.data_ptr())
+    return out
+
+
 # ---- multi-view verification ---------------------------------------------------------------------------------------
 # V posed reference views of one object (absolute rotations A_v), one query whose absolute rotation is wanted, N hypotheses Q_n
 # of it: view v sees hypothesis n as R_{v,n} = Q_n A_v^T (gt_src_2_tgt_R = R_tgt R_src^-1), and the per-view scores are fused

@@ -30,8 +30,14 @@ in a ring and runs one Viterbi step per frame over it (``smooth_step``, after ``
 the particle history (Godsill, Doucet and West 2001).  ``smoothed()`` backtraces the most probable trajectory; a frame whose
 scores disagree with its neighbours is bridged by the motion prior, or left by paying ``smooth_jump``.  Smoothing observes and
 never steers: every ``TrackStep`` is the same bytes with and without it.
-Not built: sigma adapted from the entropy, the tracker inside the multi-view path (``ops.verify_views``), forward-backward
-marginal smoothing, and the velocity-noise term of the constant-velocity transition (the smoother's transition is pose-only).
+The Viterbi path is one pose per past frame and says nothing about how sure it is.  ``marginals=True`` (with ``history``) also
+runs the forward recursion of the same model per frame (``marginal_step``, after ``smooth_step``), and
+``smoothed_marginals()`` the backward one: a row of log-weights per past frame, the probability that the trajectory passes
+through each particle given every recorded frame, which ``pose_posterior`` turns into a smoothed mean pose, its spread, the
+mass that agrees with the frame's most probable particle and the entropy.
+Not built: sigma adapted from the entropy, the tracker inside the multi-view path (``ops.verify_views``), a fixed-lag marginal
+inside the captured step, and the velocity-noise term of the constant-velocity transition (the smoother's transition is
+pose-only).
 """
 from __future__ import annotations
 
@@ -84,6 +90,11 @@ class PoseTracker:
     set ``init`` scores is not recorded (the first frame of the path is the first ``step``).  ``history=0``: none of this, the
     calls of a step are the previous ones.
 
+    ``marginals=True`` (needs ``history``; ``backend`` then also provides ``marginal_step`` and ``marginal_smooth``): the
+    tracker owns an ``ops.marginal_history`` beside the ring and every step issues ``marginal_step`` right after
+    ``smooth_step``, with the same scale and jump.  It observes and never steers: every ``TrackStep``, the ring and
+    ``smoothed()`` are the same bytes with and without it.  ``smoothed_marginals()`` returns the marginals.
+
     ``use_graph=True`` (HIP backend only; refused with a ``backend`` or on the CPU): the first step after ``init`` reads the N0-sized set and runs eagerly; the two halves of
     the ping-pong are then captured as one hipGraph each, by the second and the third step, and every later step replays the
     graph of its half.  Each graph is the linear chain of the step's launches.  The two capturing steps synchronise with the
@@ -95,7 +106,8 @@ class PoseTracker:
                  n_fresh: int = 0, temperature: float = 0.02, max_angle_deg: Optional[float] = None, batch: int = 1,
                  seed: int = 0, posterior: bool = False, mode_angle_deg: float = 15.0, use_graph: bool = False, backend=None,
                  motion: str = "walk", sigma_vel_deg: float = 1.0, damping: float = 1.0, max_speed_deg: Optional[float] = None,
-                 coast: bool = True, history: int = 0, smooth_sigma_deg: Optional[float] = None, smooth_jump: float = 8.0):
+                 coast: bool = True, history: int = 0, smooth_sigma_deg: Optional[float] = None, smooth_jump: float = 8.0,
+                 marginals: bool = False):
         dev = W1.device
         self.ops = ops if backend is None else backend
         self.W1, self.W2, self.b2 = W1, W2, b2
@@ -131,6 +143,11 @@ class PoseTracker:
         self.smooth_sigma_deg, self.smooth_jump = float(smooth_sigma_deg), ops._jump(smooth_jump)
         if self.history and not ops._angle_rad(self.smooth_sigma_deg, "smooth_sigma_deg") > 0.0:
             raise RuntimeError("smooth_sigma_deg = %r must be > 0" % (smooth_sigma_deg,))
+        self.marginals = bool(marginals)
+        if self.marginals and not self.history:
+            raise RuntimeError("marginals=True needs history >= 2: the marginals are computed over the smoother's ring")
+        if self.marginals and not (hasattr(self.ops, "marginal_step") and hasattr(self.ops, "marginal_smooth")):
+            raise RuntimeError("marginals=True needs a backend that provides marginal_step and marginal_smooth")
         self.seed = int(seed)
         self.posterior = bool(posterior)
         self.mode_angle_deg = float(mode_angle_deg)
@@ -158,6 +175,7 @@ class PoseTracker:
         self._pws = ops.pose_posterior_workspace(B, M, 1, dev) if hip and self.posterior else None
         # the smoother's ring (any backend: plain tensors); after init the counter is 0 and the first step records frame 1
         self._hist = ops.smooth_history(B, M, self.history, dev, velocities=motion != "walk") if self.history else None
+        self._marg = ops.marginal_history(B, M, self.history, dev) if self.marginals else None
         self._cur = None      # (R, scores, key) of the set the next step draws from
         self._n = 0           # steps since init
         self._static = None
@@ -234,6 +252,9 @@ class PoseTracker:
         if self._hist is not None:   # observes the step, changes none of its outputs
             o.smooth_step(self._hist, R, scores, self._step, self.temperature, self.smooth_sigma_deg, jump=self.smooth_jump,
                           V=self._V[p] if self._V is not None else None, damping=self.damping, first_step=1)
+            if self._marg is not None:
+                o.marginal_step(self._hist, self._marg, R, scores, self._step, self.temperature, self.smooth_sigma_deg,
+                                jump=self.smooth_jump, first_step=1)
         return TrackStep(score, idx, R_map, R, scores, draws, *post, reacq)
 
     @torch.no_grad()
@@ -251,6 +272,41 @@ class PoseTracker:
                 raise RuntimeError("frames = %d must be at least 1" % int(frames))
             F = min(F, int(frames))
         return self.ops.smooth_backtrace(self._hist, self._step, frames=F, first_step=1, out=out)
+
+    @torch.no_grad()
+    def smoothed_marginals(self, frames: Optional[int] = None, out=None, posterior: bool = False):
+        """The smoothed marginals over the last ``min(frames, steps since init, history)`` frames:
+        ``ops.SmoothedMarginals(logw (B,F,M), idx (B,F) int64, R (B,F,3,3))``, oldest first, the last column the current frame
+        (where the marginal is the filter's own posterior).  ``logw[b,f]`` is the log-probability that the trajectory passes
+        through each particle of that frame given all F frames, ``idx`` its first arg-max and ``R`` that particle's pose.  F
+        launches, no host synchronisation; ``out``: a ``SmoothedMarginals`` of that size to write into.
+        ``posterior=True``: returns ``(marginals, R_mean (B,F,3,3), spread_deg, mode_mass, entropy (B,F))`` -- every frame's
+        row and particle set through ``pose_posterior`` at ``temperature=1`` with the frame's ``R`` as the single anchor and
+        ``mode_angle_deg``, as one batch of B F rows: the smoothed mean pose, its spread, the mass within ``mode_angle_deg`` of
+        the most probable particle and the entropy in nats.  The query gathers the frames from the ring and allocates."""
+        if self._marg is None:
+            raise RuntimeError("smoothed_marginals() needs a tracker built with history >= 2 and marginals=True")
+        if self._n < 1:
+            raise RuntimeError("smoothed_marginals() before the first step: nothing has been recorded since init")
+        F = min(self._n, self.history)
+        if frames is not None:
+            if int(frames) < 1:
+                raise RuntimeError("frames = %d must be at least 1" % int(frames))
+            F = min(F, int(frames))
+        if posterior:
+            ops.min_trace(self.mode_angle_deg)        # raises outside (0, 180), before any launch
+        res = self.ops.marginal_smooth(self._hist, self._marg, self._step, self.smooth_sigma_deg, jump=self.smooth_jump, frames=F,
+                                       first_step=1, out=out)
+        if not posterior:
+            return res
+        B, M = self.B, self.M
+        # the counter is 0 after init and moves by one per step: frame n lives in slot n mod H
+        slots = torch.tensor([(self._n - F + 1 + f) % self.history for f in range(F)], dtype=torch.int64, device=res.logw.device)
+        sets = self._hist.R.index_select(0, slots).transpose(0, 1).reshape(B * F, M, 3, 3)
+        p = self.ops.pose_posterior(res.logw.reshape(B * F, M), sets, 1.0, anchors=res.R.reshape(B * F, 1, 3, 3),
+                                    min_angle_deg=self.mode_angle_deg)
+        return (res, p.R_mean.reshape(B, F, 3, 3), p.spread_deg.reshape(B, F), p.mode_prob[:, 0].reshape(B, F),
+                p.entropy.reshape(B, F))
 
     @torch.no_grad()
     def step(self, vol_src: Optional[torch.Tensor] = None, vol_tgt: Optional[torch.Tensor] = None) -> TrackStep:
