@@ -26,6 +26,8 @@ AHV_SO3_MAX_LADDER = 8
 AHV_POSTERIOR_MAX_MODES = 16
 AHV_POSTERIOR_RESET_STATE = 1
 AHV_VIEWS_MAX = 16
+AHV_SYM_MAX_ELEMENTS = 64
+AHV_SYM_FOLD_MAX_ANCHORS = 16
 AHV_VIEWS_RESET_BEST = 1
 AHV_VIEWS_NO_ANGLE_LIMIT = 2
 AHV_VIEW_SLOT_EXCLUDED = -1
@@ -93,6 +95,13 @@ SIGNATURES["ahv_select_topk_f32"] = (_int, [_vp, _int, _vp, _i64, _i64, _i64, _i
 SIGNATURES["ahv_compose_rotations_topk_f32"] = (_int, [_vp, _int, _vp, _i64, _i64, _i64, _vp, _i64, _int, _vp, _vp])
 SIGNATURES["ahv_topk_modes_workspace_bytes"] = (ctypes.c_size_t, [_int, _i64, _int])
 SIGNATURES["ahv_topk_modes_f32"] = (_int, [_vp, _vp, _i64, _int, _i64, _i64, _int, ctypes.c_float, _vp, _vp, ctypes.c_size_t, _vp])
+# (scores, R, r_batch_stride, B, N, n_offset, K, min_trace, S, s_batch_stride, G, axis or NULL, axis_batch_stride, keys, workspace,
+#  workspace_bytes, stream)
+SIGNATURES["ahv_topk_modes_sym_f32"] = (_int, [_vp, _vp, _i64, _int, _i64, _i64, _int, ctypes.c_float, _vp, _i64, _int, _vp, _i64, _vp,
+                                               _vp, ctypes.c_size_t, _vp])
+# (R, r_batch_stride, B, N, S, s_batch_stride, G, axis or NULL, axis_batch_stride, anchors, K, min_trace, keep, V or NULL, R_out,
+#  V_out or NULL, which, elem, trace: each or NULL, stream)
+SIGNATURES["ahv_sym_fold_f32"] = (_int, [_vp, _i64, _int, _i64, _vp, _i64, _int, _vp, _i64, _vp, _int, ctypes.c_float, _i64] + [_vp] * 7)
 SIGNATURES["ahv_score_rotation_grad_workspace_bytes"] = (ctypes.c_size_t, [_int, _i64])
 SIGNATURES["ahv_score_rotation_grad_f32"] = (_int, [_vp, _vp, _vp, _i64, _vp, _vp, _vp, _int, _i64, _vp, _vp, ctypes.c_size_t,
                                                     _vp, _vp])

@@ -31,6 +31,10 @@ hipError_t launch_compose_rotations_topk(const int64_t*, int, const float*, int6
 int64_t topk_modes_state_stride(int64_t N);
 hipError_t launch_topk_modes(const float*, const float*, int64_t, int, int64_t, int64_t, int, float, int64_t*, int64_t*,
                              hipStream_t);
+hipError_t launch_topk_modes_sym(const float*, const float*, int64_t, int, int64_t, int64_t, int, float, const float*, int64_t, int,
+                                 const float*, int64_t, int64_t*, int64_t*, hipStream_t);
+hipError_t launch_sym_fold(const float*, int64_t, int, int64_t, const float*, int64_t, int, const float*, int64_t, const float*, int,
+                           float, int64_t, const float*, float*, float*, int32_t*, int32_t*, float*, hipStream_t);
 hipError_t launch_view_rotations(const float*, int64_t, const float*, int, int, int64_t, float*, hipStream_t);
 hipError_t launch_fuse_views(const float*, const float*, int64_t, const float*, const float*, int, int, int64_t, int64_t, float,
                              bool, float*, int64_t*, hipStream_t);
@@ -705,6 +709,73 @@ int ahv_topk_modes_f32(const float* scores, const float* R, int64_t r_batch_stri
     hipError_t e = ahv::launch_topk_modes(scores, R, r_batch_stride, B, N, n_offset, K, min_trace, keys,
                                           static_cast<int64_t*>(workspace), s);
     if (e != hipSuccess) return hip_fail("topk_modes: launch", e);
+    return AHV_OK;
+}
+
+// ---- pose selection modulo a symmetry group ------------------------------------------------------------------
+static int sym_group(const char* who, const float* S, int64_t s_batch_stride, int G, const float* axis, int64_t axis_batch_stride)
+{
+    if (G < 1 || G > AHV_SYM_MAX_ELEMENTS) return fail(AHV_EINVAL, "%s: G = %d outside 1..%d", who, G, AHV_SYM_MAX_ELEMENTS);
+    if (s_batch_stride != 0 && s_batch_stride != (int64_t)G * 9)
+        return fail(AHV_EINVAL, "%s: s_batch_stride %lld must be 0 or G*9", who, (long long)s_batch_stride);
+    if (axis_batch_stride != 0 && axis_batch_stride != 3)
+        return fail(AHV_EINVAL, "%s: axis_batch_stride %lld must be 0 or 3", who, (long long)axis_batch_stride);
+    if (!S) return fail(AHV_EINVAL, "%s: null pointer (S)", who);
+    (void)axis;
+    return AHV_OK;
+}
+
+int ahv_topk_modes_sym_f32(const float* scores, const float* R, int64_t r_batch_stride, int B, int64_t N, int64_t n_offset, int K,
+                           float min_trace, const float* S, int64_t s_batch_stride, int G, const float* axis,
+                           int64_t axis_batch_stride, int64_t* keys, void* workspace, size_t workspace_bytes, void* stream)
+{
+    if (bad_k(K)) return fail(AHV_EINVAL, "topk_modes_sym: K = %d outside 1..%d", K, AHV_TOPK_MAX_K);
+    if (B < 0 || N < 0) return fail(AHV_EINVAL, "topk_modes_sym: negative size");
+    if (B > 65535) return fail(AHV_EINVAL, "topk_modes_sym: B > 65535");
+    if (n_offset < 0 || n_offset + N > 4294967296ll) return fail(AHV_EINVAL, "topk_modes_sym: n_offset + N must fit in 32 bits");
+    if (!(min_trace > -1.0f && min_trace < 3.0f))   // false for a NaN
+        return fail(AHV_EINVAL, "topk_modes_sym: min_trace = %g outside (-1, 3) (1 + 2 cos theta, 0 < theta < 180 degrees)",
+                    (double)min_trace);
+    if (r_batch_stride != 0 && r_batch_stride != N * 9)
+        return fail(AHV_EINVAL, "topk_modes_sym: r_batch_stride %lld must be 0 or N*9", (long long)r_batch_stride);
+    if (int rc = sym_group("topk_modes_sym", S, s_batch_stride, G, axis, axis_batch_stride)) return rc;
+    if (B == 0) return AHV_OK;
+    if (!keys || (N > 0 && (!scores || !R))) return fail(AHV_EINVAL, "topk_modes_sym: null pointer");
+    const size_t need = ahv_topk_modes_workspace_bytes(B, N, K);
+    if (need && (!workspace || workspace_bytes < need || (reinterpret_cast<uintptr_t>(workspace) & 15)))
+        return fail(AHV_EINVAL, "topk_modes_sym: needs a 16-byte aligned workspace of %zu bytes (ahv_topk_modes_workspace_bytes), "
+                    "got %zu", need, workspace_bytes);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (N == 0) {
+        hipError_t e = ahv::launch_fill_keys(keys, B * K, s);
+        if (e != hipSuccess) return hip_fail("topk_modes_sym: list fill", e);
+        return AHV_OK;
+    }
+    hipError_t e = ahv::launch_topk_modes_sym(scores, R, r_batch_stride, B, N, n_offset, K, min_trace, S, s_batch_stride, G, axis,
+                                              axis_batch_stride, keys, static_cast<int64_t*>(workspace), s);
+    if (e != hipSuccess) return hip_fail("topk_modes_sym: launch", e);
+    return AHV_OK;
+}
+
+int ahv_sym_fold_f32(const float* R, int64_t r_batch_stride, int B, int64_t N, const float* S, int64_t s_batch_stride, int G,
+                     const float* axis, int64_t axis_batch_stride, const float* anchors, int K, float min_trace, int64_t keep,
+                     const float* V, float* R_out, float* V_out, int32_t* which, int32_t* elem, float* trace, void* stream)
+{
+    if (K < 1 || K > AHV_SYM_FOLD_MAX_ANCHORS) return fail(AHV_EINVAL, "sym_fold: K = %d outside 1..%d", K, AHV_SYM_FOLD_MAX_ANCHORS);
+    if (B < 0 || N < 0) return fail(AHV_EINVAL, "sym_fold: negative size");
+    if (B > 65535) return fail(AHV_EINVAL, "sym_fold: B > 65535");
+    if (!(min_trace == -__builtin_inff() || (min_trace > -1.0f && min_trace < 3.0f)))   // false for a NaN
+        return fail(AHV_EINVAL, "sym_fold: min_trace = %g is neither -inf (no limit) nor inside (-1, 3)", (double)min_trace);
+    if (r_batch_stride != 0 && r_batch_stride != N * 9)
+        return fail(AHV_EINVAL, "sym_fold: r_batch_stride %lld must be 0 or N*9", (long long)r_batch_stride);
+    if (int rc = sym_group("sym_fold", S, s_batch_stride, G, axis, axis_batch_stride)) return rc;
+    if (keep < 0 || keep > N) return fail(AHV_EINVAL, "sym_fold: keep = %lld outside 0..N", (long long)keep);
+    if ((V == nullptr) != (V_out == nullptr)) return fail(AHV_EINVAL, "sym_fold: V and V_out go together");
+    if (B == 0 || N == 0) return AHV_OK;
+    if (!R || !anchors || !R_out) return fail(AHV_EINVAL, "sym_fold: null pointer");
+    hipError_t e = ahv::launch_sym_fold(R, r_batch_stride, B, N, S, s_batch_stride, G, axis, axis_batch_stride, anchors, K, min_trace,
+                                        keep, V, R_out, V_out, which, elem, trace, static_cast<hipStream_t>(stream));
+    if (e != hipSuccess) return hip_fail("sym_fold: launch", e);
     return AHV_OK;
 }
 

@@ -1,9 +1,11 @@
 // ahv_select.hip -- pose selection: everything that happens AFTER the scores exist.  Packed keys (arg-max, fill), K-best
-// lists (top-K, merge, decode + gather, compose), distinct modes, the pose posterior, draws from it (systematic resampling, the
-// indexed compose) and the SO(3) ascent step.  These kernels
+// lists (top-K, merge, decode + gather, compose), distinct modes -- plain and modulo a symmetry group, with the fold into a
+// fundamental domain (ahv_sym.h) --, the pose posterior, draws from it (systematic resampling, the indexed compose) and the SO(3)
+// ascent step.  These kernels
 // read scores, keys and rotation matrices only: no volume, no MFMA.  (unpack_best_kernel, the decode without a gather, sits
 // with the scorer in ahv_score.hip.)
 #include "ahv_device.h"
+#include "ahv_sym.h"
 
 namespace ahv {
 
@@ -379,6 +381,239 @@ __global__ __launch_bounds__(kTopkThreads) void topk_modes_kernel(const float* _
             }
         }
         modes_publish(best, wl, list + j);
+    }
+}
+
+// ---------------------------------------------------------------------------------
+// Pose selection modulo a symmetry group (ahv_topk_modes_sym_f32 / ahv_sym_fold_f32; the maths: ahv_sym.h).
+//  - topk_modes_sym_kernel: round j >= 1 of the mode selection with t_G(R_i, R_w) in the place of t(i, w).  Round 0 and the list
+//    fill are the plain ones (topk_modes_kernel<true> knows no rotation), as are the alive state, the workspace and the hand-over of
+//    keys[j - 1] across the kernel boundary.  Every workgroup builds the winner's orbit R_w S_g^T (G matrices) in LDS first.
+//  - sym_fold_kernel: ONE pass on the grid rule of the modes kernels.  A hypothesis takes the FIRST non-empty anchor k with
+//    t_G(R_n, A_k) >= tau and becomes R_n S_g* Rot(a, phi*), the member of its orbit nearest that anchor; a body-frame velocity
+//    follows as (S_g* Rot)^T v.  The K G tables A_k S_g^T sit in LDS.  A lane reads its own four matrices before it writes them, so
+//    R_out may be R itself (per-sample R).  No atomics, no workspace: the same inputs give the same bytes.
+// ---------------------------------------------------------------------------------
+constexpr int kSymFoldMaxK = 16;
+
+template <bool kAxis>
+__global__ __launch_bounds__(kTopkThreads) void topk_modes_sym_kernel(const float* __restrict__ R, long r_batch_stride, long N, long Ns,
+                                                                      long n_offset, int K, int j, float tau,
+                                                                      const float* __restrict__ S, long s_batch_stride, int G,
+                                                                      const float* __restrict__ axis, long axis_batch_stride,
+                                                                      key_t* __restrict__ state, key_t* __restrict__ keys)
+{
+    __shared__ key_t wl[kTopkThreads / 64];
+    __shared__ float T[kSymMaxG * 9];
+    __shared__ float sig[kSymMaxG];
+    const int tid = threadIdx.x, b = blockIdx.y;
+    key_t* st = state + (long)b * Ns;
+    key_t* list = keys + (long)b * K;
+    const long tiles = (N + kTopkTile - 1) / kTopkTile;
+    const key_t prev = list[j - 1];
+    if (prev == kKeyEmpty) return;  // the alive set ran out (uniform over the grid)
+    const long widx = key_index(prev) - n_offset;
+    if (widx < 0 || widx >= N) return;
+    const float* Rb = R + (long)b * r_batch_stride;
+    float w[9], a[3] = {0.0f, 0.0f, 0.0f}, wa[3] = {0.0f, 0.0f, 0.0f};
+#pragma unroll
+    for (int i = 0; i < 9; ++i) w[i] = Rb[widx * 9 + i];
+    if constexpr (kAxis) {
+#pragma unroll
+        for (int i = 0; i < 3; ++i) a[i] = axis[(long)b * axis_batch_stride + i];
+        sym_apply(w, a, wa);
+    }
+    if (tid < G) {
+        float sg[9];
+#pragma unroll
+        for (int i = 0; i < 9; ++i) sg[i] = S[(long)b * s_batch_stride + tid * 9 + i];
+        sym_orbit_matrix(w, sg, tid, T + tid * 9);
+        if constexpr (kAxis) sig[tid] = sym_axis_sign(sg, a);
+    }
+    __syncthreads();
+    key_t best = kKeyEmpty;
+    for (long t = blockIdx.x; t < tiles; t += gridDim.x) {
+        const long n0 = t * kTopkTile + (long)tid * 4;
+        if (n0 >= N) continue;
+        const i64x2 c01 = *reinterpret_cast<const i64x2*>(st + n0), c23 = *reinterpret_cast<const i64x2*>(st + n0 + 2);
+        key_t c[4] = {c01.x, c01.y, c23.x, c23.y};
+        if (c[0] == kKeyEmpty && c[1] == kKeyEmpty && c[2] == kKeyEmpty && c[3] == kKeyEmpty) continue;
+        const bool alive[4] = {c[0] != kKeyEmpty, c[1] != kKeyEmpty, c[2] != kKeyEmpty, c[3] != kKeyEmpty};
+        float r[4][9], tr[4], cp[4], sp[4];
+        int gs[4];
+        load_rotations4(Rb, n0, N, alive, r);
+        sym_trace<4, kAxis>(r, T, G, sig, a, wa, tr, gs, cp, sp);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            if (c[e] == kKeyEmpty) continue;
+            if (tr[e] >= tau || n0 + e == widx) {  // false for a NaN t_G; the winner goes by its index
+                st[n0 + e] = kKeyEmpty;
+                continue;
+            }
+            best = c[e] > best ? c[e] : best;
+        }
+    }
+    modes_publish(best, wl, list + j);
+}
+
+// (R / R_out and V / V_out may be the same buffers: no __restrict__ on them)
+template <bool kAxis>
+__global__ __launch_bounds__(kTopkThreads) void sym_fold_kernel(const float* R, long r_batch_stride, long N,
+                                                                const float* __restrict__ S, long s_batch_stride, int G,
+                                                                const float* __restrict__ axis, long axis_batch_stride,
+                                                                const float* __restrict__ anchors, int K, float tau, long keep,
+                                                                const float* V, float* R_out, float* V_out, int* __restrict__ which,
+                                                                int* __restrict__ elem, float* __restrict__ trace)
+{
+    __shared__ float T[kSymFoldMaxK * kSymMaxG * 9];  // A_k S_g^T, [k][g][9]
+    __shared__ float Sl[kSymMaxG * 9];
+    __shared__ float sig[kSymMaxG];
+    __shared__ float Aa[kSymFoldMaxK][3];
+    __shared__ int used[kSymFoldMaxK];  // an all-zero anchor is an empty slot (the posterior's convention)
+    const int tid = threadIdx.x, b = blockIdx.y;
+    const float* An = anchors + (long)b * K * 9;
+    float a[3] = {0.0f, 0.0f, 0.0f};
+    if constexpr (kAxis) {
+#pragma unroll
+        for (int i = 0; i < 3; ++i) a[i] = axis[(long)b * axis_batch_stride + i];
+    }
+    for (int e = tid; e < G * 9; e += kTopkThreads) Sl[e] = S[(long)b * s_batch_stride + e];
+    __syncthreads();
+    for (int e = tid; e < K * G; e += kTopkThreads) {
+        const int k = e / G, g = e - k * G;
+        float ak[9];
+#pragma unroll
+        for (int i = 0; i < 9; ++i) ak[i] = An[k * 9 + i];
+        sym_orbit_matrix(ak, Sl + g * 9, g, T + e * 9);
+    }
+    if (tid < K) {
+        float ak[9];
+        bool any = false;
+#pragma unroll
+        for (int i = 0; i < 9; ++i) {
+            ak[i] = An[tid * 9 + i];
+            any = any || ak[i] != 0.0f;  // true for a NaN entry: its t_G then matches nothing
+        }
+        used[tid] = any ? 1 : 0;
+        if constexpr (kAxis) sym_apply(ak, a, Aa[tid]);
+    }
+    if (kAxis && tid < G) sig[tid] = sym_axis_sign(Sl + tid * 9, a);
+    __syncthreads();
+
+    const float* Rb = R + (long)b * r_batch_stride;
+    float* Ro = R_out + (long)b * N * 9;
+    const long tiles = (N + kTopkTile - 1) / kTopkTile;
+    for (long t = blockIdx.x; t < tiles; t += gridDim.x) {
+        const long n0 = t * kTopkTile + (long)tid * 4;
+        if (n0 >= N) continue;
+        float r[4][9];
+        const bool every[4] = {true, true, true, true};
+        load_rotations4(Rb, n0, N, every, r);
+        int wh[4], el[4];
+        float tt[4], cp[4], sp[4];
+        bool open[4];
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            wh[e] = el[e] = -1;
+            tt[e] = __builtin_nanf("");
+            cp[e] = 1.0f;
+            sp[e] = 0.0f;
+            open[e] = n0 + e < N && n0 + e >= keep;
+        }
+        for (int k = 0; k < K; ++k) {
+            if (!used[k]) continue;                                        // (uniform over the workgroup)
+            if (!__ballot(open[0] || open[1] || open[2] || open[3])) break;  // (uniform over the wave)
+            float t4[4], c4[4], s4[4];
+            int g4[4];
+            sym_trace<4, kAxis>(r, T + k * G * 9, G, sig, a, Aa[k], t4, g4, c4, s4);
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                if (open[e] && t4[e] >= tau) {  // the FIRST anchor within; false for a NaN t_G
+                    wh[e] = k;
+                    el[e] = g4[e];
+                    tt[e] = t4[e];
+                    cp[e] = c4[e];
+                    sp[e] = s4[e];
+                    open[e] = false;
+                }
+            }
+        }
+        float v[4][3], vo[4][3];
+        const long vb = ((long)b * N + n0) * 3;
+        const bool whole = n0 + 3 < N;
+        if (V) {
+            if (whole && aligned16(V + vb)) {
+                float4 q[3];
+#pragma unroll
+                for (int i = 0; i < 3; ++i) q[i] = reinterpret_cast<const float4*>(V + vb)[i];
+#pragma unroll
+                for (int f = 0; f < 12; ++f) {
+                    const float4 x = q[f >> 2];
+                    v[f / 3][f % 3] = (f & 3) == 0 ? x.x : (f & 3) == 1 ? x.y : (f & 3) == 2 ? x.z : x.w;
+                }
+            } else {
+#pragma unroll
+                for (int f = 0; f < 12; ++f) v[f / 3][f % 3] = n0 + f / 3 < N ? V[vb + f] : 0.0f;
+            }
+        }
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            // the identity element without an axis turn: the input's bytes, not a product with the identity
+            const bool moved = wh[e] >= 0 && (el[e] != 0 || (kAxis && !(sp[e] == 0.0f && cp[e] > 0.0f)));
+            float Q[9], o[9];
+            sym_element<kAxis>(Sl + (moved ? el[e] : 0) * 9, a, cp[e], sp[e], Q);
+#pragma unroll
+            for (int i = 0; i < 3; ++i)
+#pragma unroll
+                for (int c = 0; c < 3; ++c)
+                    o[i * 3 + c] = fmaf(r[e][i * 3 + 2], Q[6 + c], fmaf(r[e][i * 3 + 1], Q[3 + c], r[e][i * 3] * Q[c]));
+#pragma unroll
+            for (int i = 0; i < 9; ++i) r[e][i] = moved ? o[i] : r[e][i];
+            if (V) {
+#pragma unroll
+                for (int c = 0; c < 3; ++c) {
+                    const float x = fmaf(Q[6 + c], v[e][2], fmaf(Q[3 + c], v[e][1], Q[c] * v[e][0]));  // (Q^T v)[c]
+                    vo[e][c] = moved ? x : v[e][c];
+                }
+            }
+        }
+        float* rp = Ro + n0 * 9;
+        if (whole && aligned16(rp)) {
+#pragma unroll
+            for (int q = 0; q < 9; ++q) {
+                const int f = q * 4;
+                reinterpret_cast<float4*>(rp)[q] = make_float4(r[f / 9][f % 9], r[(f + 1) / 9][(f + 1) % 9], r[(f + 2) / 9][(f + 2) % 9],
+                                                               r[(f + 3) / 9][(f + 3) % 9]);
+            }
+        } else {
+#pragma unroll
+            for (int e = 0; e < 4; ++e)
+#pragma unroll
+                for (int i = 0; i < 9; ++i)
+                    if (n0 + e < N) rp[e * 9 + i] = r[e][i];
+        }
+        if (V) {
+            if (whole && aligned16(V_out + vb)) {
+#pragma unroll
+                for (int q = 0; q < 3; ++q) {
+                    const int f = q * 4;
+                    reinterpret_cast<float4*>(V_out + vb)[q] = make_float4(vo[f / 3][f % 3], vo[(f + 1) / 3][(f + 1) % 3],
+                                                                           vo[(f + 2) / 3][(f + 2) % 3], vo[(f + 3) / 3][(f + 3) % 3]);
+                }
+            } else {
+#pragma unroll
+                for (int f = 0; f < 12; ++f)
+                    if (n0 + f / 3 < N) V_out[vb + f] = vo[f / 3][f % 3];
+            }
+        }
+        const long ob = (long)b * N + n0;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            if (n0 + e >= N) continue;
+            if (which) which[ob + e] = wh[e];
+            if (elem) elem[ob + e] = el[e];
+            if (trace) trace[ob + e] = tt[e];
+        }
     }
 }
 
@@ -1537,6 +1772,50 @@ hipError_t launch_topk_modes(const float* scores, const float* R, int64_t r_batc
         hipLaunchKernelGGL(topk_modes_kernel<false>, grid, dim3(kTopkThreads), 0, stream, scores, R, (long)r_batch_stride,
                            (long)N, Ns, (long)n_offset, K, j, tau, reinterpret_cast<key_t*>(state),
                            reinterpret_cast<key_t*>(keys));
+    return hipGetLastError();
+}
+
+// ---- pose selection modulo a symmetry group ------------------------------------------------------------------
+// launch_topk_modes with the rounds j >= 1 taken modulo the group (axis == nullptr: the finite part alone)
+hipError_t launch_topk_modes_sym(const float* scores, const float* R, int64_t r_batch_stride, int B, int64_t N, int64_t n_offset,
+                                 int K, float tau, const float* S, int64_t s_batch_stride, int G, const float* axis,
+                                 int64_t axis_batch_stride, int64_t* keys, int64_t* state, hipStream_t stream)
+{
+    hipError_t e = launch_fill_keys(keys, B * K, stream);
+    if (e != hipSuccess) return e;
+    const int64_t tiles = (N + kTopkTile - 1) / kTopkTile;
+    const dim3 grid((unsigned)(tiles < 1024 ? tiles : 1024), (unsigned)B);
+    const long Ns = (long)topk_modes_state_stride(N);
+    hipLaunchKernelGGL(topk_modes_kernel<true>, grid, dim3(kTopkThreads), 0, stream, scores, R, (long)r_batch_stride, (long)N,
+                       Ns, (long)n_offset, K, 0, tau, reinterpret_cast<key_t*>(state), reinterpret_cast<key_t*>(keys));
+    for (int j = 1; j < K; ++j) {
+        if (axis)
+            hipLaunchKernelGGL(topk_modes_sym_kernel<true>, grid, dim3(kTopkThreads), 0, stream, R, (long)r_batch_stride, (long)N, Ns,
+                               (long)n_offset, K, j, tau, S, (long)s_batch_stride, G, axis, (long)axis_batch_stride,
+                               reinterpret_cast<key_t*>(state), reinterpret_cast<key_t*>(keys));
+        else
+            hipLaunchKernelGGL(topk_modes_sym_kernel<false>, grid, dim3(kTopkThreads), 0, stream, R, (long)r_batch_stride, (long)N, Ns,
+                               (long)n_offset, K, j, tau, S, (long)s_batch_stride, G, axis, (long)axis_batch_stride,
+                               reinterpret_cast<key_t*>(state), reinterpret_cast<key_t*>(keys));
+    }
+    return hipGetLastError();
+}
+
+hipError_t launch_sym_fold(const float* R, int64_t r_batch_stride, int B, int64_t N, const float* S, int64_t s_batch_stride, int G,
+                           const float* axis, int64_t axis_batch_stride, const float* anchors, int K, float tau, int64_t keep,
+                           const float* V, float* R_out, float* V_out, int32_t* which, int32_t* elem, float* trace,
+                           hipStream_t stream)
+{
+    const int64_t tiles = (N + kTopkTile - 1) / kTopkTile;
+    const dim3 grid((unsigned)(tiles < 1024 ? tiles : 1024), (unsigned)B);
+    if (axis)
+        hipLaunchKernelGGL(sym_fold_kernel<true>, grid, dim3(kTopkThreads), 0, stream, R, (long)r_batch_stride, (long)N, S,
+                           (long)s_batch_stride, G, axis, (long)axis_batch_stride, anchors, K, tau, (long)keep, V, R_out, V_out, which,
+                           elem, trace);
+    else
+        hipLaunchKernelGGL(sym_fold_kernel<false>, grid, dim3(kTopkThreads), 0, stream, R, (long)r_batch_stride, (long)N, S,
+                           (long)s_batch_stride, G, axis, (long)axis_batch_stride, anchors, K, tau, (long)keep, V, R_out, V_out, which,
+                           elem, trace);
     return hipGetLastError();
 }
 

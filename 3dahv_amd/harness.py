@@ -26,7 +26,7 @@ from typing import Callable, Dict, Iterable, Optional
 import numpy as np
 import torch
 
-from .rotations import geodesic_deg, random_rotations
+from .rotations import Symmetry, geodesic_deg, geodesic_sym_deg, random_rotations
 
 
 def get_permutations(num_frames: int) -> torch.Tensor:
@@ -366,10 +366,19 @@ def run_co3d(cfg, model, categories: Dict[str, Iterable[dict]], repeats: int = 5
 
 @torch.no_grad()
 def test_linemod_category(cfg, model, loader: Iterable[dict], clsID: int, out_dir: Optional[str] = None,
-                          proposals_fn: Optional[Callable] = None):
+                          proposals_fn: Optional[Callable] = None, symmetry=None):
     """Evident intent of ``test_category`` (test_linemod.py:20-86; the shipped script does not run, SURVEY.md
-    section 2 row 7): per batch a fresh codebook, verify, angular error (<, not <=), ``linemod_pred_Rs`` file."""
+    section 2 row 7): per batch a fresh codebook, verify, angular error (<, not <=), ``linemod_pred_Rs`` file.
+    ``symmetry``: None (the reference's metric), a ``rotations.Symmetry`` in the OBJECT'S frame, or ``"config"`` -- the entry
+    ``cfg["LINEMOD"]["SYMMETRIC_OBJ"]["%06d" % clsID]`` (``['Z', 180]``: the reference lists eggbox and glue and reads the key
+    nowhere; no entry: no symmetry).  The group is conjugated into each pair's source view by ``data["src_R"]`` and the error is
+    ``geodesic_sym_deg``: a prediction that differs from the ground truth by a symmetry of the object is correct."""
     pred_Rs, errs = [], []
+    if isinstance(symmetry, str):
+        if symmetry != "config":
+            raise ValueError("symmetry = %r: expected None, 'config' or a rotations.Symmetry" % (symmetry,))
+        entry = cfg.get("LINEMOD", {}).get("SYMMETRIC_OBJ", {}).get("%06d" % clsID)
+        symmetry = Symmetry.from_config(entry) if entry is not None else None
     for data in loader:
         mask_src, mask_tgt = data["src_mask"], data["ref_mask"]
         thr = cfg["DATA"]["SIZE_THR"]
@@ -381,7 +390,10 @@ def test_linemod_category(cfg, model, loader: Iterable[dict], clsID: int, out_di
         vol_src, vol_tgt = model(data["src_img"], mask_src, data["ref_img"], mask_tgt)
         gt = torch.bmm(data["ref_R"], torch.inverse(data["src_R"]))
         _, _, _, R_pred = model.verify(vol_src, vol_tgt, codebook.to(dev))
-        errs.append(geodesic_deg(R_pred, gt))
+        if symmetry is None:
+            errs.append(geodesic_deg(R_pred, gt))
+        else:
+            errs.append(geodesic_sym_deg(R_pred, gt, symmetry.to(dev).conjugate(data["src_R"])))
         pred_Rs.append(R_pred.cpu().numpy().reshape(-1))
     err = torch.cat(errs)
     acc30, acc15 = 100 * (err < 30).float().mean().item(), 100 * (err < 15).float().mean().item()

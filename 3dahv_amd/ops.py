@@ -799,18 +799,23 @@ def topk_modes_workspace(B: int, N: int, k: int, device) -> torch.Tensor | None:
 
 @torch.no_grad()
 def topk_modes(scores: torch.Tensor, R: torch.Tensor, k: int, min_angle_deg: float, n_offset: int = 0,
-               keys: torch.Tensor | None = None, workspace: torch.Tensor | None = None):
+               keys: torch.Tensor | None = None, workspace: torch.Tensor | None = None, symmetry=None):
     """Up to K distinct pose modes of ``scores (B,N)`` over the hypotheses ``R (N,3,3)`` / ``(B,N,3,3)`` as packed keys
     ``(B,K)`` (``ahv_topk_modes_f32``): the K-best order with every hypothesis within ``min_angle_deg`` of an earlier entry
     left out, padded with AHV_KEY_EMPTY when the set holds fewer modes.  ``keys`` is OVERWRITTEN (modes do not merge: select
     once over the whole set -- ``dist.all_gather_scores`` for shards); ``workspace``: an int64 tensor of
     ``ahv_topk_modes_workspace_bytes`` bytes (``topk_modes_workspace``), else a static one per shape.  With both given the call
-    allocates nothing.  Decode with ``select_topk``."""
+    allocates nothing.  Decode with ``select_topk``.  ``symmetry`` (a ``rotations.Symmetry`` in the source view's frame): modes are
+    distinct MODULO the group (``ahv_topk_modes_sym_f32``) -- a hypothesis dies when any pose equivalent to it is within
+    ``min_angle_deg`` of the winner; same list format, same workspace."""
     if scores.dim() != 2:
         raise RuntimeError("scores must be (B,N)")
     k = _topk_k(k)
     tau = min_trace(min_angle_deg)
+    if symmetry is not None and not hasattr(symmetry, "S"):
+        raise RuntimeError("symmetry must be a rotations.Symmetry, got %r" % (type(symmetry).__name__,))
     dev = _need_gpu(scores, R)
+    sym = _sym_args(symmetry, scores.shape[0], dev) if symmetry is not None else None
     B, N = scores.shape
     n_rot, rstride = _rot_layout(R, B)
     if n_rot != N:
@@ -822,6 +827,10 @@ def topk_modes(scores: torch.Tensor, R: torch.Tensor, k: int, min_angle_deg: flo
     s, Rc = scores.detach().contiguous(), R.detach().contiguous()
     workspace, have = _workspace(_MODES_WS, (dev, B, N), _lib.load().ahv_topk_modes_workspace_bytes(B, N, k), torch.int64,
                                  workspace)
+    if sym is not None:
+        _call(dev, "ahv_topk_modes_sym_f32", s.data_ptr(), Rc.data_ptr(), rstride, B, N, n_offset, k, tau, *_sym_ptrs(sym),
+              keys.data_ptr(), workspace.data_ptr() if workspace is not None else None, have)
+        return keys
     _call(dev, "ahv_topk_modes_f32", s.data_ptr(), Rc.data_ptr(), rstride, B, N, n_offset, k, tau, keys.data_ptr(),
           workspace.data_ptr() if workspace is not None else None, have)
     return keys
@@ -829,13 +838,98 @@ def topk_modes(scores: torch.Tensor, R: torch.Tensor, k: int, min_angle_deg: flo
 
 def verify_pair_modes(vol_src: torch.Tensor, vol_tgt: torch.Tensor, R: torch.Tensor, W1: torch.Tensor, W2: torch.Tensor,
                       b2: torch.Tensor, k: int, min_angle_deg: float, keys: torch.Tensor | None = None,
-                      workspace: torch.Tensor | None = None, **kw):
+                      workspace: torch.Tensor | None = None, symmetry=None, **kw):
     """The verify step with distinct modes: ``verify_pair`` with the scores kept -> ``topk_modes`` -> ``select_topk``.
     Returns ``(mode_scores (B,K), mode_idx (B,K), R_modes (B,K,3,3))``; a slot past the last mode holds -inf, -1 and a zero
-    matrix.  Other keywords go to ``verify_pair``."""
+    matrix.  ``symmetry``: as in ``topk_modes``.  Other keywords go to ``verify_pair``."""
     k = _topk_k(k)
     scores = verify_pair(vol_src, vol_tgt, R, W1, W2, b2, want_scores=True, **kw)[0]
-    return select_topk(topk_modes(scores, R, k, min_angle_deg, keys=keys, workspace=workspace), R)
+    return select_topk(topk_modes(scores, R, k, min_angle_deg, keys=keys, workspace=workspace, symmetry=symmetry), R)
+
+
+# ---- pose selection modulo a symmetry group --------------------------------------------------------------------
+# A ``rotations.Symmetry`` in the SOURCE VIEW'S frame makes R and R S the same pose (include/ahv.h, "Pose selection modulo an
+# object's symmetry group").  ``topk_modes(symmetry=)`` selects modes of the quotient; ``sym_fold`` moves every hypothesis to the
+# member of its orbit nearest an anchor, after which the plain posterior, tracker and smoothers see one fundamental domain.
+
+SymFold = collections.namedtuple("SymFold", ["R", "which", "elem", "trace", "V"])
+
+
+def _sym_args(symmetry, B: int, dev):
+    """``(S, s_batch_stride, G, axis or None, axis_batch_stride)`` of a ``rotations.Symmetry`` for B samples on ``dev``."""
+    S, axis = getattr(symmetry, "S", None), getattr(symmetry, "axis", None)
+    if S is None:
+        raise RuntimeError("symmetry must be a rotations.Symmetry, got %r" % (type(symmetry).__name__,))
+    _need_gpu(*((S,) if axis is None else (S, axis)))
+    if S.device != dev:
+        raise RuntimeError("Expected all tensors to be on the same device, found %s and %s" % (dev, S.device))
+    G = S.shape[-3]
+    if not 1 <= G <= _lib.AHV_SYM_MAX_ELEMENTS:
+        raise RuntimeError("G = %d outside 1..%d" % (G, _lib.AHV_SYM_MAX_ELEMENTS))
+    if S.dim() == 4 and S.shape[0] != B:
+        raise RuntimeError("symmetry holds %d samples, the call %d" % (S.shape[0], B))
+    if axis is not None and axis.dim() == 2 and axis.shape[0] != B:
+        raise RuntimeError("symmetry axis holds %d samples, the call %d" % (axis.shape[0], B))
+    S = S.contiguous()
+    axis = None if axis is None else axis.contiguous()
+    return S, (G * 9 if S.dim() == 4 else 0), G, axis, (3 if axis is not None and axis.dim() == 2 else 0)
+
+
+def _sym_ptrs(sym):
+    S, sstride, G, axis, astride = sym
+    return S.data_ptr(), sstride, G, (axis.data_ptr() if axis is not None else None), astride
+
+
+@torch.no_grad()
+def sym_fold(R: torch.Tensor, symmetry, anchors: torch.Tensor, min_angle_deg: float | None = None, keep: int = 0,
+             V: torch.Tensor | None = None, out: torch.Tensor | None = None, V_out: torch.Tensor | None = None,
+             want_info: bool = True) -> SymFold:
+    """Fold the hypotheses ``R (N,3,3)`` / ``(B,N,3,3)`` into the fundamental domain around ``anchors (B,K,3,3)`` (K <= 16; an
+    all-zero anchor is an empty slot) modulo ``symmetry`` (``ahv_sym_fold_f32``, one launch): hypothesis n takes the FIRST anchor k
+    with an equivalent pose within ``min_angle_deg`` (``None``: no limit, so the first non-empty anchor) and becomes that pose,
+    ``R_n S_g* Rot(axis, phi*)``; a body-frame velocity ``V (B,N,3)`` follows as ``(S_g* Rot)^T v``.  Returns ``SymFold(R (B,N,3,3),
+    which (B,N) int32, elem (B,N) int32, trace (B,N), V)``: the anchor, the group element and the symmetric trace t_G, -1 / -1 / NaN
+    for a hypothesis no anchor took (copied byte for byte) and for the slots ``n < keep`` (always copied).  ``out`` / ``V_out``:
+    where to write -- ``out`` may be ``R`` itself when R is per-sample and ``V_out`` may be ``V`` (in place); the anchors must not
+    overlap ``out``.  ``want_info=False``: ``which``, ``elem`` and ``trace`` are not written (``None``); with ``out`` (and
+    ``V_out``) the call then allocates nothing."""
+    if anchors.dim() != 4 or tuple(anchors.shape[2:]) != (3, 3):
+        raise RuntimeError("anchors must be (B,K,3,3), got %s" % (tuple(anchors.shape),))
+    B, K = anchors.shape[:2]
+    if not 1 <= K <= _lib.AHV_SYM_FOLD_MAX_ANCHORS:
+        raise RuntimeError("K = %d outside 1..%d" % (K, _lib.AHV_SYM_FOLD_MAX_ANCHORS))
+    tau = -math.inf if min_angle_deg is None else min_trace(min_angle_deg)
+    N, rstride = _rot_layout(R, B)
+    keep = int(keep)
+    if not 0 <= keep <= N:
+        raise RuntimeError("keep = %d outside 0..N = %d" % (keep, N))
+    dev = _need_gpu(*((R, anchors) if V is None else (R, anchors, V)))
+    sym = _sym_args(symmetry, B, dev)
+    if V is not None and (tuple(V.shape) != (B, N, 3) or not V.is_contiguous()):
+        raise RuntimeError("V must be a contiguous (B,N,3) tensor")
+    if V is None and V_out is not None:
+        raise RuntimeError("V_out without V")
+    if R.data_ptr() == (out.data_ptr() if out is not None else 0) and (rstride == 0 and B > 1 or not R.is_contiguous()):
+        raise RuntimeError("in place needs a contiguous per-sample R")
+    Rc, Ac = R.detach().contiguous(), anchors.detach().contiguous()
+    if out is None:
+        out = torch.empty((B, N, 3, 3), dtype=torch.float32, device=dev)
+    elif tuple(out.shape) != (B, N, 3, 3) or not out.is_contiguous() or out.device != dev or out.dtype != torch.float32:
+        raise RuntimeError("out must be a contiguous float32 (B,N,3,3) = %s tensor on %s" % ((B, N, 3, 3), dev))
+    if V is not None:
+        if V_out is None:
+            V_out = torch.empty((B, N, 3), dtype=torch.float32, device=dev)
+        elif tuple(V_out.shape) != (B, N, 3) or not V_out.is_contiguous() or V_out.device != dev or V_out.dtype != torch.float32:
+            raise RuntimeError("V_out must be a contiguous float32 (B,N,3) tensor on %s" % (dev,))
+    which = elem = trace = None
+    if want_info:
+        which = torch.empty((B, N), dtype=torch.int32, device=dev)
+        elem = torch.empty((B, N), dtype=torch.int32, device=dev)
+        trace = torch.empty((B, N), dtype=torch.float32, device=dev)
+    ptr = lambda t: t.data_ptr() if t is not None else None
+    _call(dev, "ahv_sym_fold_f32", Rc.data_ptr(), rstride, B, N, *_sym_ptrs(sym), Ac.data_ptr(), K, tau, keep, ptr(V), out.data_ptr(),
+          ptr(V_out), ptr(which), ptr(elem), ptr(trace))
+    return SymFold(out, which, elem, trace, V_out)
 
 
 # ---- pose posterior --------------------------------------------------------------------------------------------
@@ -934,7 +1028,7 @@ def merge_posterior(states: torch.Tensor, k: int, temperature: float = 0.1, stat
 @torch.no_grad()
 def pose_posterior(scores: torch.Tensor, R: torch.Tensor, temperature: float = 0.1, anchors: torch.Tensor | None = None,
                    min_angle_deg: float | None = None, state: torch.Tensor | None = None, workspace: torch.Tensor | None = None,
-                   reset: bool | None = None) -> PosePosterior:
+                   reset: bool | None = None, symmetry=None) -> PosePosterior:
     """The posterior of ``scores (B,N)`` over the hypotheses ``R (N,3,3)`` / ``(B,N,3,3)`` at ``temperature``, bucketed by the
     ``anchors (B,K,3,3)`` (K <= 16; normally the rotations ``select_topk`` returns for a modes list; an all-zero anchor is an
     empty slot): hypothesis i counts for the FIRST anchor within ``min_angle_deg`` of it, else for the rest.  Returns a
@@ -943,11 +1037,18 @@ def pose_posterior(scores: torch.Tensor, R: torch.Tensor, temperature: float = 0
     weighted mean matrix), ``mode_spread_deg`` / ``spread_deg``, and ``state``.  ``state`` given: this call's hypotheses are
     merged into it (chunked N) unless ``reset``, and the outputs describe the merged state.  ``workspace``: a uint8 tensor of
     ``ahv_pose_posterior_workspace_bytes`` bytes (``pose_posterior_workspace``), else a static one per shape.  Three launches;
-    with ``state`` and ``workspace`` given only the outputs are allocated."""
+    with ``state`` and ``workspace`` given only the outputs are allocated.  ``symmetry`` (needs anchors): the hypotheses are first
+    folded with the same anchors and angle (``sym_fold``, one more launch and a (B,N,3,3) buffer), then the unchanged posterior runs
+    on the folded set -- exact for the quotient: a folded hypothesis is within the angle of its anchor in the plain distance and of no
+    earlier one, an unfolded one of none, so masses, mean poses and spreads are those modulo the group, and states still merge."""
     beta = inverse_temperature(temperature)
     if scores.dim() != 2:
         raise RuntimeError("scores must be (B,N)")
     B, N = scores.shape
+    if symmetry is not None:
+        if anchors is None or min_angle_deg is None:
+            raise RuntimeError("symmetry needs anchors and min_angle_deg")
+        R = sym_fold(R, symmetry, anchors, min_angle_deg, want_info=False).R
     if anchors is None:
         k, tau = 0, 0.0
     else:
@@ -982,16 +1083,17 @@ def pose_posterior(scores: torch.Tensor, R: torch.Tensor, temperature: float = 0
 
 
 def verify_pair_posterior(vol_src: torch.Tensor, vol_tgt: torch.Tensor, R: torch.Tensor, W1: torch.Tensor, W2: torch.Tensor,
-                          b2: torch.Tensor, k: int, min_angle_deg: float, temperature: float = 0.1, **kw):
+                          b2: torch.Tensor, k: int, min_angle_deg: float, temperature: float = 0.1, symmetry=None, **kw):
     """The verify step with distinct modes and their posterior: ``verify_pair`` with the scores kept -> ``topk_modes`` ->
     ``select_topk`` -> ``pose_posterior`` with the modes as anchors.  Returns ``verify_pair_modes``'s triple ``(mode_scores
-    (B,K), mode_idx (B,K), R_modes (B,K,3,3))`` and the ``PosePosterior``; K <= 16.  Other keywords go to ``verify_pair``."""
+    (B,K), mode_idx (B,K), R_modes (B,K,3,3))`` and the ``PosePosterior``; K <= 16.  ``symmetry``: modes and posterior modulo the
+    group (``topk_modes`` / ``pose_posterior``).  Other keywords go to ``verify_pair``."""
     k = _posterior_k(k)
     beta = inverse_temperature(temperature)  # (checked before the first launch)
     del beta
     scores = verify_pair(vol_src, vol_tgt, R, W1, W2, b2, want_scores=True, **kw)[0]
-    m_s, m_i, m_R = select_topk(topk_modes(scores, R, _topk_k(k), min_angle_deg), R)
-    return m_s, m_i, m_R, pose_posterior(scores, R, temperature, anchors=m_R, min_angle_deg=min_angle_deg)
+    m_s, m_i, m_R = select_topk(topk_modes(scores, R, _topk_k(k), min_angle_deg, symmetry=symmetry), R)
+    return m_s, m_i, m_R, pose_posterior(scores, R, temperature, anchors=m_R, min_angle_deg=min_angle_deg, symmetry=symmetry)
 
 
 # ---- posterior resampling -----------------------------------------------------------------------------------------

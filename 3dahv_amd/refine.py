@@ -67,7 +67,8 @@ class CoarseToFine:
     mode) -- ``argmax`` / ``select_rotation`` on the (B*K, N2) view of the fine scores; multi-rank, the N2-blocks are cut
     across ranks and the second all-reduce carries the (B,K) per-block keys instead of the (B,) key: still two collectives.
     The fine winner returned is the best of those (fine index ``mode * N2 + idx``), ``self.last["coarse_topk"]`` the coarse
-    modes.  With ``polish_iters > 0`` all K per-mode poses are polished (``self.last["polish"]`` is (B,K)-shaped) and the
+    modes.  ``symmetry`` (a ``rotations.Symmetry`` in the source view's frame; with ``modes`` only, any other seeding raises): the
+    seeds are distinct MODULO the group, so a symmetric object's K slots are not spent on copies of one pose.  With ``polish_iters > 0`` all K per-mode poses are polished (``self.last["polish"]`` is (B,K)-shaped) and the
     best polished one is returned.  ``modes=1`` gives the ``seeds=1`` step's outputs bit for bit.  Exclusive with
     ``seeds > 1`` and with ``fused``: both raise.
     ``polish_iters > 0`` (gradient-based polishing, ``ops.polish_rotations``): after the fine stage the fine winner takes
@@ -99,7 +100,7 @@ class CoarseToFine:
                  want_scores: bool = False, force_collectives: bool = False, no_teams: bool = False,
                  fused: Optional[bool] = None, seeds: int = 1, polish_iters: int = 0, polish_angle_deg: float = 2.0,
                  polish_ladder=(0.25, 0.5, 1.0, 2.0), modes: int = 0, mode_angle_deg: float = 15.0, resample: bool = False,
-                 resample_temperature: float = 0.1, resample_u=None):
+                 resample_temperature: float = 0.1, resample_u=None, symmetry=None):
         dev = R_coarse.device
         self.ops = ops if backend is None else backend
         self.W1, self.W2, self.b2 = W1, W2, b2
@@ -126,6 +127,10 @@ class CoarseToFine:
             raise RuntimeError("the one-launch step (fused=True) refines around ONE seed; seeds = %d needs fused=False"
                                % self.seeds)
         self.modes = int(modes)
+        self.symmetry = symmetry
+        if symmetry is not None and not self.modes:
+            raise RuntimeError("symmetry selects the stage-2 seeds modulo the group: it needs modes = K (seeds, resample and the "
+                               "one-launch step know no symmetry)")
         if self.modes:
             if not 1 <= self.modes <= 64:
                 raise RuntimeError("modes = %d outside 1..64" % self.modes)
@@ -313,7 +318,8 @@ class CoarseToFine:
         if self.collectives:  # modes do not compose across shards: the whole row on every rank, then ONE selection
             s_all = all_gather_scores(s1, self.R_coarse.shape[-3], group=self.group, force=True, out=self._s_all,
                                       staging=self._s_stage)
-        klist = o.topk_modes(s_all, self.R_coarse, K, self.mode_angle_deg, keys=self._klist, workspace=self._modes_ws)
+        sym = {} if self.symmetry is None else {"symmetry": self.symmetry}   # (None: the call is the previous one)
+        klist = o.topk_modes(s_all, self.R_coarse, K, self.mode_angle_deg, keys=self._klist, workspace=self._modes_ws, **sym)
         R_fine_all = o.compose_rotations_topk(klist, self.R_coarse, self.D, out=self._R_fine)
         R_fine = R_fine_all if self.world == 1 else R_fine_all[:, self.f_lo:self.f_hi]
         s2, _ = o.score_hypotheses(vol_src, f_tgt, R_fine, self.W1, self.W2, self.b2, n_offset=self.f_lo, want_scores=True, **kw)

@@ -35,9 +35,13 @@ runs the forward recursion of the same model per frame (``marginal_step``, after
 ``smoothed_marginals()`` the backward one: a row of log-weights per past frame, the probability that the trajectory passes
 through each particle given every recorded frame, which ``pose_posterior`` turns into a smoothed mean pose, its spread, the
 mass that agrees with the frame's most probable particle and the entropy.
+A symmetric object has |G| equivalent clusters of particles, and the MAP pose hops between them from frame to frame.
+``symmetry=`` (a ``rotations.Symmetry`` in the source view's frame) folds the predicted set into the fundamental domain around the
+previous frame's MAP pose (``sym_fold``, one launch before ``verify_pair``): the cloud lives in one domain, so the MAP pose, the
+posterior and both smoothers need no change.
 Not built: sigma adapted from the entropy, the tracker inside the multi-view path (``ops.verify_views``), a fixed-lag marginal
-inside the captured step, and the velocity-noise term of the constant-velocity transition (the smoother's transition is
-pose-only).
+inside the captured step, the velocity-noise term of the constant-velocity transition (the smoother's transition is
+pose-only), and symmetry-aware transitions inside the smoothers (the fold makes them unnecessary for a tracked cloud).
 """
 from __future__ import annotations
 
@@ -95,6 +99,13 @@ class PoseTracker:
     ``smooth_step``, with the same scale and jump.  It observes and never steers: every ``TrackStep``, the ring and
     ``smoothed()`` are the same bytes with and without it.  ``smoothed_marginals()`` returns the marginals.
 
+    ``symmetry=sym`` (``backend`` then also provides ``sym_fold``; refused at construction otherwise): every step issues one
+    ``sym_fold`` after the predict step and before ``verify_pair``, in place on the step's particle buffer (and, with
+    ``motion="constant_velocity"``, on its velocity buffer: a body-frame velocity turns with the element).  The single anchor is
+    the previous frame's ``R_map``, with no angle limit; ``keep`` is 1, or 2 with ``coast``, so the elite (and the coasting slot)
+    stay bit for bit.  The launch sits inside the captured chain.  The fresh Haar slots are folded too: they are still uniform on
+    the quotient, but no longer the sampler's bytes.  ``symmetry=None``: the previous tracker, call for call.
+
     ``use_graph=True`` (HIP backend only; refused with a ``backend`` or on the CPU): the first step after ``init`` reads the N0-sized set and runs eagerly; the two halves of
     the ping-pong are then captured as one hipGraph each, by the second and the third step, and every later step replays the
     graph of its half.  Each graph is the linear chain of the step's launches.  The two capturing steps synchronise with the
@@ -107,9 +118,12 @@ class PoseTracker:
                  seed: int = 0, posterior: bool = False, mode_angle_deg: float = 15.0, use_graph: bool = False, backend=None,
                  motion: str = "walk", sigma_vel_deg: float = 1.0, damping: float = 1.0, max_speed_deg: Optional[float] = None,
                  coast: bool = True, history: int = 0, smooth_sigma_deg: Optional[float] = None, smooth_jump: float = 8.0,
-                 marginals: bool = False):
+                 marginals: bool = False, symmetry=None):
         dev = W1.device
         self.ops = ops if backend is None else backend
+        self.symmetry = symmetry
+        if symmetry is not None and not hasattr(self.ops, "sym_fold"):
+            raise RuntimeError("symmetry needs a backend that provides sym_fold")
         self.W1, self.W2, self.b2 = W1, W2, b2
         self.M, self.B = int(particles), int(batch)
         if not 1 <= self.M < (1 << 31):
@@ -177,6 +191,7 @@ class PoseTracker:
         self._hist = ops.smooth_history(B, M, self.history, dev, velocities=motion != "walk") if self.history else None
         self._marg = ops.marginal_history(B, M, self.history, dev) if self.marginals else None
         self._cur = None      # (R, scores, key) of the set the next step draws from
+        self._anchor = None   # (B,3,3): the previous frame's MAP pose, the anchor of the fold (symmetry)
         self._n = 0           # steps since init
         self._static = None
         self._graphs = {}     # half of the ping-pong -> (captured graph, its TrackStep)
@@ -223,6 +238,7 @@ class PoseTracker:
             self._ws0, self._ws0_n = ops.resample_workspace(self.B, n0, R0.device), n0
         self._step.zero_()
         self._cur, self._n, self._vel = (R0, scores, key), 0, None
+        self._anchor = R_map   # the pose the next step folds around (symmetry)
         post = self._posterior(scores, R0, R_map)
         return TrackStep(score, idx, R_map, R0, scores, None, *post, torch.zeros_like(idx, dtype=torch.bool))
 
@@ -243,6 +259,9 @@ class PoseTracker:
                                        n_fresh=self.n_fresh, max_angle_deg=self.max_angle_deg, max_speed_deg=self.max_speed_deg,
                                        out=self._R[p], vel_out=self._V[p])
             first = 2 if self.coast else 1
+        if self.symmetry is not None:   # in place: one fundamental domain around the previous MAP pose; the elite slots are kept
+            V = self._V[p] if self._V is not None else None
+            o.sym_fold(R, self.symmetry, self._anchor[:, None], None, keep=min(first, self.M), V=V, out=R, V_out=V, want_info=False)
         scores, key = o.verify_pair(vol_src, vol_tgt, R, self.W1, self.W2, self.b2, want_scores=True, best_key=self._keys[p],
                                     reset_best=True, scores_out=self._scores[p])
         score, idx, R_map = o.select_rotation(key, R, out=self._sel[p])
@@ -338,6 +357,7 @@ class PoseTracker:
             graph, out = self._graphs[p]
             graph.replay()
         self._cur, self._n = (self._R[p], self._scores[p], self._keys[p]), n
+        self._anchor = self._sel[p][2]
         if self._V is not None:
             self._vel = self._V[p]
         return out
