@@ -32,6 +32,7 @@ AHV_VIEWS_RESET_BEST = 1
 AHV_VIEWS_NO_ANGLE_LIMIT = 2
 AHV_VIEW_SLOT_EXCLUDED = -1
 AHV_VIEW_SLOT_OVERFLOW = -2
+AHV_GATHER_BROADCAST = 1
 
 _vp = ctypes.c_void_p
 _i64 = ctypes.c_int64
@@ -123,6 +124,10 @@ SIGNATURES["ahv_view_rotations_compact_f32"] = (_int, [_vp, _i64, _vp, _vp, _int
                                                        _vp, ctypes.c_size_t, _vp])
 # (scores, slot, weights: HOST floats, B, V, N, capacity, n_offset, fused, best_key, flags, stream)
 SIGNATURES["ahv_fuse_view_scores_compact_f32"] = (_int, [_vp, _vp, _vp, _int, _int, _i64, _i64, _i64, _vp, _vp, _u32, _vp])
+# (anchor, A, B, V, K, view_idx: int32, A_sel, stream)
+SIGNATURES["ahv_nearest_views_f32"] = (_int, [_vp, _vp, _int, _int, _int, _vp, _vp, _vp])
+# (src, view_idx: int32 or NULL with AHV_GATHER_BROADCAST, B, V, K, L, dst, flags, stream)
+SIGNATURES["ahv_gather_views_f32"] = (_int, [_vp, _vp, _int, _int, _int, _i64, _vp, _u32, _vp])
 SIGNATURES["ahv_resample_workspace_bytes"] = (ctypes.c_size_t, [_int, _i64])
 # (scores, B, N, beta, M, u: DEVICE floats or NULL, idx, workspace, workspace_bytes, flags, stream)
 SIGNATURES["ahv_resample_f32"] = (_int, [_vp, _int, _i64, ctypes.c_float, _i64, _vp, _vp, _vp, ctypes.c_size_t, _u32, _vp])

@@ -38,6 +38,8 @@ hipError_t launch_sym_fold(const float*, int64_t, int, int64_t, const float*, in
 hipError_t launch_view_rotations(const float*, int64_t, const float*, int, int, int64_t, float*, hipStream_t);
 hipError_t launch_fuse_views(const float*, const float*, int64_t, const float*, const float*, int, int, int64_t, int64_t, float,
                              bool, float*, int64_t*, hipStream_t);
+hipError_t launch_nearest_views(const float*, const float*, int, int, int, int32_t*, float*, hipStream_t);
+hipError_t launch_gather_views(const void*, const int32_t*, int, int, int, int64_t, void*, bool, hipStream_t);
 int64_t view_compact_tiles(int64_t N);
 hipError_t launch_view_rotations_compact(const float*, int64_t, const float*, const float*, int, int, int64_t, float, int64_t,
                                          float*, int32_t*, int64_t*, void*, hipStream_t);
@@ -851,6 +853,41 @@ int ahv_fuse_view_scores_f32(const float* scores, const float* Q, int64_t q_batc
     hipError_t e = ahv::launch_fuse_views(scores, Q, q_batch_stride, A, weights, B, V, N, n_offset, min_trace, limit, fused,
                                           best_key, s);
     if (e != hipSuccess) return hip_fail("fuse_view_scores: launch", e);
+    return AHV_OK;
+}
+
+// the selection entries: K of V views per sample
+static int views_selection(const char* who, int B, int V, int K)
+{
+    if (V < 1 || V > AHV_VIEWS_MAX) return fail(AHV_EINVAL, "%s: V = %d outside 1..%d", who, V, AHV_VIEWS_MAX);
+    if (K < 1 || K > V) return fail(AHV_EINVAL, "%s: K = %d outside 1..V = %d", who, K, V);
+    if (B < 1) return fail(AHV_EINVAL, "%s: B = %d must be at least 1", who, B);
+    if (B > 65535) return fail(AHV_EINVAL, "%s: B > 65535", who);
+    return AHV_OK;
+}
+
+int ahv_nearest_views_f32(const float* anchor, const float* A, int B, int V, int K, int32_t* view_idx, float* A_sel, void* stream)
+{
+    if (int rc = views_selection("nearest_views", B, V, K)) return rc;
+    if (!anchor || !A || !view_idx || !A_sel) return fail(AHV_EINVAL, "nearest_views: null pointer");
+    hipError_t e = ahv::launch_nearest_views(anchor, A, B, V, K, view_idx, A_sel, static_cast<hipStream_t>(stream));
+    if (e != hipSuccess) return hip_fail("nearest_views: launch", e);
+    return AHV_OK;
+}
+
+int ahv_gather_views_f32(const float* src, const int32_t* view_idx, int B, int V, int K, int64_t L, float* dst, unsigned flags,
+                         void* stream)
+{
+    if (int rc = views_selection("gather_views", B, V, K)) return rc;
+    if (flags & ~AHV_GATHER_BROADCAST) return fail(AHV_EINVAL, "gather_views: unknown flags 0x%x", flags);
+    const bool broadcast = (flags & AHV_GATHER_BROADCAST) != 0;
+    if (L < 4 || (L & 3)) return fail(AHV_EINVAL, "gather_views: L = %lld must be a positive multiple of 4 floats", (long long)L);
+    if (L > (int64_t)1 << 40) return fail(AHV_EINVAL, "gather_views: L = %lld exceeds 2^40 floats per row", (long long)L);
+    if (!src || !dst || (!broadcast && !view_idx)) return fail(AHV_EINVAL, "gather_views: null pointer");
+    if ((reinterpret_cast<uintptr_t>(src) | reinterpret_cast<uintptr_t>(dst)) & 15)
+        return fail(AHV_EINVAL, "gather_views: src and dst must be 16-byte aligned (the rows move as 16-byte words)");
+    hipError_t e = ahv::launch_gather_views(src, view_idx, B, V, K, L / 4, dst, broadcast, static_cast<hipStream_t>(stream));
+    if (e != hipSuccess) return hip_fail("gather_views: launch", e);
     return AHV_OK;
 }
 

@@ -750,6 +750,76 @@ __global__ __launch_bounds__(kTopkThreads) void fuse_views_kernel(const float* _
 }
 
 // ---------------------------------------------------------------------------------
+// The nearest views of a pose, and staging what belongs to them (ahv_nearest_views_f32 / ahv_gather_views_f32): a tracked
+// particle cloud sits within a few degrees of one pose, so only the K reference views nearest that pose are scored.
+//  - nearest_views_kernel: 16 lanes per sample, lane v holds A_v and t_v = view_trace(anchor, A_v) -- the chain that decides
+//    participation in fuse_views_kernel, so "the K nearest" and "within the angle" agree to the bit.  The V values go through
+//    LDS and lane v counts the views ranked ahead of it (t descending, the lower v first among equals, a NaN behind every
+//    number): that count is its place, and the lanes with a place below K write their index and a bit copy of their matrix.
+//    The anchor is read here, on the device: a replayed graph follows a pose that has moved.  No atomics.
+//  - gather_views_kernel: dst[b][k] = src[b][view_idx[b][k]] as 16-byte bit copies; workgroup (row, chunk) reads its row's
+//    index once (uniform), an index outside 0..V-1 gives a row of zeros, broadcast reads src[b] for every k.
+// ---------------------------------------------------------------------------------
+constexpr int kNearestThreads = 256;
+
+__device__ __forceinline__ bool view_ranks_ahead(float tu, int u, float tv, int v)
+{
+    const bool nu = tu != tu, nv = tv != tv;
+    if (nu || nv) return nu == nv ? u < v : nv;  // a number ranks ahead of a NaN; NaNs among themselves by v
+    return tu > tv || (tu == tv && u < v);
+}
+
+__global__ __launch_bounds__(kNearestThreads) void nearest_views_kernel(const float* __restrict__ anchor,
+                                                                        const float* __restrict__ A, int B, int V, int K,
+                                                                        int* __restrict__ view_idx, float* __restrict__ A_sel)
+{
+    __shared__ float ts[kNearestThreads / kViewsMax][kViewsMax];
+    const int tid = threadIdx.x, v = tid % kViewsMax, sl = tid / kViewsMax;
+    const long b = (long)blockIdx.x * (kNearestThreads / kViewsMax) + sl;
+    const bool live = b < B && v < V;
+    float a[9];
+    float t = 0.0f;
+    if (live) {
+        float q[9];
+#pragma unroll
+        for (int i = 0; i < 9; ++i) {
+            q[i] = anchor[b * 9 + i];
+            a[i] = A[(b * V + v) * 9 + i];
+        }
+        t = view_trace(q, a);
+    }
+    ts[sl][v] = t;
+    __syncthreads();
+    if (!live) return;
+    int place = 0;
+    for (int u = 0; u < V; ++u) place += (u != v && view_ranks_ahead(ts[sl][u], u, t, v)) ? 1 : 0;
+    if (place >= K) return;
+    view_idx[b * K + place] = v;
+    float* o = A_sel + (b * K + place) * 9;
+#pragma unroll
+    for (int i = 0; i < 9; ++i) o[i] = a[i];
+}
+
+constexpr int kGatherThreads = 256;
+
+__global__ __launch_bounds__(kGatherThreads) void gather_views_kernel(const uint4* __restrict__ src, const int* __restrict__ view_idx,
+                                                                      int V, int K, long L4, bool broadcast,
+                                                                      uint4* __restrict__ dst)
+{
+    const long row = blockIdx.x;  // b K + k
+    const long b = row / K;
+    long from = b;
+    if (!broadcast) {
+        const int v = view_idx[row];
+        from = (v >= 0 && v < V) ? b * V + v : -1;
+    }
+    uint4* d = dst + row * L4;
+    const uint4* s = from >= 0 ? src + from * L4 : nullptr;
+    for (long i = (long)blockIdx.y * kGatherThreads + threadIdx.x; i < L4; i += (long)gridDim.y * kGatherThreads)
+        d[i] = s ? s[i] : make_uint4(0u, 0u, 0u, 0u);
+}
+
+// ---------------------------------------------------------------------------------
 // Angle-limited multi-view verification, compact (ahv_view_rotations_compact_f32 / ahv_fuse_view_scores_compact_f32): under an
 // angle limit only the pairs with g_{v,n} = [w_v > 0] [t(Q_n, A_v) >= tau] are composed and scored.  Per (b, v) the
 // participating hypotheses are numbered in increasing n (a stable compaction): slot[b][v][n] = that number m while m < capacity,
@@ -1840,6 +1910,26 @@ hipError_t launch_fuse_views(const float* scores, const float* Q, int64_t q_batc
     const dim3 grid((unsigned)(tiles < 1024 ? tiles : 1024), (unsigned)B);
     hipLaunchKernelGGL(fuse_views_kernel, grid, dim3(kTopkThreads), 0, stream, scores, Q, (long)q_batch_stride, A, w, V, (long)N,
                        (long)n_offset, tau, limit, fused, reinterpret_cast<key_t*>(best_key));
+    return hipGetLastError();
+}
+
+hipError_t launch_nearest_views(const float* anchor, const float* A, int B, int V, int K, int32_t* view_idx, float* A_sel,
+                                hipStream_t stream)
+{
+    constexpr int per = kNearestThreads / kViewsMax;  // samples per workgroup
+    hipLaunchKernelGGL(nearest_views_kernel, dim3((unsigned)((B + per - 1) / per)), dim3(kNearestThreads), 0, stream, anchor, A, B, V,
+                       K, view_idx, A_sel);
+    return hipGetLastError();
+}
+
+// L4: the row length in 16-byte units; grid (B K rows, up to 64 chunks of a row)
+hipError_t launch_gather_views(const void* src, const int32_t* view_idx, int B, int V, int K, int64_t L4, void* dst, bool broadcast,
+                               hipStream_t stream)
+{
+    const int64_t chunks = (L4 + kGatherThreads - 1) / kGatherThreads;
+    const dim3 grid((unsigned)((int64_t)B * K), (unsigned)(chunks < 64 ? chunks : 64));
+    hipLaunchKernelGGL(gather_views_kernel, grid, dim3(kGatherThreads), 0, stream, static_cast<const uint4*>(src), view_idx, V, K,
+                       (long)L4, broadcast, static_cast<uint4*>(dst));
     return hipGetLastError();
 }
 

@@ -21,7 +21,7 @@ exercise this file's plumbing without a GPU -- the product default has no CPU pa
 from __future__ import annotations
 
 import os
-from typing import Callable, Dict, Iterable, Optional
+from typing import Callable, Dict, Iterable, Optional, Sequence
 
 import numpy as np
 import torch
@@ -236,7 +236,8 @@ def evaluate_category(cfg, model, sequences: Iterable[dict], num_frames: int = 2
 @torch.no_grad()
 def track_sequence(model, item: dict, tracker, ref: int = 0, proposals: Optional[torch.Tensor] = None, device=None,
                    encoder_fn: Optional[Callable] = None, row_vector_R: bool = False, smoothed: bool = False,
-                   marginals: bool = False) -> dict:
+                   marginals: bool = False, refs: Optional[Sequence[int]] = None, views_per_step: Optional[int] = None,
+                   max_view_angle_deg: Optional[float] = None) -> dict:
     """Track ONE sequence with a ``track.PoseTracker`` (batch 1).  ``item`` is what ``SyntheticSequences`` or
     ``co3d.Co3dSequences`` yields.  Frame ``ref`` is the reference view; every other frame is tracked in order: per frame the
     encoder runs on (reference, frame) -- ``encoder_fn`` or ``model.forward_features`` for ``layer4`` inputs, else ``model`` --,
@@ -256,7 +257,25 @@ def track_sequence(model, item: dict, tracker, ref: int = 0, proposals: Optional
     like ``"smoothed"`` from ``tracker.smoothed_marginals()`` -- ``idx`` and ``R`` the most probable particle of each frame's
     smoothed marginal, ``err`` its error -- and, when the tracker's backend has ``pose_posterior``, ``"R_mean" (F',3,3)``,
     ``"err_mean"``, ``"spread_deg"``, ``"mode_mass"`` and ``"entropy"`` (F',): the marginal-weighted mean pose and its error, the
-    spread, the mass within the tracker's ``mode_angle_deg`` of ``R`` and the entropy of the marginal."""
+    spread, the mass within the tracker's ``mode_angle_deg`` of ``R`` and the entropy of the marginal.
+    ``refs=[i0, i1, ...]`` (a tracker built with ``views=item["R"][refs]``, ``views_per_step`` and ``max_view_angle_deg``; the
+    two keywords here must repeat the tracker's, or be None): the listed frames are the reference views, with their ``item["R"]``
+    as ``A``; ``ref`` is not used, every other frame is tracked, and the tracker's poses -- and ``err`` -- are the frames'
+    ABSOLUTE rotations in ``A``'s frame.  The first tracked frame is encoded against all V references for ``tracker.init``;
+    per later frame ``tracker.select_views()`` picks the K references (no host read), their inputs are gathered by its ``idx``,
+    the encoder runs on that batch of K (reference, frame) pairs and ``tracker.step(..., staged=True)`` scores them.  Still ONE
+    host synchronisation, at the end.  ``row_vector_R=True`` (``Co3dSequences``): a model trained on annotations that act on row
+    vectors gives the pair (src, tgt) the rotation ``R_src^T R_tgt``; for the pair (reference, frame) that is ``R_v^T R_t``,
+    the reference on the LEFT, which no absolute ``Q`` turns into ``Q A_v^T`` for more than one view.  So the pair is encoded
+    the other way round, (frame, reference): its rotation ``R_t^T R_v`` is ``Q A_v^T`` with ``Q = R_t^T`` and ``A_v = R_v^T``.
+    Build the tracker with ``views=item["R"][refs].transpose(-1, -2)``; the frame's volume is then the one the scorer rotates,
+    the reference's the target, the tracker's poses are ``R_t^T`` and ``err`` is taken against that.
+    ``refs=None``: the single-reference function above."""
+    if refs is not None:
+        return _track_sequence_views(model, item, tracker, list(refs), proposals, device, encoder_fn, row_vector_R, smoothed,
+                                     marginals, views_per_step, max_view_angle_deg)
+    if views_per_step is not None or max_view_angle_deg is not None:
+        raise RuntimeError("views_per_step and max_view_angle_deg belong to refs=")
     if tracker.B != 1:
         raise RuntimeError("track_sequence tracks one sequence: the tracker must have batch = 1, got %d" % tracker.B)
     if device is None:
@@ -286,6 +305,11 @@ def track_sequence(model, item: dict, tracker, ref: int = 0, proposals: Optional
         truth.append(R_gt)
     if not order:
         return {"frames": [], "R_map": torch.zeros(0, 3, 3), "score": torch.zeros(0), "err": torch.zeros(0)}
+    return _track_result(tracker, order, R_map, score, err, truth, smoothed, marginals)
+
+
+def _track_result(tracker, order, R_map, score, err, truth, smoothed, marginals) -> dict:
+    """The result of ``track_sequence``: the ONE host copy of the per-frame rows, and the smoothers' queries."""
     packed = torch.cat([torch.stack(R_map).reshape(-1, 9), torch.stack(score)[:, None], torch.stack(err)[:, None]], dim=1).cpu()
     out = {"frames": order, "R_map": packed[:, :9].reshape(-1, 3, 3), "score": packed[:, 9], "err": packed[:, 10]}
     if smoothed:
@@ -317,6 +341,58 @@ def track_sequence(model, item: dict, tracker, ref: int = 0, proposals: Optional
                            mode_mass=mass[0].cpu(), entropy=entropy[0].cpu())
         out["marginals"] = rec
     return out
+
+
+def _track_sequence_views(model, item, tracker, refs, proposals, device, encoder_fn, row_vector_R, smoothed, marginals,
+                          views_per_step, max_view_angle_deg) -> dict:
+    """``track_sequence(refs=...)``: see there."""
+    if tracker.B != 1:
+        raise RuntimeError("track_sequence tracks one sequence: the tracker must have batch = 1, got %d" % tracker.B)
+    if getattr(tracker, "views", None) is None:
+        raise RuntimeError("refs= needs a tracker built with views= (the references' item[\"R\"])")
+    n = int(item["n"])
+    V, K = len(refs), tracker.K
+    if V != tracker.V or len(set(refs)) != V or not all(0 <= int(r) < n for r in refs):
+        raise RuntimeError("refs must be %d distinct frames of the sequence's %d (the tracker's views), got %s" % (tracker.V, n, refs))
+    if views_per_step is not None and int(views_per_step) != K:
+        raise RuntimeError("views_per_step = %d, the tracker was built with %d" % (int(views_per_step), K))
+    if max_view_angle_deg is not None and float(max_view_angle_deg) != tracker.max_view_angle_deg:
+        raise RuntimeError("max_view_angle_deg = %r, the tracker was built with %r" % (max_view_angle_deg, tracker.max_view_angle_deg))
+    if device is None:
+        device = tracker.W1.device
+    device = torch.device(device)
+    if "get_data" in item:   # lazy source (co3d.Co3dSequences): decode every frame of the sequence
+        item = dict(item, **item["get_data"](np.arange(n)))
+    uses_l4 = "layer4" in item
+    frames = (item["layer4"] if uses_l4 else item["image"]).to(device=device, dtype=torch.float32)
+    rots = item["R"].to(device=device, dtype=torch.float32)
+    where = torch.tensor([int(r) for r in refs], dtype=torch.int64, device=device)
+    ref_inputs = frames.index_select(0, where)[None].contiguous()          # (1,V,...): what gather_views picks K rows of
+    embed = (encoder_fn or model.forward_features) if uses_l4 else model
+    if proposals is None:
+        proposals = random_rotations(4096, generator=torch.Generator().manual_seed(0))
+    proposals = proposals.to(device)
+    order = [t for t in range(n) if t not in set(int(r) for r in refs)]
+    # (rotated volume, target volume) of a batch of pairs: (reference, frame), or -- row vectors -- (frame, reference)
+    pairs = (lambda r, f: embed(f, r)) if row_vector_R else embed
+    R_map, score, err, truth = [], [], [], []
+    for k, t in enumerate(order):
+        if k == 0:    # every reference against the first tracked frame
+            vol_rot, vol_tgt = pairs(ref_inputs[0], frames[t:t + 1].expand((V,) + tuple(frames.shape[1:])))
+            res = tracker.init(vol_rot[None], vol_tgt[None], proposals)
+        else:         # the K references nearest the previous MAP pose, chosen and gathered on the device
+            sel = tracker.select_views()
+            picked = tracker.ops.gather_views(ref_inputs, sel.idx)[0]
+            vol_rot, vol_tgt = pairs(picked, frames[t:t + 1].expand((K,) + tuple(frames.shape[1:])))
+            res = tracker.step(vol_rot[None], vol_tgt[None], staged=True)
+        R_gt = rots[t].transpose(0, 1) if row_vector_R else rots[t]
+        R_map.append(res.R_map[0].clone())          # (the tracker's outputs are buffers it reuses two steps later)
+        score.append(res.score[0].clone())
+        err.append(geodesic_deg(res.R_map, R_gt[None])[0])
+        truth.append(R_gt)
+    if not order:
+        return {"frames": [], "R_map": torch.zeros(0, 3, 3), "score": torch.zeros(0), "err": torch.zeros(0)}
+    return _track_result(tracker, order, R_map, score, err, truth, smoothed, marginals)
 
 
 def evaluate_pairwise(cfg, model, categories: Dict[str, Iterable[dict]], num_frames: int = 2, print_results=True,

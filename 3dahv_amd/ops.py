@@ -1910,6 +1910,177 @@ def _verify_views_compact(vol_refs, vol_query, Q, A, W1, W2, b2, weights, max_vi
     return res
 
 
+# ---- the nearest views of a pose, staged --------------------------------------------------------------------------
+# A tracked cloud sits within a few degrees of one pose: pick the K views nearest that pose on the device, stage their volumes
+# and score against those K alone (``ahv_nearest_views_f32`` / ``ahv_gather_views_f32``, include/ahv.h).
+
+ViewSelection = collections.namedtuple("ViewSelection", ["idx", "A"])
+
+
+def _selection_k(k, V: int) -> int:
+    K = int(k)
+    if not 1 <= K <= V:
+        raise RuntimeError("k = %r outside 1..V = %d" % (k, V))
+    return K
+
+
+def nearest_views(anchor: torch.Tensor, A: torch.Tensor, k: int, out: ViewSelection | None = None) -> ViewSelection:
+    """The ``k`` reference views nearest ``anchor (B,3,3)`` among ``A (B,V,3,3)`` (``ahv_nearest_views_f32``, ONE launch) ->
+    ``ViewSelection(idx (B,k) int32, A (B,k,3,3))``, nearest first: ranked by ``t = sum_ab anchor[a][b] A_v[a][b]``, descending,
+    with the fp32 chain by which ``fuse_view_scores`` decides participation; equal ``t``: the lower v first; a NaN ``t`` behind
+    every number.  ``A`` of the result holds bit copies of the chosen matrices: pass it as ``A`` to ``verify_views_staged``.
+    The anchor is read on the device (no host synchronisation; a replayed graph follows a moving pose).  ``out``: a
+    ``ViewSelection`` of that size to write into.  Inference only."""
+    _refuse_grad("nearest_views", anchor, A)
+    if A.dim() != 4 or tuple(A.shape[2:]) != (3, 3):
+        raise RuntimeError("A must be (B,V,3,3), got %s" % (tuple(A.shape),))
+    B, V = A.shape[:2]
+    if not 1 <= V <= _lib.AHV_VIEWS_MAX:
+        raise RuntimeError("V = %d outside 1..%d" % (V, _lib.AHV_VIEWS_MAX))
+    K = _selection_k(k, V)
+    if tuple(anchor.shape) != (B, 3, 3):
+        raise RuntimeError("anchor must be (B,3,3) with B = %d, got %s" % (B, tuple(anchor.shape)))
+    dev = _need_gpu(anchor, A)
+    if out is None:
+        out = ViewSelection(torch.empty((B, K), dtype=torch.int32, device=dev), torch.empty((B, K, 3, 3), dtype=torch.float32, device=dev))
+    elif (tuple(out.idx.shape) != (B, K) or out.idx.dtype != torch.int32 or tuple(out.A.shape) != (B, K, 3, 3)
+          or out.A.dtype != torch.float32 or out.idx.device != dev or out.A.device != dev or not out.idx.is_contiguous()
+          or not out.A.is_contiguous()):
+        raise RuntimeError("out must be ViewSelection(idx: contiguous int32 (B,k), A: contiguous float32 (B,k,3,3)) on %s" % dev)
+    _call(dev, "ahv_nearest_views_f32", anchor.detach().contiguous().data_ptr(), A.detach().contiguous().data_ptr(), B, V, K,
+          out.idx.data_ptr(), out.A.data_ptr())
+    return out
+
+
+def gather_views(src: torch.Tensor, idx: torch.Tensor, out: torch.Tensor | None = None, broadcast: bool = False) -> torch.Tensor:
+    """``out[b, k] = src[b, idx[b, k]]`` as bit copies (``ahv_gather_views_f32``, ONE launch): ``src (B,V,...)``, ``idx (B,K)``
+    int32 (a ``ViewSelection.idx``), ``out (B,K,...)``.  The trailing dimensions hold a multiple of 4 floats (a feature volume:
+    8192; the encoder's inputs are as good) and ``src`` and ``out`` are contiguous and 16-byte aligned.  An index outside
+    0..V-1 gives a row of zeros.  ``broadcast=True``: ``src (B,...)`` has no view axis and every k receives ``src[b]``.
+    Inference only."""
+    _refuse_grad("gather_views", src)
+    if idx.dim() != 2:
+        raise RuntimeError("idx must be (B,K), got %s" % (tuple(idx.shape),))
+    B, K = idx.shape
+    lead = 1 if broadcast else 2
+    if src.dim() <= lead or src.shape[0] != B:
+        raise RuntimeError("src must be %s with B = %d, got %s" % ("(B,...)" if broadcast else "(B,V,...)", B, tuple(src.shape)))
+    V = K if broadcast else src.shape[1]
+    if not 1 <= V <= _lib.AHV_VIEWS_MAX:
+        raise RuntimeError("V = %d outside 1..%d" % (V, _lib.AHV_VIEWS_MAX))
+    _selection_k(K, V)
+    rest = tuple(src.shape[lead:])
+    L = 1
+    for d in rest:
+        L *= int(d)
+    if L < 4 or L % 4:
+        raise RuntimeError("the rows of src hold L = %d floats: gather_views moves 16-byte words, L must be a positive multiple of 4" % L)
+    dev = _need_gpu(src)
+    if idx.device != dev or idx.dtype != torch.int32 or not idx.is_contiguous():
+        raise RuntimeError("idx must be a contiguous int32 tensor on %s, got %s on %s" % (dev, idx.dtype, idx.device))
+    if not src.is_contiguous():
+        raise RuntimeError("src must be contiguous (gather_views makes no copy of its own)")
+    if out is None:
+        out = torch.empty((B, K) + rest, dtype=torch.float32, device=dev)
+    elif tuple(out.shape) != (B, K) + rest or out.dtype != torch.float32 or out.device != dev or not out.is_contiguous():
+        raise RuntimeError("out must be a contiguous float32 %s tensor on %s" % ((B, K) + rest, dev))
+    if (src.data_ptr() | out.data_ptr()) & 15:
+        raise RuntimeError("src and out must be 16-byte aligned (the rows move as 16-byte words)")
+    _call(dev, "ahv_gather_views_f32", src.detach().data_ptr(), idx.data_ptr(), B, V, K, L, out.data_ptr(),
+          _lib.AHV_GATHER_BROADCAST if broadcast else 0)
+    return out
+
+
+class verify_views_workspace:
+    """What ``verify_views_staged`` needs between its launches on (B, K, N): ``R (B,K,N,3,3)``, the per-view rotations;
+    ``scores (B,K,N)``, the per-view scores; ``keys (B*K,)``, the scoring launch's own keys; and, each on first use, ``query
+    (B,K,16,8,8,8)``, the K-fold copy of a query volume that is shared by the views, and ``feat (B*K,32,64)``, the target
+    features of the split-f16 scorer.  Allocate once, pass to every call: past the first one a call allocates nothing."""
+
+    def __init__(self, B: int, K: int, N: int, device):
+        self.B, self.K, self.N = int(B), int(K), int(N)
+        f = lambda *shape: torch.empty(shape, dtype=torch.float32, device=device)
+        self.R = f(self.B, self.K, self.N, 3, 3)
+        self.scores = f(self.B, self.K, self.N)
+        self.keys = torch.empty((self.B * self.K,), dtype=torch.int64, device=device)
+        self.query = self.feat = None
+
+    def shared_query(self) -> torch.Tensor:
+        if self.query is None:
+            self.query = torch.empty((self.B, self.K) + _VOL, dtype=torch.float32, device=self.R.device)
+        return self.query
+
+    def features(self) -> torch.Tensor:
+        if self.feat is None:
+            self.feat = torch.empty((self.B * self.K, 32, 64), dtype=torch.float32, device=self.R.device)
+        return self.feat
+
+
+def verify_views_staged(vol_refs: torch.Tensor, vol_query: torch.Tensor, Q: torch.Tensor, A_sel: torch.Tensor, W1: torch.Tensor,
+                        W2: torch.Tensor, b2: torch.Tensor, max_view_angle_deg: float | None = None,
+                        workspace: verify_views_workspace | None = None, scores_out: torch.Tensor | None = None,
+                        best_key: torch.Tensor | None = None, reset_best: bool | None = None, split_f16: bool | None = None):
+    """``verify_views`` on K staged views, with every buffer the caller's: ``vol_refs (B,K,16,8,8,8)`` with rotations ``A_sel
+    (B,K,3,3)`` (a ``ViewSelection.A``), ``vol_query (B,K,16,8,8,8)`` -- one query volume per view, what an encoder that sees a
+    (reference, frame) pair produces -- or ``(B,16,8,8,8)``, shared by the views; hypotheses ``Q (N,3,3)`` / ``(B,N,3,3)`` of the
+    query's absolute rotation.  ``view_rotations`` into the workspace -> the scoring launch of ``verify_pair`` over the B*K
+    samples -> ``fuse_view_scores`` with weights of ones.  Returns ``(fused (B,N), best_key (B,))``; with a shared query both
+    are ``verify_views(vol_refs, vol_query, Q, A_sel, max_view_angle_deg=...)``'s bit for bit.
+    ``workspace`` (``verify_views_workspace(B, K, N, device)``), ``scores_out (B,N)`` and ``best_key (B,)`` given: no allocation
+    (graph-capturable).  ``best_key`` given: merged into unless ``reset_best``.  A hypothesis no view sees within the angle
+    scores -inf.  Inference only."""
+    _refuse_grad("verify_views_staged", vol_refs, vol_query, Q, A_sel, W1, W2, b2)
+    B, K, N, qstride = _view_poses(A_sel, Q)
+    if vol_refs.dim() != 6 or tuple(vol_refs.shape) != (B, K) + _VOL:
+        raise RuntimeError("vol_refs must be (B,K,16,8,8,8) = %s, got %s" % ((B, K) + _VOL, tuple(vol_refs.shape)))
+    shared = tuple(vol_query.shape) == (B,) + _VOL
+    if not shared and tuple(vol_query.shape) != (B, K) + _VOL:
+        raise RuntimeError("vol_query must be (B,K,16,8,8,8) or (B,16,8,8,8) with B = %d and K = %d, got %s"
+                           % (B, K, tuple(vol_query.shape)))
+    flags = 0
+    if max_view_angle_deg is None:
+        flags |= _lib.AHV_VIEWS_NO_ANGLE_LIMIT
+        tau = 0.0
+    else:
+        tau = min_trace(max_view_angle_deg)
+    dev = _need_gpu(vol_refs, vol_query, Q, A_sel, W1, W2, b2)
+    ws = workspace
+    if ws is None:
+        ws = verify_views_workspace(B, K, N, dev)
+    elif (ws.B, ws.K, ws.N) != (B, K, N) or ws.R.device != dev:
+        raise RuntimeError("workspace was made for (B, K, N) = %s on %s, the call has %s on %s"
+                           % ((ws.B, ws.K, ws.N), ws.R.device, (B, K, N), dev))
+    if scores_out is None:
+        scores_out = torch.empty((B, N), dtype=torch.float32, device=dev)
+    elif (scores_out.dtype != torch.float32 or tuple(scores_out.shape) != (B, N) or not scores_out.is_contiguous()
+          or scores_out.device != dev):
+        raise RuntimeError("scores_out must be a contiguous float32 (B,N) = %s tensor on %s" % ((B, N), dev))
+    if best_key is None:
+        best_key = torch.empty((B,), dtype=torch.int64, device=dev)
+        reset_best = True
+    elif best_key.dtype != torch.int64 or best_key.numel() != B or best_key.device != dev or not best_key.is_contiguous():
+        raise RuntimeError("best_key must be a contiguous int64 tensor of B = %d elements on %s" % (B, dev))
+    if reset_best:
+        flags |= _lib.AHV_VIEWS_RESET_BEST
+    split = bool(_SPLIT_F16.get() if split_f16 is None else split_f16)
+    with torch.no_grad():
+        Qc, Ac = Q.detach().contiguous(), A_sel.detach().contiguous()
+        _call(dev, "ahv_view_rotations_f32", Qc.data_ptr(), qstride, Ac.data_ptr(), B, K, N, ws.R.data_ptr())
+        Rv = ws.R.view(B * K, N, 3, 3)
+        vq = vol_query.detach().contiguous()
+        if shared:
+            copies = ws.shared_query()
+            _call(dev, "ahv_gather_views_f32", vq.data_ptr(), None, B, K, K, 16 * 8 * 8 * 8, copies.data_ptr(),
+                  _lib.AHV_GATHER_BROADCAST)   # the K-fold copy the scoring launch reads per sample
+            vq = copies
+        _score_hypotheses_nograd(vol_refs.detach().reshape((B * K,) + _VOL), vq.view((B * K,) + _VOL), Rv, W1, W2, b2, 0, True, ws.keys,
+                                 True, split, None, tgt_is_volume=True, feat_tgt_out=ws.features() if split else None,
+                                 scores_out=ws.scores.view(B * K, N))
+        _call(dev, "ahv_fuse_view_scores_f32", ws.scores.data_ptr(), Qc.data_ptr(), qstride, Ac.data_ptr(), None, B, K, N, 0, tau,
+              scores_out.data_ptr(), best_key.data_ptr(), flags)
+    return scores_out, best_key
+
+
 # ---- rotation gradient of the score, gradient-based pose polishing ------------------------------------------
 
 @torch.no_grad()

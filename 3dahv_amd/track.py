@@ -39,7 +39,14 @@ A symmetric object has |G| equivalent clusters of particles, and the MAP pose ho
 ``symmetry=`` (a ``rotations.Symmetry`` in the source view's frame) folds the predicted set into the fundamental domain around the
 previous frame's MAP pose (``sym_fold``, one launch before ``verify_pair``): the cloud lives in one domain, so the MAP pose, the
 posterior and both smoothers need no change.
-Not built: sigma adapted from the entropy, the tracker inside the multi-view path (``ops.verify_views``), a fixed-lag marginal
+One reference view cannot carry a pose through a full turn: the network is trained on pairs closer than ``DATA.VIEW_THR`` (90
+degrees, the limit ``fuse_view_scores`` cites), so past that range a single-reference tracker has no trustworthy score.
+``views=A`` gives the tracker V posed reference views: its particles are then ABSOLUTE poses Q in the frame of ``A`` (view v sees
+``Q A_v^T``), and per step it picks, on the device, the ``views_per_step`` views nearest the previous MAP pose
+(``nearest_views``), stages their volumes (``gather_views``) and scores the set against those alone, fused under the angle
+limit (``verify_views_staged``) -- all inside the captured chain, with no host read.
+Not built: sigma adapted from the entropy, per-view weights other than present / absent and per-particle view selection inside
+the tracker, the compact multi-view path inside the tracker, symmetry together with views, a fixed-lag marginal
 inside the captured step, the velocity-noise term of the constant-velocity transition (the smoother's transition is
 pose-only), and symmetry-aware transitions inside the smoothers (the fold makes them unnecessary for a tracked cloud).
 """
@@ -106,6 +113,25 @@ class PoseTracker:
     stay bit for bit.  The launch sits inside the captured chain.  The fresh Haar slots are folded too: they are still uniform on
     the quotient, but no longer the sampler's bytes.  ``symmetry=None``: the previous tracker, call for call.
 
+    ``views=A`` (``(V,3,3)`` or ``(B,V,3,3)``, the reference views' absolute rotations; ``backend`` then also provides
+    ``nearest_views``, ``gather_views`` and ``verify_views_staged``): particles, ``R_map``, the smoother's ring and the posterior are
+    absolute poses in the frame of ``A``.  ``views_per_step=K`` views are scored per step (None: all V), ``max_view_angle_deg``
+    is the angle limit of the fusion (None: none).  ``init(vol_refs (B,V,16,8,8,8), vol_query (B,16,8,8,8) or (B,V,16,8,8,8),
+    R_init)`` scores ``R_init`` densely over all V views.  The tracker owns the selection (``view_selection``: ``idx (B,K)`` int32
+    and ``A (B,K,3,3)``), the staged volumes ``buffers = (refs (B,K,16,8,8,8), query (B,K,16,8,8,8))`` and the workspace.
+    ``select_views()`` is one launch whose anchor is the current MAP pose, read on the device; it returns the ``ViewSelection``
+    the next step uses.  ``step(vol_refs (B,V,...), vol_query (B,...) or (B,V,...))`` runs select -> gather -> the chain;
+    ``step(refs_K, query_K, staged=True)`` and ``step()`` run the chain on what is staged (the caller gathered the K references'
+    inputs by ``view_selection.idx`` and encoded K pairs) and raise unless ``select_views()`` was called since the last step.
+    The chain is that of the module docstring with ``verify_views_staged`` in the place of ``verify_pair``; the smoothers and the
+    posterior follow unchanged: they see ``(Q, fused scores)``.  A particle no selected view sees within the angle limit scores
+    -inf, and by ``resample``'s rule for such a score (it takes no part and is never drawn) it leaves no descendant; a fresh
+    Haar slot far from the selected views therefore cannot re-acquire -- ``views_per_step=None`` scores every view and can.
+    With ``use_graph=True`` each kind of step is captured once per half of the ping-pong -- selection, gather and the chain, or
+    the chain alone for a staged step --, and the anchor being read on the device, a replay follows a selection that has
+    changed since the capture; ``view_inputs`` are the static ``(B,V,...)`` inputs of the first kind, ``buffers`` of the second.
+    ``symmetry=`` together with ``views`` is refused.  ``views=None``: the previous tracker, call for call.
+
     ``use_graph=True`` (HIP backend only; refused with a ``backend`` or on the CPU): the first step after ``init`` reads the N0-sized set and runs eagerly; the two halves of
     the ping-pong are then captured as one hipGraph each, by the second and the third step, and every later step replays the
     graph of its half.  Each graph is the linear chain of the step's launches.  The two capturing steps synchronise with the
@@ -118,10 +144,31 @@ class PoseTracker:
                  seed: int = 0, posterior: bool = False, mode_angle_deg: float = 15.0, use_graph: bool = False, backend=None,
                  motion: str = "walk", sigma_vel_deg: float = 1.0, damping: float = 1.0, max_speed_deg: Optional[float] = None,
                  coast: bool = True, history: int = 0, smooth_sigma_deg: Optional[float] = None, smooth_jump: float = 8.0,
-                 marginals: bool = False, symmetry=None):
+                 marginals: bool = False, symmetry=None, views: Optional[torch.Tensor] = None,
+                 views_per_step: Optional[int] = None, max_view_angle_deg: Optional[float] = None):
         dev = W1.device
         self.ops = ops if backend is None else backend
         self.symmetry = symmetry
+        self.views = None
+        if views is None:
+            if views_per_step is not None or max_view_angle_deg is not None:
+                raise RuntimeError("views_per_step and max_view_angle_deg belong to views=")
+        else:
+            if symmetry is not None:
+                raise RuntimeError("symmetry= together with views= is not built")
+            if not all(hasattr(self.ops, n) for n in ("nearest_views", "gather_views", "verify_views_staged")):
+                raise RuntimeError("views= needs a backend that provides nearest_views, gather_views and verify_views_staged")
+            if views.dim() not in (3, 4) or tuple(views.shape[-2:]) != (3, 3) or (views.dim() == 4 and views.shape[0] != int(batch)):
+                raise RuntimeError("views must be (V,3,3) or (B,V,3,3) with B = %d, got %s" % (int(batch), tuple(views.shape)))
+            self.V = int(views.shape[-3])
+            if not 1 <= self.V <= ops._lib.AHV_VIEWS_MAX:
+                raise RuntimeError("views: V = %d outside 1..%d" % (self.V, ops._lib.AHV_VIEWS_MAX))
+            self.K = self.V if views_per_step is None else int(views_per_step)
+            if not 1 <= self.K <= self.V:
+                raise RuntimeError("views_per_step = %r outside 1..V = %d" % (views_per_step, self.V))
+            self.max_view_angle_deg = None if max_view_angle_deg is None else float(max_view_angle_deg)
+            if self.max_view_angle_deg is not None:
+                ops.min_trace(self.max_view_angle_deg)    # raises outside (0, 180)
         if symmetry is not None and not hasattr(self.ops, "sym_fold"):
             raise RuntimeError("symmetry needs a backend that provides sym_fold")
         self.W1, self.W2, self.b2 = W1, W2, b2
@@ -194,14 +241,49 @@ class PoseTracker:
         self._anchor = None   # (B,3,3): the previous frame's MAP pose, the anchor of the fold (symmetry)
         self._n = 0           # steps since init
         self._static = None
-        self._graphs = {}     # half of the ping-pong -> (captured graph, its TrackStep)
+        self._selected = False    # select_views() since the last step (views)
+        self._graphs = {}     # half of the ping-pong (views: and whether the step selects and gathers) -> (graph, its TrackStep)
+        if views is not None:
+            A = views.detach().to(device=dev, dtype=torch.float32)
+            self.views = (A[None].expand(B, self.V, 3, 3) if A.dim() == 3 else A).contiguous()
+            K = self.K
+            self._vsel = ops.ViewSelection(torch.zeros((B, K), dtype=torch.int32, device=dev), f(B, K, 3, 3))
+            self._vws = ops.verify_views_workspace(B, K, M, dev) if hip else None
+            self._full = None        # the static (B,V,...) inputs of a captured step that selects and gathers
 
     @property
     def buffers(self):
-        """The static input volumes ``(vol_src, vol_tgt)`` of the captured step (allocated on first use)."""
+        """The static input volumes ``(vol_src, vol_tgt)`` of the captured step (allocated on first use); with ``views`` the
+        staged volumes ``(refs (B,K,16,8,8,8), query (B,K,16,8,8,8))`` of every step."""
         if self._static is None:
-            self._static = tuple(torch.zeros((self.B, 16, 8, 8, 8), dtype=torch.float32, device=self.W1.device) for _ in range(2))
+            lead = (self.B,) if self.views is None else (self.B, self.K)
+            self._static = tuple(torch.zeros(lead + (16, 8, 8, 8), dtype=torch.float32, device=self.W1.device) for _ in range(2))
         return self._static
+
+    @property
+    def view_selection(self):
+        """``ops.ViewSelection(idx (B,K) int32, A (B,K,3,3))``: the views the last step scored against, or -- after
+        ``select_views()`` -- the ones the next step will.  Buffers the tracker owns (None without ``views``)."""
+        return self._vsel if self.views is not None else None
+
+    @property
+    def view_inputs(self):
+        """The static ``(vol_refs (B,V,...), vol_query)`` of the captured step that selects and gathers (``use_graph=True``
+        with ``views``): allocated, in the shapes given, by the first such step after the eager one; None before.  Write the
+        frame's volumes there and pass the two tensors themselves to ``step`` to replay with no staging copy."""
+        return self._full if self.views is not None else None
+
+    @torch.no_grad()
+    def select_views(self):
+        """Pick the ``views_per_step`` views nearest the current MAP pose: ONE launch, the anchor read on the device.  Returns
+        the ``ViewSelection`` the next step uses (gather the K references' inputs by its ``idx``)."""
+        if self.views is None:
+            raise RuntimeError("select_views() needs a tracker built with views=")
+        if self._cur is None:
+            raise RuntimeError("call init(vol_refs, vol_query, R_init) before select_views()")
+        self.ops.nearest_views(self._anchor, self.views, self.K, out=self._vsel)
+        self._selected = True
+        return self._vsel
 
     @property
     def step_counter(self) -> torch.Tensor:
@@ -231,7 +313,12 @@ class PoseTracker:
         if vol_src.shape[0] != self.B:
             raise RuntimeError("the tracker was built for batch = %d, got volumes %s" % (self.B, tuple(vol_src.shape)))
         R0 = R_init.detach().clone(memory_format=torch.contiguous_format)   # the first step reads it: keep a copy of our own
-        scores, key = o.verify_pair(vol_src, vol_tgt, R0, self.W1, self.W2, self.b2, want_scores=True)
+        if self.views is None:
+            scores, key = o.verify_pair(vol_src, vol_tgt, R0, self.W1, self.W2, self.b2, want_scores=True)
+        else:   # densely over all V views
+            scores, key = o.verify_views_staged(vol_src, vol_tgt, R0, self.views, self.W1, self.W2, self.b2,
+                                                max_view_angle_deg=self.max_view_angle_deg)
+            self._selected = False
         score, idx, R_map = o.select_rotation(key, R0)
         n0 = R0.shape[-3]
         if self.ops is ops and R0.is_cuda and (self._ws0 is None or self._ws0_n != n0):
@@ -262,8 +349,13 @@ class PoseTracker:
         if self.symmetry is not None:   # in place: one fundamental domain around the previous MAP pose; the elite slots are kept
             V = self._V[p] if self._V is not None else None
             o.sym_fold(R, self.symmetry, self._anchor[:, None], None, keep=min(first, self.M), V=V, out=R, V_out=V, want_info=False)
-        scores, key = o.verify_pair(vol_src, vol_tgt, R, self.W1, self.W2, self.b2, want_scores=True, best_key=self._keys[p],
-                                    reset_best=True, scores_out=self._scores[p])
+        if self.views is None:
+            scores, key = o.verify_pair(vol_src, vol_tgt, R, self.W1, self.W2, self.b2, want_scores=True, best_key=self._keys[p],
+                                        reset_best=True, scores_out=self._scores[p])
+        else:   # (vol_src, vol_tgt) are the K staged views' volumes, self._vsel.A their rotations
+            scores, key = o.verify_views_staged(vol_src, vol_tgt, R, self._vsel.A, self.W1, self.W2, self.b2,
+                                                max_view_angle_deg=self.max_view_angle_deg, workspace=self._vws,
+                                                scores_out=self._scores[p], best_key=self._keys[p], reset_best=True)
         score, idx, R_map = o.select_rotation(key, R, out=self._sel[p])
         # the winner sits in a fresh slot (slot 0 is the elite, and slot 1 the coasting one, even when every slot is fresh)
         reacq = torch.ge(idx, max(self.M - self.n_fresh, first), out=self._reacq[p])
@@ -327,37 +419,83 @@ class PoseTracker:
         return (res, p.R_mean.reshape(B, F, 3, 3), p.spread_deg.reshape(B, F), p.mode_prob[:, 0].reshape(B, F),
                 p.entropy.reshape(B, F))
 
-    @torch.no_grad()
-    def step(self, vol_src: Optional[torch.Tensor] = None, vol_tgt: Optional[torch.Tensor] = None) -> TrackStep:
-        """Advance the filter by one frame.  Called with no volumes it runs on ``self.buffers`` as they are."""
-        if self._cur is None:
-            raise RuntimeError("call init(vol_src, vol_tgt, R_init) before the first step")
-        if (vol_src is None) != (vol_tgt is None):
-            raise RuntimeError("pass both volumes or neither")
+    def _run_views(self, vol_refs, vol_query, p: int) -> TrackStep:
+        """One step of a tracker with views from ``(B,V,...)`` inputs: select, gather into the staged buffers, the chain."""
+        o = self.ops
+        vol_refs, vol_query = vol_refs.detach().contiguous(), vol_query.detach().contiguous()
+        sel = o.nearest_views(self._anchor, self.views, self.K, out=self._vsel)
+        refs, query = self.buffers
+        o.gather_views(vol_refs, sel.idx, out=refs)
+        o.gather_views(vol_query, sel.idx, out=query, broadcast=vol_query.dim() == 5)
+        return self._run(refs, query, p)
+
+    def _step_views(self, vol_refs, vol_query, staged: bool) -> TrackStep:
+        B, V, K = self.B, self.V, self.K
+        vol = (16, 8, 8, 8)
+        staged = staged or vol_refs is None
+        if staged:
+            if not self._selected:
+                raise RuntimeError("a staged step scores against the views of select_views(): call it after the last step "
+                                   "(and gather the inputs by its idx)")
+            if vol_refs is not None and (tuple(vol_refs.shape) != (B, K) + vol or tuple(vol_query.shape) != (B, K) + vol):
+                raise RuntimeError("staged volumes must both be (B,K,16,8,8,8) = %s, got %s and %s"
+                                   % ((B, K) + vol, tuple(vol_refs.shape), tuple(vol_query.shape)))
+        elif tuple(vol_refs.shape) != (B, V) + vol or tuple(vol_query.shape) not in ((B,) + vol, (B, V) + vol):
+            raise RuntimeError("vol_refs must be (B,V,16,8,8,8) = %s and vol_query that or (B,16,8,8,8), got %s and %s"
+                               % ((B, V) + vol, tuple(vol_refs.shape), tuple(vol_query.shape)))
+        if staged:
+            return self._advance((vol_refs, vol_query), lambda: self.buffers, self._run, lambda p: (p, True))
+        return self._advance((vol_refs, vol_query), lambda: self._view_statics(vol_refs, vol_query), self._run_views,
+                             lambda p: (p, False))
+
+    def _view_statics(self, vol_refs, vol_query):
+        """The static ``(B,V,...)`` inputs of the captured step that selects and gathers, in the shapes given."""
+        if self._full is None or self._full[1].shape != vol_query.shape:
+            self._full = (torch.empty_like(vol_refs, memory_format=torch.contiguous_format),
+                          torch.empty_like(vol_query, memory_format=torch.contiguous_format))
+            self._graphs = {k: g for k, g in self._graphs.items() if k[1]}   # (graphs of the old inputs' shape)
+        return self._full
+
+    def _advance(self, vols, static, run, key) -> TrackStep:
+        """One step through ``run(vol_a, vol_b, p)``: eagerly on ``vols`` (``static()`` when none are given), or -- ``use_graph``,
+        past the first step -- captured once per ``key(p)`` on the inputs ``static()`` and replayed; then the ping-pong moves."""
         n = self._n + 1
         p = n & 1
         if not self.use_graph or n == 1:
-            if vol_src is None:
-                vol_src, vol_tgt = self.buffers
-            out = self._run(vol_src, vol_tgt, p)
+            out = run(*(vols if vols[0] is not None else static()), p)
         else:
-            static = self.buffers
-            if vol_src is not None and vol_src.data_ptr() != static[0].data_ptr():
-                static[0].copy_(vol_src)
-            if vol_tgt is not None and vol_tgt.data_ptr() != static[1].data_ptr():
-                static[1].copy_(vol_tgt)
-            if p not in self._graphs:
+            st = static()
+            for dst, src in zip(st, vols):
+                if src is not None and src.data_ptr() != dst.data_ptr():
+                    dst.copy_(src)
+            k = key(p)
+            if k not in self._graphs:
                 # No warm-up run: the eager first step has issued every launch of the chain once, and a warm-up here would
                 # move the filter (the counter, the sets).  Capture records the step; the replay below runs it.
                 torch.cuda.synchronize()
                 graph = torch.cuda.CUDAGraph()
                 with torch.cuda.graph(graph):
-                    captured = self._run(static[0], static[1], p)
-                self._graphs[p] = (graph, captured)
-            graph, out = self._graphs[p]
+                    captured = run(st[0], st[1], p)
+                self._graphs[k] = (graph, captured)
+            graph, out = self._graphs[k]
             graph.replay()
         self._cur, self._n = (self._R[p], self._scores[p], self._keys[p]), n
         self._anchor = self._sel[p][2]
+        self._selected = False
         if self._V is not None:
             self._vel = self._V[p]
         return out
+
+    @torch.no_grad()
+    def step(self, vol_src: Optional[torch.Tensor] = None, vol_tgt: Optional[torch.Tensor] = None, staged: bool = False) -> TrackStep:
+        """Advance the filter by one frame.  Called with no volumes it runs on ``self.buffers`` as they are.  With ``views``:
+        ``(B,V,...)`` inputs are selected from and gathered; ``staged=True`` (or no volumes) runs on the K staged views."""
+        if self._cur is None:
+            raise RuntimeError("call init(vol_src, vol_tgt, R_init) before the first step")
+        if (vol_src is None) != (vol_tgt is None):
+            raise RuntimeError("pass both volumes or neither")
+        if self.views is not None:
+            return self._step_views(vol_src, vol_tgt, staged)
+        if staged:
+            raise RuntimeError("staged=True belongs to a tracker built with views=")
+        return self._advance((vol_src, vol_tgt), lambda: self.buffers, self._run, lambda p: p)
