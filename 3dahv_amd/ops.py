@@ -1258,98 +1258,9 @@ def track_advance(step: torch.Tensor, seed: int, batch: int, u: torch.Tensor | N
     return u
 
 
-@torch.no_grad()
-def diffuse_rotations(R: torch.Tensor, idx: torch.Tensor | None = None, m: int | None = None, sigma_deg: float = 3.0,
-                      step: torch.Tensor | None = None, seed: int = 0, best_key: torch.Tensor | None = None, n_fresh: int = 0,
-                      max_angle_deg: float | None = None, out: torch.Tensor | None = None, want_omega: bool = False,
-                      omega_out: torch.Tensor | None = None):
-    """Predict step of a particle filter (``ahv_diffuse_rotations_f32``, one launch): the next particle set ``(B,M,3,3)`` from
-    ``R (N,3,3)`` / ``(B,N,3,3)``.  Slot j of sample b is ``R[idx[b,j]] exp([w]x)`` with ``w = sigma z`` fresh Gaussian noise
-    (``idx (B,M)`` int64 from ``resample``; None: ``j mod N`` with ``m`` slots, default N), composed as unit quaternions and
-    normalised.  ``best_key (B,)`` given: slot 0 is the elite, ``R[decode(key)]`` bit for bit.  The last ``n_fresh`` slots are
-    fresh Haar rotations: ``random_rotations`` at seed ``seed ^ 0x9E3779B97F4A7C15`` and offset ``(step B + b) M + j``.
-    ``step``: the int64 device counter ``track_advance`` moves (read on the device: a replayed graph draws new noise); the noise
-    of a slot is a function of ``(seed, step, b, j)`` alone.  ``max_angle_deg``: ``|w|`` is clipped to it (None: no limit).
-    B comes from ``idx``, a per-sample ``R`` or ``best_key``, else 1.  ``want_omega``: also return ``w (B,M,3)`` as applied
-    (zeros in elite and fresh slots), into ``omega_out`` (float32 ``(B,M,3)``) when one is given.  ``out`` and ``omega_out``
-    must not overlap ``R``: a slot reads any row of it.  Returns ``out`` or ``(out, omega)``."""
-    _need_gpu(R)
-    dev = R.device
-    if step is None:
-        raise RuntimeError("step is required: an int64 tensor of ONE element on the device")
-    step = _step_counter(step, dev)
-    if idx is not None:
-        if not isinstance(idx, torch.Tensor) or idx.dim() != 2 or idx.dtype != torch.int64 or not idx.is_contiguous():
-            raise RuntimeError("idx must be a contiguous (B,M) int64 tensor")
-        if idx.device != dev:
-            raise RuntimeError("Expected all tensors to be on the same device, found %s and %s" % (dev, idx.device))
-        B = idx.shape[0]
-        if m is not None and int(m) != idx.shape[1]:
-            raise RuntimeError("m = %d disagrees with idx %s" % (int(m), tuple(idx.shape)))
-        M = idx.shape[1]
-    else:
-        B = R.shape[0] if R.dim() == 4 else (best_key.numel() if best_key is not None else 1)
-        M = None
-    N, rstride = _rot_layout(R, B)
-    if N < 1:
-        raise RuntimeError("R holds no rotation (N = 0)")
-    M = _draws((N if m is None else m) if M is None else M)
-    if not 1 <= B <= 65535:
-        raise RuntimeError("B = %d outside 1..65535" % B)
-    n_fresh = int(n_fresh)
-    if not 0 <= n_fresh <= M:
-        raise RuntimeError("n_fresh = %d outside 0..M = %d" % (n_fresh, M))
-    sigma = _angle_rad(sigma_deg, "sigma_deg")
-    max_angle = _angle_rad(max_angle_deg, "max_angle_deg", allow_none=True)
-    if best_key is not None and (not isinstance(best_key, torch.Tensor) or best_key.dtype != torch.int64
-                                 or best_key.numel() != B or best_key.device != dev or not best_key.is_contiguous()):
-        raise RuntimeError("best_key must be a contiguous int64 tensor of B = %d elements on %s" % (B, dev))
-    if out is None:
-        out = torch.empty((B, M, 3, 3), dtype=torch.float32, device=dev)
-    elif tuple(out.shape) != (B, M, 3, 3) or not out.is_contiguous() or out.dtype != torch.float32 or out.device != dev:
-        raise RuntimeError("out must be a contiguous float32 (B, M, 3, 3) = %s tensor on %s" % ((B, M, 3, 3), dev))
-    omega = omega_out
-    if omega is not None:
-        if (not isinstance(omega, torch.Tensor) or tuple(omega.shape) != (B, M, 3) or not omega.is_contiguous()
-                or omega.dtype != torch.float32 or omega.device != dev):
-            raise RuntimeError("omega_out must be a contiguous float32 (B, M, 3) = %s tensor on %s" % ((B, M, 3), dev))
-    elif want_omega:
-        omega = torch.empty((B, M, 3), dtype=torch.float32, device=dev)
-    Rc = R.detach().contiguous()
-    r_lo, r_hi = Rc.data_ptr(), Rc.data_ptr() + 4 * Rc.numel()
-    for name, t in (("out", out), ("omega_out", omega)):
-        if t is not None and t.data_ptr() < r_hi and r_lo < t.data_ptr() + 4 * t.numel():
-            raise RuntimeError("%s must not overlap R (a slot reads any row of R)" % name)
-    _call(dev, "ahv_diffuse_rotations_f32", idx.data_ptr() if idx is not None else None, Rc.data_ptr(), rstride, N,
-          best_key.data_ptr() if best_key is not None else None, M, n_fresh, B, int(seed) & (2**64 - 1), step.data_ptr(), sigma,
-          max_angle, out.data_ptr(), omega.data_ptr() if omega is not None else None)
-    return (out, omega) if omega is not None else out
-
-
-def _unit_interval(x, what: str) -> float:
-    d = float(x)
-    if not 0.0 <= d <= 1.0:      # (false for NaN)
-        raise RuntimeError("%s = %r must lie in [0, 1]" % (what, x))
-    return d
-
-
-@torch.no_grad()
-def predict_rotations(R: torch.Tensor, V: torch.Tensor | None = None, idx: torch.Tensor | None = None, m: int | None = None,
-                      sigma_deg: float = 3.0, sigma_vel_deg: float = 1.0, damping: float = 1.0, step: torch.Tensor | None = None,
-                      seed: int = 0, best_key: torch.Tensor | None = None, coast: bool = True, n_fresh: int = 0,
-                      max_angle_deg: float | None = None, max_speed_deg: float | None = None, out: torch.Tensor | None = None,
-                      vel_out: torch.Tensor | None = None, want_omega: bool = False, omega_out: torch.Tensor | None = None):
-    """Predict step with a constant-velocity motion model (``ahv_predict_rotations_f32``, one launch).  A particle is ``(R, v)``,
-    ``v`` its body-frame rotation vector per frame: ``V (N,3)`` / ``(B,N,3)`` float32, or None for all zeros (a freshly scored
-    set).  Slot j of sample b, with ``i = idx[b,j]``: ``v' = damping v_i + sigma_vel y`` (``|v'|`` clipped to ``max_speed_deg``),
-    ``R_out = R_i exp([v' + w]x)`` with ``w = sigma z`` the noise ``diffuse_rotations`` draws for the same ``(seed, step, b, j)``
-    (clipped to ``max_angle_deg``) and ``y`` a second, independent draw; composed as unit quaternions and normalised.
-    ``best_key (B,)`` given: slot 0 is the elite, ``R`` and ``v`` of row ``decode(key)`` bit for bit, and with ``coast`` slot 1 is
-    that row moved by its own velocity with no noise, ``R_n exp([v_n]x)``.  The last ``n_fresh`` slots are the Haar rotations
-    ``diffuse_rotations`` writes there, with zero velocity.  Other arguments as ``diffuse_rotations``; B comes from ``idx``, a
-    per-sample ``R`` or ``V``, or ``best_key``, else 1.  ``out`` / ``omega_out`` must not overlap ``R`` and ``vel_out`` must not
-    overlap ``V``.  Returns ``(R_out (B,M,3,3), V_out (B,M,3))``, with ``want_omega`` / ``omega_out`` also the total rotation
-    vector applied ``(B,M,3)`` (``v' + w``; ``v_n`` in the coast slot, zeros in elite and fresh slots)."""
+def _predict_args(R, idx, m, step, best_key, n_fresh, V=None):
+    """What ``diffuse_rotations`` and ``predict_rotations`` (which alone has ``V``) resolve alike, after checking ``step``, ``V``,
+    ``idx`` and ``n_fresh`` against ``R``: ``(dev, step, B, M, N, rstride, vstride, n_fresh)``."""
     _need_gpu(R)
     dev = R.device
     if step is None:
@@ -1387,37 +1298,104 @@ def predict_rotations(R: torch.Tensor, V: torch.Tensor | None = None, idx: torch
     n_fresh = int(n_fresh)
     if not 0 <= n_fresh <= M:
         raise RuntimeError("n_fresh = %d outside 0..M = %d" % (n_fresh, M))
-    sigma = _angle_rad(sigma_deg, "sigma_deg")
-    sigma_vel = _angle_rad(sigma_vel_deg, "sigma_vel_deg")
-    damping = _unit_interval(damping, "damping")
-    max_angle = _angle_rad(max_angle_deg, "max_angle_deg", allow_none=True)
-    max_speed = _angle_rad(max_speed_deg, "max_speed_deg", allow_none=True)
+    return dev, step, B, M, N, rstride, vstride, n_fresh
+
+
+def _check_best_key(best_key, B: int, dev) -> None:
+    """After the angle checks of the two predict ops, where it has always been: the first error raised stays the same."""
     if best_key is not None and (not isinstance(best_key, torch.Tensor) or best_key.dtype != torch.int64
                                  or best_key.numel() != B or best_key.device != dev or not best_key.is_contiguous()):
         raise RuntimeError("best_key must be a contiguous int64 tensor of B = %d elements on %s" % (B, dev))
 
-    def _output(t, name, shape, wanted=True):
-        if t is None:
-            return torch.empty(shape, dtype=torch.float32, device=dev) if wanted else None
-        if (not isinstance(t, torch.Tensor) or tuple(t.shape) != shape or not t.is_contiguous() or t.dtype != torch.float32
-                or t.device != dev):
-            raise RuntimeError("%s must be a contiguous float32 %s = %s tensor on %s"
-                               % (name, "(B, M, 3, 3)" if len(shape) == 4 else "(B, M, 3)", shape, dev))
-        return t
 
-    out = _output(out, "out", (B, M, 3, 3))
-    vel_out = _output(vel_out, "vel_out", (B, M, 3))
-    omega = _output(omega_out, "omega_out", (B, M, 3), wanted=want_omega)
-    Rc = R.detach().contiguous()
-    Vc = V.detach().contiguous() if V is not None else None
-    outputs = (("out", out), ("vel_out", vel_out), ("omega_out", omega))
-    for src, what in ((Rc, "R"), (Vc, "V")):
+def _output(t, name, shape, dev, wanted=True):
+    """The float32 output ``name`` of a predict step: ``t`` checked, or a new tensor when ``t`` is None and one is ``wanted``."""
+    if t is None:
+        return torch.empty(shape, dtype=torch.float32, device=dev) if wanted else None
+    if (not isinstance(t, torch.Tensor) or tuple(t.shape) != shape or not t.is_contiguous() or t.dtype != torch.float32
+            or t.device != dev):
+        raise RuntimeError("%s must be a contiguous float32 %s = %s tensor on %s"
+                           % (name, "(B, M, 3, 3)" if len(shape) == 4 else "(B, M, 3)", shape, dev))
+    return t
+
+
+def _refuse_overlap(sources, outputs) -> None:
+    """A slot reads any row of a source, so no output may share memory with one.  ``sources``: (tensor or None, name) pairs."""
+    for src, what in sources:
         if src is None:
             continue
         lo, hi = src.data_ptr(), src.data_ptr() + 4 * src.numel()
         for name, t in outputs:
             if t is not None and t.data_ptr() < hi and lo < t.data_ptr() + 4 * t.numel():
                 raise RuntimeError("%s must not overlap %s (a slot reads any row of %s)" % (name, what, what))
+
+
+@torch.no_grad()
+def diffuse_rotations(R: torch.Tensor, idx: torch.Tensor | None = None, m: int | None = None, sigma_deg: float = 3.0,
+                      step: torch.Tensor | None = None, seed: int = 0, best_key: torch.Tensor | None = None, n_fresh: int = 0,
+                      max_angle_deg: float | None = None, out: torch.Tensor | None = None, want_omega: bool = False,
+                      omega_out: torch.Tensor | None = None):
+    """Predict step of a particle filter (``ahv_diffuse_rotations_f32``, one launch): the next particle set ``(B,M,3,3)`` from
+    ``R (N,3,3)`` / ``(B,N,3,3)``.  Slot j of sample b is ``R[idx[b,j]] exp([w]x)`` with ``w = sigma z`` fresh Gaussian noise
+    (``idx (B,M)`` int64 from ``resample``; None: ``j mod N`` with ``m`` slots, default N), composed as unit quaternions and
+    normalised.  ``best_key (B,)`` given: slot 0 is the elite, ``R[decode(key)]`` bit for bit.  The last ``n_fresh`` slots are
+    fresh Haar rotations: ``random_rotations`` at seed ``seed ^ 0x9E3779B97F4A7C15`` and offset ``(step B + b) M + j``.
+    ``step``: the int64 device counter ``track_advance`` moves (read on the device: a replayed graph draws new noise); the noise
+    of a slot is a function of ``(seed, step, b, j)`` alone.  ``max_angle_deg``: ``|w|`` is clipped to it (None: no limit).
+    B comes from ``idx``, a per-sample ``R`` or ``best_key``, else 1.  ``want_omega``: also return ``w (B,M,3)`` as applied
+    (zeros in elite and fresh slots), into ``omega_out`` (float32 ``(B,M,3)``) when one is given.  ``out`` and ``omega_out``
+    must not overlap ``R``: a slot reads any row of it.  Returns ``out`` or ``(out, omega)``."""
+    dev, step, B, M, N, rstride, _, n_fresh = _predict_args(R, idx, m, step, best_key, n_fresh)
+    sigma = _angle_rad(sigma_deg, "sigma_deg")
+    max_angle = _angle_rad(max_angle_deg, "max_angle_deg", allow_none=True)
+    _check_best_key(best_key, B, dev)
+    out = _output(out, "out", (B, M, 3, 3), dev)
+    omega = _output(omega_out, "omega_out", (B, M, 3), dev, wanted=want_omega)
+    Rc = R.detach().contiguous()
+    _refuse_overlap(((Rc, "R"),), (("out", out), ("omega_out", omega)))
+    _call(dev, "ahv_diffuse_rotations_f32", idx.data_ptr() if idx is not None else None, Rc.data_ptr(), rstride, N,
+          best_key.data_ptr() if best_key is not None else None, M, n_fresh, B, int(seed) & (2**64 - 1), step.data_ptr(), sigma,
+          max_angle, out.data_ptr(), omega.data_ptr() if omega is not None else None)
+    return (out, omega) if omega is not None else out
+
+
+def _unit_interval(x, what: str) -> float:
+    d = float(x)
+    if not 0.0 <= d <= 1.0:      # (false for NaN)
+        raise RuntimeError("%s = %r must lie in [0, 1]" % (what, x))
+    return d
+
+
+@torch.no_grad()
+def predict_rotations(R: torch.Tensor, V: torch.Tensor | None = None, idx: torch.Tensor | None = None, m: int | None = None,
+                      sigma_deg: float = 3.0, sigma_vel_deg: float = 1.0, damping: float = 1.0, step: torch.Tensor | None = None,
+                      seed: int = 0, best_key: torch.Tensor | None = None, coast: bool = True, n_fresh: int = 0,
+                      max_angle_deg: float | None = None, max_speed_deg: float | None = None, out: torch.Tensor | None = None,
+                      vel_out: torch.Tensor | None = None, want_omega: bool = False, omega_out: torch.Tensor | None = None):
+    """Predict step with a constant-velocity motion model (``ahv_predict_rotations_f32``, one launch).  A particle is ``(R, v)``,
+    ``v`` its body-frame rotation vector per frame: ``V (N,3)`` / ``(B,N,3)`` float32, or None for all zeros (a freshly scored
+    set).  Slot j of sample b, with ``i = idx[b,j]``: ``v' = damping v_i + sigma_vel y`` (``|v'|`` clipped to ``max_speed_deg``),
+    ``R_out = R_i exp([v' + w]x)`` with ``w = sigma z`` the noise ``diffuse_rotations`` draws for the same ``(seed, step, b, j)``
+    (clipped to ``max_angle_deg``) and ``y`` a second, independent draw; composed as unit quaternions and normalised.
+    ``best_key (B,)`` given: slot 0 is the elite, ``R`` and ``v`` of row ``decode(key)`` bit for bit, and with ``coast`` slot 1 is
+    that row moved by its own velocity with no noise, ``R_n exp([v_n]x)``.  The last ``n_fresh`` slots are the Haar rotations
+    ``diffuse_rotations`` writes there, with zero velocity.  Other arguments as ``diffuse_rotations``; B comes from ``idx``, a
+    per-sample ``R`` or ``V``, or ``best_key``, else 1.  ``out`` / ``omega_out`` must not overlap ``R`` and ``vel_out`` must not
+    overlap ``V``.  Returns ``(R_out (B,M,3,3), V_out (B,M,3))``, with ``want_omega`` / ``omega_out`` also the total rotation
+    vector applied ``(B,M,3)`` (``v' + w``; ``v_n`` in the coast slot, zeros in elite and fresh slots)."""
+    dev, step, B, M, N, rstride, vstride, n_fresh = _predict_args(R, idx, m, step, best_key, n_fresh, V)
+    sigma = _angle_rad(sigma_deg, "sigma_deg")
+    sigma_vel = _angle_rad(sigma_vel_deg, "sigma_vel_deg")
+    damping = _unit_interval(damping, "damping")
+    max_angle = _angle_rad(max_angle_deg, "max_angle_deg", allow_none=True)
+    max_speed = _angle_rad(max_speed_deg, "max_speed_deg", allow_none=True)
+    _check_best_key(best_key, B, dev)
+    out = _output(out, "out", (B, M, 3, 3), dev)
+    vel_out = _output(vel_out, "vel_out", (B, M, 3), dev)
+    omega = _output(omega_out, "omega_out", (B, M, 3), dev, wanted=want_omega)
+    Rc = R.detach().contiguous()
+    Vc = V.detach().contiguous() if V is not None else None
+    _refuse_overlap(((Rc, "R"), (Vc, "V")), (("out", out), ("vel_out", vel_out), ("omega_out", omega)))
     _call(dev, "ahv_predict_rotations_f32", idx.data_ptr() if idx is not None else None, Rc.data_ptr(), rstride,
           Vc.data_ptr() if Vc is not None else None, vstride, N, best_key.data_ptr() if best_key is not None else None, M,
           n_fresh, B, int(seed) & (2**64 - 1), step.data_ptr(), sigma, sigma_vel, damping, max_angle, max_speed,
@@ -1498,10 +1476,7 @@ def smooth_step(history: SmoothHistory, R: torch.Tensor, scores: torch.Tensor, s
         if tuple(V.shape) != (B, M, 3):
             raise RuntimeError("V must be (B,M,3) = %s, got %s" % ((B, M, 3), tuple(V.shape)))
     beta = inverse_temperature(temperature)
-    sigma = _angle_rad(sigma_deg, "sigma_deg")
-    if not (sigma > 0.0 and 1.0 / (4.0 * sigma * sigma) < 3.0e38):
-        raise RuntimeError("sigma_deg = %r must be > 0 (and 1 / (4 sigma^2) must fit a float32)" % (sigma_deg,))
-    jump = _jump(jump)
+    sigma, jump = _transition_scale(sigma_deg, jump)
     damping = _unit_interval(damping, "damping")
     Rc, sc = R.detach().contiguous(), scores.detach().contiguous()
     Vc = V.detach().contiguous() if V is not None else None

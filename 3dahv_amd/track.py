@@ -368,6 +368,17 @@ class PoseTracker:
                                 jump=self.smooth_jump, first_step=1)
         return TrackStep(score, idx, R_map, R, scores, draws, *post, reacq)
 
+    def _frames(self, frames: Optional[int], what: str) -> int:
+        """F of a smoothing query: ``min(frames, steps since init, history)``, ``frames`` None standing for no limit."""
+        if self._n < 1:
+            raise RuntimeError("%s before the first step: nothing has been recorded since init" % what)
+        F = min(self._n, self.history)
+        if frames is not None:
+            if int(frames) < 1:
+                raise RuntimeError("frames = %d must be at least 1" % int(frames))
+            F = min(F, int(frames))
+        return F
+
     @torch.no_grad()
     def smoothed(self, frames: Optional[int] = None, out=None):
         """The MAP trajectory over the last ``min(frames, steps since init, history)`` frames (``frames`` None: as many as there
@@ -375,14 +386,7 @@ class PoseTracker:
         no host synchronisation; ``out``: a ``SmoothedPath`` of that size to write into."""
         if self._hist is None:
             raise RuntimeError("smoothed() needs a tracker built with history >= 2")
-        if self._n < 1:
-            raise RuntimeError("smoothed() before the first step: nothing has been recorded since init")
-        F = min(self._n, self.history)
-        if frames is not None:
-            if int(frames) < 1:
-                raise RuntimeError("frames = %d must be at least 1" % int(frames))
-            F = min(F, int(frames))
-        return self.ops.smooth_backtrace(self._hist, self._step, frames=F, first_step=1, out=out)
+        return self.ops.smooth_backtrace(self._hist, self._step, frames=self._frames(frames, "smoothed()"), first_step=1, out=out)
 
     @torch.no_grad()
     def smoothed_marginals(self, frames: Optional[int] = None, out=None, posterior: bool = False):
@@ -397,13 +401,7 @@ class PoseTracker:
         the most probable particle and the entropy in nats.  The query gathers the frames from the ring and allocates."""
         if self._marg is None:
             raise RuntimeError("smoothed_marginals() needs a tracker built with history >= 2 and marginals=True")
-        if self._n < 1:
-            raise RuntimeError("smoothed_marginals() before the first step: nothing has been recorded since init")
-        F = min(self._n, self.history)
-        if frames is not None:
-            if int(frames) < 1:
-                raise RuntimeError("frames = %d must be at least 1" % int(frames))
-            F = min(F, int(frames))
+        F = self._frames(frames, "smoothed_marginals()")
         if posterior:
             ops.min_trace(self.mode_angle_deg)        # raises outside (0, 180), before any launch
         res = self.ops.marginal_smooth(self._hist, self._marg, self._step, self.smooth_sigma_deg, jump=self.smooth_jump, frames=F,
