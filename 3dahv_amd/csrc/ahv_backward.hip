@@ -25,6 +25,7 @@
 #include "ahv_device.h"
 #define AHV_FP32_LOW_HALF  // these kernels leave registers free on their SIMDs: see low_half (ahv_dual.h)
 #include "ahv_dual.h"
+#include "ahv_trilinear.h"
 
 namespace ahv {
 
@@ -1269,26 +1270,6 @@ hipError_t launch_score_backward(const float* vol_src, const float* feat_tgt, co
 // ---------------------------------------------------------------------------------------------------
 constexpr int kRotGradThreads = 256;
 
-struct RgAxis {
-    float w0, w1;   // value weights of rows j, j + 1 (0 where the row is outside the volume)
-    float d0, d1;   // their derivatives w.r.t. the sample coordinate (-1 / +1, 0 where outside)
-    int o0, o1;     // clamped row index * stride (floats)
-};
-
-__device__ __forceinline__ void rg_axis(float i, int stride, RgAxis& a)
-{
-    i = fminf(fmaxf(i, -2.0f), 9.0f);   // keeps the conversion defined for any R; all corners are outside there anyway
-    const float fl = floorf(i), t = i - fl;
-    const int i0 = (int)fl, i1 = i0 + 1;
-    const bool in0 = (unsigned)i0 < 8u, in1 = (unsigned)i1 < 8u;
-    a.w0 = in0 ? 1.0f - t : 0.0f;
-    a.w1 = in1 ? t : 0.0f;
-    a.d0 = in0 ? -1.0f : 0.0f;
-    a.d1 = in1 ? 1.0f : 0.0f;
-    a.o0 = min(max(i0, 0), 7) * stride;
-    a.o1 = min(max(i1, 0), 7) * stride;
-}
-
 // the lane's four voxels of half volume H: plane al = 0..3 (depth 2 H + (al & 1) + 4 (al >> 1)), y = lane >> 3, x = lane & 7
 template <int H>
 __device__ __forceinline__ void rg_gather_half(float (&sum)[9], const float* xbuf, const float* src_ch, const float* Rm, int lane)
@@ -1300,27 +1281,7 @@ __device__ __forceinline__ void rg_gather_half(float (&sum)[9], const float* xbu
         const float z4 = (float)(2 * H + (al & 1) + 4 * (al >> 1)) - 3.5f;
         const float* xp = xbuf + al * kXPlane + yb * kXRow + xe * 4;   // 8-byte aligned
         const f32x2 dlo = *reinterpret_cast<const f32x2*>(xp), dhi = *reinterpret_cast<const f32x2*>(xp + 2);
-        RgAxis ax, ay, az;
-        rg_axis(fmaf(Rm[0], x4, fmaf(Rm[1], y4, fmaf(Rm[2], z4, 3.5f))), kSrcStride, ax);
-        rg_axis(fmaf(Rm[3], x4, fmaf(Rm[4], y4, fmaf(Rm[5], z4, 3.5f))), kSrcRowsY * kSrcStride, ay);
-        rg_axis(fmaf(Rm[6], x4, fmaf(Rm[7], y4, fmaf(Rm[8], z4, 3.5f))), kSrcPlaneRows * kSrcStride, az);
-        float tx = 0.0f, ty = 0.0f, tz = 0.0f;
-#pragma unroll
-        for (int c = 0; c < 8; ++c) {   // corner (dz, dy, dx) = bits (4, 2, 1)
-            const float wx = (c & 1) ? ax.w1 : ax.w0, gx = (c & 1) ? ax.d1 : ax.d0;
-            const float wy = (c & 2) ? ay.w1 : ay.w0, gy = (c & 2) ? ay.d1 : ay.d0;
-            const float wz = (c & 4) ? az.w1 : az.w0, gz = (c & 4) ? az.d1 : az.d0;
-            const int off = ((c & 1) ? ax.o1 : ax.o0) + ((c & 2) ? ay.o1 : ay.o0) + ((c & 4) ? az.o1 : az.o0);
-            const f32x4 v = *reinterpret_cast<const f32x4*>(src_ch + off);
-            float s = fmaf(dhi[1], v[3], fmaf(dhi[0], v[2], fmaf(dlo[1], v[1], dlo[0] * v[0])));
-            s = (gx != 0.0f && gy != 0.0f && gz != 0.0f) ? s : 0.0f;   // outside: the clamped row is not this corner's
-            tx = fmaf(s, gx * (wy * wz), tx);
-            ty = fmaf(s, gy * (wx * wz), ty);
-            tz = fmaf(s, gz * (wx * wy), tz);
-        }
-        sum[0] = fmaf(tx, x4, sum[0]); sum[1] = fmaf(tx, y4, sum[1]); sum[2] = fmaf(tx, z4, sum[2]);
-        sum[3] = fmaf(ty, x4, sum[3]); sum[4] = fmaf(ty, y4, sum[4]); sum[5] = fmaf(ty, z4, sum[5]);
-        sum[6] = fmaf(tz, x4, sum[6]); sum[7] = fmaf(tz, y4, sum[7]); sum[8] = fmaf(tz, z4, sum[8]);
+        rot_grad_voxel(sum, dlo[0], dlo[1], dhi[0], dhi[1], src_ch, Rm, x4, y4, z4);
     }
 }
 
@@ -1364,27 +1325,14 @@ __global__ __launch_bounds__(kRotGradThreads) void score_rotation_grad_kernel(
         __syncthreads();
         if (tid == 0) lds_bad[1] = 0u;
         __syncthreads();
-        {
-            bool bad = false;
-            const float* vol = vol_src + (long)b * (16 * 512);
-            for (int i = tid; i < 16 * 512; i += kRotGradThreads) {
-                const int c = i >> 9, v = i & 511;
-                const float x = vol[i];
-                bad = bad || __builtin_amdgcn_classf(x, 0x207);   // sNaN | qNaN | -inf | +inf
-                lds_src[((v >> 6) * kSrcPlaneRows + ((v >> 3) & 7) * kSrcRowsY + (v & 7)) * kSrcStride + c] = x;
-            }
-            if (bad) lds_bad[1] = 1u;
-        }
+        if (stage_src_volume_scan(lds_src, vol_src + (long)b * (16 * 512), tid, kRotGradThreads)) lds_bad[1] = 1u;
         __syncthreads();
         const bool poisoned = (lds_bad[0] | lds_bad[1]) != 0u;
         const float* Rb = R + (long)b * r_batch_stride;
         for (long h = blockIdx.x; h < N; h += gridDim.x) {
             float Rm[9];
-#pragma unroll
-            for (int i = 0; i < 9; ++i) Rm[i] = Rb[h * 9 + i];
-            bool bad_r = false;   // a NaN / inf entry of R: autograd's gradient is NaN, the clamp in rg_axis would hide it
-#pragma unroll
-            for (int i = 0; i < 9; ++i) bad_r = bad_r || __builtin_amdgcn_classf(Rm[i], 0x207);
+            bool bad_r;
+            load_rotation(Rm, bad_r, Rb + h * 9);
             DuRegs du;
             load_du_regs(du, du_ws + ((long)b * N + h) * 2048, lane);
             float sum[9];
@@ -1398,25 +1346,7 @@ __global__ __launch_bounds__(kRotGradThreads) void score_rotation_grad_kernel(
             wave_lds_fence();
             rg_gather_half<1>(sum, xbuf, src_ch, Rm, lane);
             wave_lds_fence();
-#pragma unroll
-            for (int i = 0; i < 9; ++i) {
-                float x = sum[i];
-#pragma unroll
-                for (int s = 32; s >= 1; s >>= 1) x += __shfl_xor(x, s, 64);
-                sum[i] = x;
-            }
-            if (lane < 9) {
-                float x = sum[0];
-#pragma unroll
-                for (int i = 1; i < 9; ++i) x = lane == i ? sum[i] : x;
-                lds_red[m * 12 + lane] = x;
-            }
-            __syncthreads();
-            if (tid < 9) {
-                const float x = (lds_red[tid] + lds_red[12 + tid]) + (lds_red[24 + tid] + lds_red[36 + tid]);
-                grad_R[((long)b * N + h) * 9 + tid] = (poisoned || bad_r) ? __builtin_nanf("") : x;
-            }
-            __syncthreads();
+            reduce_store_nine(sum, lds_red, tid, poisoned || bad_r, grad_R + ((long)b * N + h) * 9);
         }
     }
 }
@@ -1452,9 +1382,9 @@ hipError_t launch_score_rotation_grad(const float* vol_src, const float* feat_tg
 // gradient READ instead of formed.  There dX = W1^T du comes out of MFMAs; here it is grad_out[n], the 32 KiB the op-level
 // caller holds in HBM, and nothing else changes:
 //   grad_R[n][a][b] = sum_p ( sum_c grad_out[n][c][p] * d out[n][c][p] / d i_a ) * (S_a / 2) * p_b
-// with p = (x_w, y_h, z_d) the voxel centres, i_a = ((R_n p)_a + 1) S_a / 2 - 1/2, S = (W, H, D), and the conventions stated
-// above score_rotation_grad_kernel (floor(i) is the cell, an outside corner contributes nothing, the coordinate is clamped
-// before the conversion).
+// with p = (x_w, y_h, z_d) the voxel centres, i_a = ((R_n p)_a + 1) S_a / 2 - 1/2, S = (W, H, D), and the conventions of
+// ahv_trilinear.h (floor(i) is the cell, an outside corner contributes nothing, the coordinate is clamped before the
+// conversion).  The forward and the volume adjoint are ahv_rotate.hip.
 // (16, 8, 8, 8): the same team -- one workgroup of four waves per hypothesis, wave m = channels 4 m .. 4 m + 3, the source
 // channel-last in LDS, staged once per workgroup when the volume is shared (vol_batch_stride = 0) and once per hypothesis
 // otherwise.  A lane owns the voxels (d, y = lane >> 3, x = lane & 7), d = 0 .. 7: its 32 words of grad_out are 32 loads of
@@ -1467,59 +1397,6 @@ hipError_t launch_score_rotation_grad(const float* vol_src, const float* feat_tg
 // upstream gradients are not looked for: they propagate through the in-range corners by IEEE arithmetic.
 // ---------------------------------------------------------------------------------------------------
 constexpr int kRvgThreads = 256;
-
-// plane z of the lane (y = lane >> 3, x = lane & 7): rg_gather_half's voxel body with dX of the wave's four channels in registers
-__device__ __forceinline__ void rvg_gather_plane(float (&sum)[9], float g0, float g1, float g2, float g3, const float* src_ch,
-                                                 const float* Rm, int lane, int z)
-{
-    const float x4 = (float)(lane & 7) - 3.5f, y4 = (float)(lane >> 3) - 3.5f, z4 = (float)z - 3.5f;   // 4 * voxel centre
-    RgAxis ax, ay, az;
-    rg_axis(fmaf(Rm[0], x4, fmaf(Rm[1], y4, fmaf(Rm[2], z4, 3.5f))), kSrcStride, ax);
-    rg_axis(fmaf(Rm[3], x4, fmaf(Rm[4], y4, fmaf(Rm[5], z4, 3.5f))), kSrcRowsY * kSrcStride, ay);
-    rg_axis(fmaf(Rm[6], x4, fmaf(Rm[7], y4, fmaf(Rm[8], z4, 3.5f))), kSrcPlaneRows * kSrcStride, az);
-    float tx = 0.0f, ty = 0.0f, tz = 0.0f;
-#pragma unroll
-    for (int c = 0; c < 8; ++c) {   // corner (dz, dy, dx) = bits (4, 2, 1)
-        const float wx = (c & 1) ? ax.w1 : ax.w0, gx = (c & 1) ? ax.d1 : ax.d0;
-        const float wy = (c & 2) ? ay.w1 : ay.w0, gy = (c & 2) ? ay.d1 : ay.d0;
-        const float wz = (c & 4) ? az.w1 : az.w0, gz = (c & 4) ? az.d1 : az.d0;
-        const int off = ((c & 1) ? ax.o1 : ax.o0) + ((c & 2) ? ay.o1 : ay.o0) + ((c & 4) ? az.o1 : az.o0);
-        const f32x4 v = *reinterpret_cast<const f32x4*>(src_ch + off);
-        float s = fmaf(g3, v[3], fmaf(g2, v[2], fmaf(g1, v[1], g0 * v[0])));
-        s = (gx != 0.0f && gy != 0.0f && gz != 0.0f) ? s : 0.0f;   // outside: the clamped row is not this corner's
-        tx = fmaf(s, gx * (wy * wz), tx);
-        ty = fmaf(s, gy * (wx * wz), ty);
-        tz = fmaf(s, gz * (wx * wy), tz);
-    }
-    sum[0] = fmaf(tx, x4, sum[0]); sum[1] = fmaf(tx, y4, sum[1]); sum[2] = fmaf(tx, z4, sum[2]);   // S_a / 2 * p_b = 4 p_b
-    sum[3] = fmaf(ty, x4, sum[3]); sum[4] = fmaf(ty, y4, sum[4]); sum[5] = fmaf(ty, z4, sum[5]);
-    sum[6] = fmaf(tz, x4, sum[6]); sum[7] = fmaf(tz, y4, sum[7]); sum[8] = fmaf(tz, z4, sum[8]);
-}
-
-// the nine sums of a hypothesis from its four waves' lane sums; every thread of the workgroup calls it (two barriers)
-__device__ __forceinline__ void rvg_reduce_store(float (&sum)[9], float* lds_red, int tid, bool bad_r, float* dst)
-{
-    const int lane = tid & 63, m = tid >> 6;
-#pragma unroll
-    for (int i = 0; i < 9; ++i) {
-        float x = sum[i];
-#pragma unroll
-        for (int s = 32; s >= 1; s >>= 1) x += __shfl_xor(x, s, 64);
-        sum[i] = x;
-    }
-    if (lane < 9) {
-        float x = sum[0];
-#pragma unroll
-        for (int i = 1; i < 9; ++i) x = lane == i ? sum[i] : x;
-        lds_red[m * 12 + lane] = x;
-    }
-    __syncthreads();
-    if (tid < 9) {
-        const float x = (lds_red[tid] + lds_red[12 + tid]) + (lds_red[24 + tid] + lds_red[36 + tid]);
-        dst[tid] = bad_r ? __builtin_nanf("") : x;
-    }
-    __syncthreads();   // lds_red, and the source image of a per-hypothesis volume, are free again
-}
 
 __global__ __launch_bounds__(kRvgThreads) void rotate_volume_rotation_grad_16x8_kernel(
     const float* __restrict__ grad_out, const float* __restrict__ vol, long vol_batch_stride, const float* __restrict__ R,
@@ -1548,40 +1425,17 @@ __global__ __launch_bounds__(kRvgThreads) void rotate_volume_rotation_grad_16x8_
             __syncthreads();
         }
         float Rm[9];
-#pragma unroll
-        for (int i = 0; i < 9; ++i) Rm[i] = R[h * 9 + i];
-        bool bad_r = false;   // a NaN / inf entry of R: autograd's gradient is NaN, the clamp in rg_axis would hide it
-#pragma unroll
-        for (int i = 0; i < 9; ++i) bad_r = bad_r || __builtin_amdgcn_classf(Rm[i], 0x207);
+        bool bad_r;
+        load_rotation(Rm, bad_r, R + h * 9);
         float sum[9];
 #pragma unroll
         for (int i = 0; i < 9; ++i) sum[i] = 0.0f;
+        const float x4 = (float)(lane & 7) - 3.5f, y4 = (float)(lane >> 3) - 3.5f;   // 4 * voxel centre = S_a / 2 * p_b
 #pragma unroll
-        for (int z = 0; z < 8; ++z) rvg_gather_plane(sum, g[0][z], g[1][z], g[2][z], g[3][z], src_ch, Rm, lane, z);
-        rvg_reduce_store(sum, lds_red, tid, bad_r, grad_R + h * 9);
+        for (int z = 0; z < 8; ++z)
+            rot_grad_voxel(sum, g[0][z], g[1][z], g[2][z], g[3][z], src_ch, Rm, x4, y4, (float)z - 3.5f);
+        reduce_store_nine(sum, lds_red, tid, bad_r, grad_R + h * 9);
     }
-}
-
-struct RvgAxisN {
-    float w0, w1;   // value weights of rows j, j + 1 (0 where the row is outside the volume)
-    float d0, d1;   // their derivatives w.r.t. the sample coordinate (-1 / +1, 0 where outside)
-    long o0, o1;    // clamped row index * stride (floats)
-};
-
-// rg_axis for an axis of any size: g = the normalised coordinate, i = ((g + 1) size - 1) / 2 as rotate_volume_generic_kernel
-__device__ __forceinline__ void rvg_axis_generic(float g, int size, long stride, RvgAxisN& a)
-{
-    float i = ((g + 1.0f) * (float)size - 1.0f) * 0.5f;
-    i = fminf(fmaxf(i, -2.0f), (float)size + 1.0f);   // keeps the conversion defined; all corners are outside there anyway
-    const float fl = floorf(i), t = i - fl;
-    const int i0 = (int)fl, i1 = i0 + 1;
-    const bool in0 = i0 >= 0 && i0 < size, in1 = i1 >= 0 && i1 < size;
-    a.w0 = in0 ? 1.0f - t : 0.0f;
-    a.w1 = in1 ? t : 0.0f;
-    a.d0 = in0 ? -1.0f : 0.0f;
-    a.d1 = in1 ? 1.0f : 0.0f;
-    a.o0 = (long)min(max(i0, 0), size - 1) * stride;
-    a.o1 = (long)min(max(i1, 0), size - 1) * stride;
 }
 
 __global__ __launch_bounds__(kRvgThreads) void rotate_volume_rotation_grad_generic_kernel(
@@ -1594,32 +1448,26 @@ __global__ __launch_bounds__(kRvgThreads) void rotate_volume_rotation_grad_gener
     const float sx = 0.5f * (float)W, sy = 0.5f * (float)H, sz = 0.5f * (float)D;   // d i_a / d q_a
     for (long n = blockIdx.x; n < N; n += gridDim.x) {
         float Rm[9];
-#pragma unroll
-        for (int i = 0; i < 9; ++i) Rm[i] = R[n * 9 + i];
-        bool bad_r = false;
-#pragma unroll
-        for (int i = 0; i < 9; ++i) bad_r = bad_r || __builtin_amdgcn_classf(Rm[i], 0x207);
+        bool bad_r;
+        load_rotation(Rm, bad_r, R + n * 9);
         const float* src = vol + n * vol_batch_stride;
         const float* go = grad_out + n * C * plane;
         float sum[9];
 #pragma unroll
         for (int i = 0; i < 9; ++i) sum[i] = 0.0f;
         for (long v = tid; v < plane; v += kRvgThreads) {
-            const int w = (int)(v % W), h = (int)((v / W) % H), d = (int)(v / ((long)W * H));
-            const float x = (2.0f * w + 1.0f) / (float)W - 1.0f;
-            const float y = (2.0f * h + 1.0f) / (float)H - 1.0f;
-            const float z = (2.0f * d + 1.0f) / (float)D - 1.0f;
-            RvgAxisN ax, ay, az;
-            rvg_axis_generic(Rm[0] * x + Rm[1] * y + Rm[2] * z, W, 1, ax);
-            rvg_axis_generic(Rm[3] * x + Rm[4] * y + Rm[5] * z, H, W, ay);
-            rvg_axis_generic(Rm[6] * x + Rm[7] * y + Rm[8] * z, D, (long)W * H, az);
+            const TriVoxel p = tri_voxel(v, D, H, W, Rm);
+            TriAxis<long> ax, ay, az;
+            tri_axis(tri_index(p.gx, W), W, 1L, ax);
+            tri_axis(tri_index(p.gy, H), H, (long)W, ay);
+            tri_axis(tri_index(p.gz, D), D, (long)W * H, az);
             long off[8];
             bool in[8];
             float s[8];
 #pragma unroll
-            for (int k = 0; k < 8; ++k) {   // corner (dz, dy, dx) = bits (4, 2, 1)
-                off[k] = ((k & 1) ? ax.o1 : ax.o0) + ((k & 2) ? ay.o1 : ay.o0) + ((k & 4) ? az.o1 : az.o0);
-                in[k] = ((k & 1) ? ax.d1 : ax.d0) != 0.0f && ((k & 2) ? ay.d1 : ay.d0) != 0.0f && ((k & 4) ? az.d1 : az.d0) != 0.0f;
+            for (int k = 0; k < 8; ++k) {
+                off[k] = tri_corner_off(k, ax, ay, az);
+                in[k] = tri_corner_in(k, ax, ay, az);
                 s[k] = 0.0f;
             }
             for (int c = 0; c < C; ++c) {   // s_corner = <grad_out[:, p], V[:, corner]>; an outside corner is not read
@@ -1631,20 +1479,10 @@ __global__ __launch_bounds__(kRvgThreads) void rotate_volume_rotation_grad_gener
             }
             float tx = 0.0f, ty = 0.0f, tz = 0.0f;
 #pragma unroll
-            for (int k = 0; k < 8; ++k) {
-                const float wx = (k & 1) ? ax.w1 : ax.w0, gx = (k & 1) ? ax.d1 : ax.d0;
-                const float wy = (k & 2) ? ay.w1 : ay.w0, gy = (k & 2) ? ay.d1 : ay.d0;
-                const float wz = (k & 4) ? az.w1 : az.w0, gz = (k & 4) ? az.d1 : az.d0;
-                tx = fmaf(s[k], gx * (wy * wz), tx);
-                ty = fmaf(s[k], gy * (wx * wz), ty);
-                tz = fmaf(s[k], gz * (wx * wy), tz);
-            }
-            tx *= sx; ty *= sy; tz *= sz;
-            sum[0] = fmaf(tx, x, sum[0]); sum[1] = fmaf(tx, y, sum[1]); sum[2] = fmaf(tx, z, sum[2]);
-            sum[3] = fmaf(ty, x, sum[3]); sum[4] = fmaf(ty, y, sum[4]); sum[5] = fmaf(ty, z, sum[5]);
-            sum[6] = fmaf(tz, x, sum[6]); sum[7] = fmaf(tz, y, sum[7]); sum[8] = fmaf(tz, z, sum[8]);
+            for (int k = 0; k < 8; ++k) tri_corner_grad(k, s[k], ax, ay, az, tx, ty, tz);
+            tri_outer_add(sum, tx * sx, ty * sy, tz * sz, p.x, p.y, p.z);
         }
-        rvg_reduce_store(sum, lds_red, tid, bad_r, grad_R + n * 9);
+        reduce_store_nine(sum, lds_red, tid, bad_r, grad_R + n * 9);
     }
 }
 

@@ -119,162 +119,30 @@ __device__ __forceinline__ void load_head_frags(HeadFrags& f, const float* __res
     }
 }
 
+// v_cmp_class_f32 mask: signalling NaN | quiet NaN | -inf | +inf
+constexpr int kClassNonFinite = 0x1 | 0x2 | 0x4 | 0x200;
+
+__device__ __forceinline__ bool non_finite(float x) { return __builtin_amdgcn_classf(x, kClassNonFinite); }
+
 // ---- source volume -> LDS (channel-last, padded) ---------------------------------
+// Returns whether this thread met a NaN / inf voxel (the project's rule for non-finite inputs, ahv_exact.h); a caller
+// that does not ask uses stage_src_volume, where the test folds away.
+__device__ __forceinline__ bool stage_src_volume_scan(float* srcT, const float* __restrict__ vol, int tid, int nthreads)
+{
+    bool bad = false;
+    for (int i = tid; i < 16 * 512; i += nthreads) {
+        const int c = i >> 9, v = i & 511;
+        const float x = vol[i];
+        bad = bad || non_finite(x);
+        srcT[((v >> 6) * kSrcPlaneRows + ((v >> 3) & 7) * kSrcRowsY + (v & 7)) * kSrcStride + c] = x;
+    }
+    return bad;
+}
+
 __device__ __forceinline__ void stage_src_volume(float* srcT, const float* __restrict__ vol, int tid,
                                                  int nthreads)
 {
-    for (int i = tid; i < 16 * 512; i += nthreads) {
-        const int c = i >> 9, v = i & 511;
-        srcT[((v >> 6) * kSrcPlaneRows + ((v >> 3) & 7) * kSrcRowsY + (v & 7)) * kSrcStride + c] = vol[i];
-    }
-}
-
-// ---- trilinear gather of one 64-voxel pass -----------------------------------------
-// Voxel of this lane: (d, h, w).  Semantics = F.affine_grid + F.grid_sample(bilinear,
-// zeros, align_corners=False) as called by utils.rotate_volume (utils.py:123-129):
-//   p = ((2w+1)/8-1, (2h+1)/8-1, (2d+1)/8-1); g = R p; i = ((g+1)*8-1)/2 per axis;
-//   8 neighbours floor(i), floor(i)+1, each dropped when outside [0,7] (zeros padding
-//   per corner).  g[0] indexes W, g[1] H, g[2] D.
-struct TriCoef {
-    float w[8];  // corner weights, order (dz,dy,dx), zero for out-of-range corners
-    int a[8];    // float index of the corner's row in the channel-last source image
-};
-
-__device__ __forceinline__ void axis_coef(float g, float& w0, float& w1, int& o0, int& o1, int scale)
-{
-    float i = ((g + 1.0f) * 8.0f - 1.0f) * 0.5f;
-    // Clamp keeps the int conversion defined for any R (inf/NaN included); every
-    // clamped-away position has all corners out of range anyway (weight 0).
-    i = fminf(fmaxf(i, -2.0f), 9.0f);
-    const float fl = floorf(i);
-    const float t = i - fl;
-    const int i0 = (int)fl;
-    const int i1 = i0 + 1;
-    w0 = ((unsigned)i0 < 8u) ? 1.0f - t : 0.0f;
-    w1 = ((unsigned)i1 < 8u) ? t : 0.0f;
-    o0 = min(max(i0, 0), 7) * scale;
-    o1 = min(max(i1, 0), 7) * scale;
-}
-
-__device__ __forceinline__ void tri_coef(TriCoef& k, const float* Rm, float x, float y, float z)
-{
-    const float gx = Rm[0] * x + Rm[1] * y + Rm[2] * z;
-    const float gy = Rm[3] * x + Rm[4] * y + Rm[5] * z;
-    const float gz = Rm[6] * x + Rm[7] * y + Rm[8] * z;
-    float wx0, wx1, wy0, wy1, wz0, wz1;
-    int ox0, ox1, oy0, oy1, oz0, oz1;
-    axis_coef(gx, wx0, wx1, ox0, ox1, kSrcStride);
-    axis_coef(gy, wy0, wy1, oy0, oy1, kSrcRowsY * kSrcStride);
-    axis_coef(gz, wz0, wz1, oz0, oz1, kSrcPlaneRows * kSrcStride);
-    const float w00 = wz0 * wy0, w01 = wz0 * wy1, w10 = wz1 * wy0, w11 = wz1 * wy1;
-    k.w[0] = w00 * wx0; k.w[1] = w00 * wx1; k.w[2] = w01 * wx0; k.w[3] = w01 * wx1;
-    k.w[4] = w10 * wx0; k.w[5] = w10 * wx1; k.w[6] = w11 * wx0; k.w[7] = w11 * wx1;
-    const int a00 = oz0 + oy0, a01 = oz0 + oy1, a10 = oz1 + oy0, a11 = oz1 + oy1;
-    k.a[0] = a00 + ox0; k.a[1] = a00 + ox1; k.a[2] = a01 + ox0; k.a[3] = a01 + ox1;
-    k.a[4] = a10 + ox0; k.a[5] = a10 + ox1; k.a[6] = a11 + ox0; k.a[7] = a11 + ox1;
-}
-
-// Blend the 16 channels of one output voxel from the LDS source image.
-__device__ __forceinline__ void tri_blend(float (&out)[16], const float* srcT, const TriCoef& k)
-{
-#pragma unroll
-    for (int c = 0; c < 16; ++c) out[c] = 0.0f;
-#pragma unroll
-    for (int n = 0; n < 8; ++n) {
-        const f32x4* row = reinterpret_cast<const f32x4*>(srcT + k.a[n]);
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const f32x4 v = row[j];
-            out[4 * j + 0] += k.w[n] * v[0];
-            out[4 * j + 1] += k.w[n] * v[1];
-            out[4 * j + 2] += k.w[n] * v[2];
-            out[4 * j + 3] += k.w[n] * v[3];
-        }
-    }
-}
-
-// Byte-offset form of the same coefficients: the corner rows come out as LDS pointers (no index -> byte
-// conversion per corner, one integer multiply per axis neighbour).
-struct TriCoefP {
-    float w[8];
-    const float* p[8];
-};
-
-__device__ __forceinline__ void axis_coef_bytes(float g, float& w0, float& w1, int& o0, int& o1, int scale_bytes)
-{
-    float i = ((g + 1.0f) * 8.0f - 1.0f) * 0.5f;
-    i = fminf(fmaxf(i, -2.0f), 9.0f);
-    const float fl = floorf(i);
-    const float t = i - fl;
-    const int i0 = (int)fl;
-    const int i1 = i0 + 1;
-    w0 = ((unsigned)i0 < 8u) ? 1.0f - t : 0.0f;
-    w1 = ((unsigned)i1 < 8u) ? t : 0.0f;
-    o0 = min(max(i0, 0), 7) * scale_bytes;
-    o1 = min(max(i1, 0), 7) * scale_bytes;
-}
-
-__device__ __forceinline__ void tri_coef_ptr(TriCoefP& k, const float* srcT, const float* Rm, float x, float y, float z)
-{
-    const float gx = Rm[0] * x + Rm[1] * y + Rm[2] * z;
-    const float gy = Rm[3] * x + Rm[4] * y + Rm[5] * z;
-    const float gz = Rm[6] * x + Rm[7] * y + Rm[8] * z;
-    float wx0, wx1, wy0, wy1, wz0, wz1;
-    int ox0, ox1, oy0, oy1, oz0, oz1;
-    axis_coef_bytes(gx, wx0, wx1, ox0, ox1, 4 * kSrcStride);
-    axis_coef_bytes(gy, wy0, wy1, oy0, oy1, 4 * kSrcRowsY * kSrcStride);
-    axis_coef_bytes(gz, wz0, wz1, oz0, oz1, 4 * kSrcPlaneRows * kSrcStride);
-    const float w00 = wz0 * wy0, w01 = wz0 * wy1, w10 = wz1 * wy0, w11 = wz1 * wy1;
-    k.w[0] = w00 * wx0; k.w[1] = w00 * wx1; k.w[2] = w01 * wx0; k.w[3] = w01 * wx1;
-    k.w[4] = w10 * wx0; k.w[5] = w10 * wx1; k.w[6] = w11 * wx0; k.w[7] = w11 * wx1;
-    const char* base = reinterpret_cast<const char*>(srcT);
-    const char* z0 = base + oz0;
-    const char* z1 = base + oz1;
-    const char* a00 = z0 + oy0; const char* a01 = z0 + oy1; const char* a10 = z1 + oy0; const char* a11 = z1 + oy1;
-    k.p[0] = reinterpret_cast<const float*>(a00 + ox0); k.p[1] = reinterpret_cast<const float*>(a00 + ox1);
-    k.p[2] = reinterpret_cast<const float*>(a01 + ox0); k.p[3] = reinterpret_cast<const float*>(a01 + ox1);
-    k.p[4] = reinterpret_cast<const float*>(a10 + ox0); k.p[5] = reinterpret_cast<const float*>(a10 + ox1);
-    k.p[6] = reinterpret_cast<const float*>(a11 + ox0); k.p[7] = reinterpret_cast<const float*>(a11 + ox1);
-}
-
-__device__ __forceinline__ void tri_blend_ptr(float (&out)[16], const TriCoefP& k)
-{
-#pragma unroll
-    for (int n = 0; n < 8; ++n) {
-        const f32x4* row = reinterpret_cast<const f32x4*>(k.p[n]);
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const f32x4 v = row[j];
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                if (n == 0) out[4 * j + e] = k.w[n] * v[e];
-                else out[4 * j + e] += k.w[n] * v[e];
-            }
-        }
-    }
-}
-
-// Produce quarter Q (d in {2Q, 2Q+1}) of the rotated volume into `buf` (swizzled planes).
-// Two passes of 64 voxels; lane -> (w = l&7, d0 = (l>>3)&1, h = 4p + 2*((l>>5)&1) + ((l>>4)&1)),
-// a mapping whose ds_write_b32 hits 32 distinct banks per half-wave.
-template <int Q>
-__device__ __forceinline__ void tri_quarter(float* buf, const float* srcT, const float* Rm, int lane)
-{
-    const int e = lane & 7, a0 = (lane >> 3) & 1, b0 = (lane >> 4) & 1, b1 = (lane >> 5) & 1;
-    const float x = (2.0f * e + 1.0f) * 0.125f - 1.0f;
-    const float z = (2.0f * (2 * Q + a0) + 1.0f) * 0.125f - 1.0f;
-#pragma unroll
-    for (int p = 0; p < 2; ++p) {
-        const int b = 4 * p + 2 * b1 + b0;
-        const float y = (2.0f * b + 1.0f) * 0.125f - 1.0f;
-        TriCoefP k;
-        tri_coef_ptr(k, srcT, Rm, x, y, z);
-        float o[16];
-        tri_blend_ptr(o, k);
-        float* dst = buf + qoff(a0, b, e);
-#pragma unroll
-        for (int c = 0; c < 16; ++c) dst[c * 128] = o[c];
-    }
+    (void)stage_src_volume_scan(srcT, vol, tid, nthreads);
 }
 
 // ---- GEMM1 on one quarter ---------------------------------------------------------

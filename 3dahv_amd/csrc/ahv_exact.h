@@ -22,10 +22,7 @@
 
 namespace ahv {
 
-// v_cmp_class_f32 mask: signalling NaN | quiet NaN | -inf | +inf
-constexpr int kClassNonFinite = 0x1 | 0x2 | 0x4 | 0x200;
-
-__device__ __forceinline__ bool non_finite(float x) { return __builtin_amdgcn_classf(x, kClassNonFinite); }
+// non_finite(x), the class test for a NaN / inf, is ahv_device.h's: the staging there reports it too
 
 // Written while a sample (generation `gen` = samples this workgroup has staged so far + 1) or the head weights are staged,
 // read behind the staging barrier.  Zeroed once per launch; a generation never repeats, so nothing is reset per sample.

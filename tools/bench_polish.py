@@ -12,7 +12,7 @@ spread), every shape warmed first -- the method of tools/bench_topk.py, whose he
       score and geodesic error of (a) the 50 000 arg-max, (b) CoarseToFine 10 000 + 1 000, (c) arg-max + polish (K = 8,
       iters = 8), (d) CoarseToFine 10 000 + 1 000 + polish_iters = 8, each with its time
 
-    python tools/bench_polish.py [--out profiles/polish_step.jsonl] [--only G,P,Q] [--rounds 5] [--iters 30]
+    python tools/bench_polish.py [--out profiles/polish_step.jsonl] [--only G,P,Q] [--rounds 5] [--iters 30] [--lib PATH] [--label NAME]
 """
 import argparse
 import importlib
@@ -35,10 +35,14 @@ def main():
     ap.add_argument("--only", default="")
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--iters", type=int, default=30)
+    ap.add_argument("--lib", default=None, help="libahv_hip.so to measure instead of the in-tree build")
+    ap.add_argument("--label", default=None, help="build label written into every row")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         sys.exit("bench_polish.py measures on the GPU only")
     ahv = importlib.import_module("3dahv_amd")
+    if a.lib:
+        ahv._lib.LIB_PATH = os.path.abspath(a.lib)
     ops, rot = ahv.ops, ahv.rotations
     dev = torch.device("cuda:0")
     g = np.load(os.path.join(REPO, "tests", "golden", "score_n128.npz"))
@@ -46,6 +50,8 @@ def main():
     vs, vt, W1, W2, b2 = (T(g[k]) for k in ("vol_src", "vol_tgt", "W1", "W2", "b2"))
     box = {"device": torch.cuda.get_device_name(0), "rocm": torch.version.hip, "torch": torch.__version__,
            "cu": ahv._lib.load().ahv_device_cu_count()}
+    if a.label:
+        box["build"] = a.label
     rows = []
 
     def emit(row, stats):

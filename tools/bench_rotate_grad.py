@@ -14,7 +14,10 @@ Three sets on (16, 8, 8, 8) volumes: one shared volume at N = 9 000 and N = 50 0
 (a per-sample set reads another 32 KiB of volume per hypothesis: "gbytes_per_s_with_volume").
 The bar: kernel_path (autograd) faster than stock at both N by more than the spread between rounds.
 
-    python tools/bench_rotate_grad.py [--out profiles/rotate_grad.jsonl] [--rounds 5] [--iters 10]
+``--lib`` measures another build of the same ABI, ``--variants`` a comma-separated subset (the rows that need "stock" are
+then left without their ratios), ``--label`` is written into every row.
+
+    python tools/bench_rotate_grad.py [--out profiles/rotate_grad.jsonl] [--rounds 5] [--iters 10] [--lib PATH] [--variants kernel,volume_adjoint] [--label NAME]
 """
 import argparse
 import importlib
@@ -49,14 +52,21 @@ def main():
     ap.add_argument("--out", default=os.path.join(REPO, "profiles", "rotate_grad.jsonl"))
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--iters", type=int, default=10)
+    ap.add_argument("--lib", default=None, help="libahv_hip.so to measure instead of the in-tree build")
+    ap.add_argument("--variants", default="", help="comma-separated subset of the variants")
+    ap.add_argument("--label", default=None, help="build label written into every row")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         sys.exit("bench_rotate_grad.py measures on the GPU only")
     ahv = importlib.import_module("3dahv_amd")
+    if a.lib:
+        ahv._lib.LIB_PATH = os.path.abspath(a.lib)
     ops = ahv.ops
     dev = torch.device("cuda:0")
     box = {"device": torch.cuda.get_device_name(0), "rocm": torch.version.hip, "torch": torch.__version__,
            "cu": ahv._lib.load().ahv_device_cu_count()}
+    if a.label:
+        box["build"] = a.label
     rows = []
     for kind, N in SETS:
         gen = torch.Generator(device=dev).manual_seed(N + len(kind))
@@ -91,6 +101,8 @@ def main():
             "volume_adjoint": lambda: ops._call(dev, "ahv_rotate_volume_backward_f32", g.data_ptr(), stride, R.data_ptr(), N,
                                                 16, 8, 8, 8, gv.data_ptr()),
         }
+        if a.variants:
+            variants = {k: variants[k] for k in a.variants.split(",")}
         st = alternate(variants, a.rounds, a.iters)
         for name, s in st.items():
             row = dict({"set": kind, "N": N, "variant": name}, **s, **box)
@@ -98,7 +110,7 @@ def main():
                 row["gbytes_per_s"] = round(N * VOL_BYTES / (s["us"] * 1e-6) / 1e9, 1)
                 if kind != "shared" and name == "kernel":
                     row["gbytes_per_s_with_volume"] = round(2 * N * VOL_BYTES / (s["us"] * 1e-6) / 1e9, 1)
-            if name == "autograd":
+            if name == "autograd" and "stock" in st:
                 row["stock_over_kernel_path"] = round(st["stock"]["us"] / s["us"], 2)
                 row["faster_beyond_spread"] = bool(s["max_us"] < st["stock"]["min_us"])
                 row["median_rel_err_vs_stock"] = float(err.median())

@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
-"""Developer tool: time ops.rotate_volume at N = 200 000 with the library given as argv[1] (default: the in-tree build)."""
-import importlib, os, sys, torch
+"""Developer tool: time ops.rotate_volume at N = 200 000 with the library given as argv[1] (default: the in-tree build);
+argv[2], if given, is a build label and adds one JSON line (median / min / max of the ten launches, in us)."""
+import importlib, json, os, sys, torch
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, REPO)
 ahv = importlib.import_module("3dahv_amd")
@@ -24,3 +25,7 @@ for _ in range(10):
 ts.sort()
 print("%s: rotate_volume N=%d  min %.4f  median %.4f ms  -> %.2f TB/s (32 804 B per hypothesis)" % (
     os.path.basename(os.path.dirname(ahv._lib.LIB_PATH)), N, ts[0], ts[5], N * 32804 / ts[5] / 1e9))
+if len(sys.argv) > 2:
+    print(json.dumps({"tool": "rot_time.py", "row": "rotate_volume", "N": N, "build": sys.argv[2], "us": round(1e3 * ts[5], 3),
+                      "min_us": round(1e3 * ts[0], 3), "max_us": round(1e3 * ts[-1], 3), "launches": len(ts),
+                      "device": torch.cuda.get_device_name(0), "rocm": torch.version.hip, "torch": torch.__version__}))
