@@ -20,6 +20,29 @@ namespace ahv {
 constexpr int kF32Threads = 256;
 constexpr int kF32LdsFloats = 4 * 2 * kQuarterFloats;
 
+// F.normalize's denominator, |v|.clamp_min(eps): torch's clamp KEEPS a NaN norm (a column that holds +-inf beside NaN is NaN
+// throughout), where fmaxf hands back eps and leaves the +-inf in the column.  For every norm that is a number, fmaxf's value.
+__device__ __forceinline__ float clamped_norm(float ss)
+{
+    const float nrm = sqrtf(ss);
+    return nrm < 1e-12f ? 1e-12f : nrm;
+}
+
+// A lane's share of |v|^2: its 2 x 4 channels of one position.  The association is spelled out -- element 1's square rounded
+// on its own, element 0 joined to it by FMA, then 2, 3 and the second four in order -- because it is what the compiler made of
+// `ss += v * v` while an fmaxf stood behind the loop; with the select of clamped_norm there it left the same loop as separate
+// multiplies and adds, and the features' last bits moved.
+__device__ __forceinline__ float sumsq8(const f32x4& a, const f32x4& b)
+{
+    float ss = a[1] * a[1];
+    ss = fmaf(a[0], a[0], ss);
+    ss = fmaf(a[2], a[2], ss);
+    ss = fmaf(a[3], a[3], ss);
+#pragma unroll
+    for (int r = 0; r < 4; ++r) ss = fmaf(b[r], b[r], ss);
+    return ss;
+}
+
 template <int Q>
 __device__ __forceinline__ void stage_quarter(float* buf, const float* __restrict__ vol, int lane)
 {
@@ -71,14 +94,10 @@ __global__ __launch_bounds__(kF32Threads, 1) void forward_3d2d_kernel(
         float* o = out + m * (32 * 64);
 #pragma unroll
         for (int t = 0; t < 4; ++t) {
-            float ss = 0.0f;
-#pragma unroll
-            for (int m2 = 0; m2 < 2; ++m2)
-#pragma unroll
-                for (int r = 0; r < 4; ++r) ss += v[m2][t][r] * v[m2][t][r];
+            float ss = sumsq8(v[0][t], v[1][t]);
             ss += __shfl_xor(ss, 16, 64);
             ss += __shfl_xor(ss, 32, 64);
-            const float nrm = fmaxf(sqrtf(ss), 1e-12f);  // F.normalize clamp_min(eps)
+            const float nrm = clamped_norm(ss);
 #pragma unroll
             for (int m2 = 0; m2 < 2; ++m2)
 #pragma unroll
@@ -142,17 +161,13 @@ __global__ __launch_bounds__(512, 2) void forward_3d2d_dual_kernel(
         float* o = out + m * (32 * 64);
 #pragma unroll
         for (int t = 0; t < 4; ++t) {
-            float ss = 0.0f;
-#pragma unroll
-            for (int m2 = 0; m2 < 2; ++m2)
-#pragma unroll
-                for (int r = 0; r < 4; ++r) ss += v[m2][t][r] * v[m2][t][r];
+            float ss = sumsq8(v[0][t], v[1][t]);
             ss += __shfl_xor(ss, 16, 64);
             ss += __shfl_xor(ss, 32, 64);
             // v / max(|v|, eps) as v * (1 / max(|v|, eps)): ONE correctly rounded division per position instead of eight per
             // lane (an IEEE division is ~10 vector instructions, and fp32 MFMAs overlap none of them: 320 of an item's ~900);
             // each feature within 1 ulp of the quotient
-            const float inv = 1.0f / fmaxf(sqrtf(ss), 1e-12f);
+            const float inv = 1.0f / clamped_norm(ss);
 #pragma unroll
             for (int m2 = 0; m2 < 2; ++m2)
 #pragma unroll
@@ -260,14 +275,10 @@ __global__ __launch_bounds__(512) void forward_3d2d_small_kernel(
             v[0] = __builtin_amdgcn_mfma_f32_16x16x4f32(a20, x, v[0], 0, 0, 0);
             v[1] = __builtin_amdgcn_mfma_f32_16x16x4f32(a21, x, v[1], 0, 0, 0);
         }
-    float ss = 0.0f;
-#pragma unroll
-    for (int m2 = 0; m2 < 2; ++m2)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) ss += v[m2][r] * v[m2][r];
+    float ss = sumsq8(v[0], v[1]);
     ss += __shfl_xor(ss, 16, 64);
     ss += __shfl_xor(ss, 32, 64);
-    const float nrm = fmaxf(sqrtf(ss), 1e-12f);
+    const float nrm = clamped_norm(ss);
     float* o = out + (long)blockIdx.x * (32 * 64);
 #pragma unroll
     for (int m2 = 0; m2 < 2; ++m2)
