@@ -33,6 +33,8 @@ AHV_VIEWS_NO_ANGLE_LIMIT = 2
 AHV_VIEW_SLOT_EXCLUDED = -1
 AHV_VIEW_SLOT_OVERFLOW = -2
 AHV_GATHER_BROADCAST = 1
+AHV_TRACK_CONTROL_WORDS = 8
+AHV_TRACK_LOST, AHV_TRACK_REACQUIRED, AHV_TRACK_UPDATED = 1, 2, 4
 
 _vp = ctypes.c_void_p
 _i64 = ctypes.c_int64
@@ -140,6 +142,14 @@ SIGNATURES["ahv_diffuse_rotations_f32"] = (_int, [_vp, _vp, _i64, _i64, _vp, _i6
 #  sigma_rad, sigma_vel_rad, damping, max_angle_rad, max_speed_rad, coast, out, vel_out, omega or NULL, stream)
 SIGNATURES["ahv_predict_rotations_f32"] = (_int, [_vp, _vp, _i64, _vp, _i64, _i64, _vp, _i64, _i64, _int, ctypes.c_uint64, _vp]
                                            + [ctypes.c_float] * 5 + [_int, _vp, _vp, _vp, _vp])
+# (R_cur, V_cur or NULL, idx, score, B, M, first, sigma0_rad, sigma_vel0_rad, n_fresh0, sigma_min_rad, sigma_max_rad, gain, rate,
+#  score_floor, n_fresh_lost, control: DEVICE [B][8] words, reacquired: DEVICE bytes, stream)
+SIGNATURES["ahv_track_control_f32"] = (_int, [_vp, _vp, _vp, _vp, _int, _i64, _int, ctypes.c_float, ctypes.c_float, _i64]
+                                       + [ctypes.c_float] * 5 + [_i64, _vp, _vp, _vp])
+# (idx or NULL, R, r_batch_stride, V or NULL, v_batch_stride, N, best_key or NULL, M, control: DEVICE [B][8] words, B, seed,
+#  step: DEVICE int64, damping, max_angle_rad, max_speed_rad, coast, out, vel_out or NULL, omega or NULL, stream)
+SIGNATURES["ahv_predict_rotations_ctl_f32"] = (_int, [_vp, _vp, _i64, _vp, _i64, _i64, _vp, _i64, _vp, _int, ctypes.c_uint64, _vp]
+                                               + [ctypes.c_float] * 3 + [_int, _vp, _vp, _vp, _vp])
 # (seed, step: DEVICE int64, B, u: DEVICE floats, stream)
 SIGNATURES["ahv_track_advance"] = (_int, [ctypes.c_uint64, _vp, _int, _vp, _vp])
 # (R_cur, scores, V_cur or NULL, step: DEVICE int64, first_step, B, M, H, beta, sigma_rad, jump, damping, hist_R, hist_P or NULL,

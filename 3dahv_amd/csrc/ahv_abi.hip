@@ -64,6 +64,11 @@ hipError_t launch_predict_rotations(const int64_t*, const float*, int64_t, const
                                     int64_t, int, uint64_t, const int64_t*, float, float, float, float, float, int, float*, float*,
                                     float*, hipStream_t);
 hipError_t launch_track_advance(uint64_t, int64_t*, int, float*, hipStream_t);
+hipError_t launch_predict_rotations_ctl(const int64_t*, const float*, int64_t, const float*, int64_t, int64_t, const int64_t*, int64_t,
+                                        const uint32_t*, int, uint64_t, const int64_t*, float, float, float, int, float*, float*,
+                                        float*, hipStream_t);
+hipError_t launch_track_control(const float*, const float*, const int64_t*, const float*, int, int64_t, int, float, float, int, float,
+                                float, float, float, float, int, uint32_t*, uint8_t*, hipStream_t);
 hipError_t launch_smooth_step(const float*, const float*, const float*, const int64_t*, int64_t, int, int64_t, int64_t, float, float,
                               float, float, float*, float*, float*, int32_t*, hipStream_t);
 hipError_t launch_smooth_backtrace(const float*, const float*, const int32_t*, const int64_t*, int64_t, int, int64_t, int64_t,
@@ -1132,6 +1137,70 @@ int ahv_track_advance(uint64_t seed, int64_t* step, int B, float* u, void* strea
     if (B < 1 || B > 65535) return fail(AHV_EINVAL, "track_advance: B = %d outside 1..65535", B);
     hipError_t e = ahv::launch_track_advance(seed, step, B, u, static_cast<hipStream_t>(stream));
     if (e != hipSuccess) return hip_fail("track_advance: launch", e);
+    return AHV_OK;
+}
+
+// ---- pose tracking: noise scale and fresh slots adapted on the device ----------------------------------------------
+static_assert(AHV_TRACK_CONTROL_WORDS == 8, "ahv_track.hip lays the control record out as eight words");
+
+int ahv_predict_rotations_ctl_f32(const int64_t* idx, const float* R, int64_t r_batch_stride, const float* V, int64_t v_batch_stride,
+                                  int64_t N, const int64_t* best_key, int64_t M, const uint32_t* control, int B, uint64_t seed,
+                                  const int64_t* step, float damping, float max_angle_rad, float max_speed_rad, int coast,
+                                  float* out, float* vel_out, float* omega, void* stream)
+{
+    const auto angle = [](float a) { return a >= 0.0f && a < __builtin_inff(); };
+    if (!R || !out || !step || !control)
+        return fail(AHV_EINVAL, "predict_rotations_ctl: null pointer (R, out, step and control are required)");
+    if (!vel_out && (V || coast != 0))
+        return fail(AHV_EINVAL, "predict_rotations_ctl: vel_out is required with V or a coast slot (without all three: the walk)");
+    if (M < 1 || M >= (int64_t)1 << 31) return fail(AHV_EINVAL, "predict_rotations_ctl: M = %lld outside 1..2^31-1", (long long)M);
+    if (N < 1) return fail(AHV_EINVAL, "predict_rotations_ctl: empty rotation set (N = %lld)", (long long)N);
+    if (B < 1 || B > 65535) return fail(AHV_EINVAL, "predict_rotations_ctl: B = %d outside 1..65535", B);
+    if (r_batch_stride != 0 && r_batch_stride != N * 9)
+        return fail(AHV_EINVAL, "predict_rotations_ctl: r_batch_stride %lld must be 0 or N*9", (long long)r_batch_stride);
+    if (v_batch_stride != 0 && v_batch_stride != N * 3)
+        return fail(AHV_EINVAL, "predict_rotations_ctl: v_batch_stride %lld must be 0 or N*3", (long long)v_batch_stride);
+    if (!(damping >= 0.0f && damping <= 1.0f))
+        return fail(AHV_EINVAL, "predict_rotations_ctl: damping = %g outside [0, 1]", (double)damping);
+    if (!angle(max_angle_rad))
+        return fail(AHV_EINVAL, "predict_rotations_ctl: max_angle = %g must be finite and >= 0 (0: no limit)", (double)max_angle_rad);
+    if (!angle(max_speed_rad))
+        return fail(AHV_EINVAL, "predict_rotations_ctl: max_speed = %g must be finite and >= 0 (0: no limit)", (double)max_speed_rad);
+    hipError_t e = ahv::launch_predict_rotations_ctl(idx, R, r_batch_stride, V, v_batch_stride, N, best_key, M, control, B, seed, step,
+                                                     damping, max_angle_rad, max_speed_rad, coast != 0, out, vel_out, omega,
+                                                     static_cast<hipStream_t>(stream));
+    if (e != hipSuccess) return hip_fail("predict_rotations_ctl: launch", e);
+    return AHV_OK;
+}
+
+int ahv_track_control_f32(const float* R_cur, const float* V_cur, const int64_t* idx, const float* score, int B, int64_t M, int first,
+                          float sigma0_rad, float sigma_vel0_rad, int64_t n_fresh0, float sigma_min_rad, float sigma_max_rad,
+                          float gain, float rate, float score_floor, int64_t n_fresh_lost, uint32_t* control, uint8_t* reacquired,
+                          void* stream)
+{
+    const auto positive = [](float a) { return a > 0.0f && a < __builtin_inff(); };
+    if (!R_cur || !idx || !score || !control || !reacquired)
+        return fail(AHV_EINVAL, "track_control: null pointer (R_cur, idx, score, control and reacquired are required)");
+    if (M < 1 || M >= (int64_t)1 << 31) return fail(AHV_EINVAL, "track_control: M = %lld outside 1..2^31-1", (long long)M);
+    if (B < 1 || B > 65535) return fail(AHV_EINVAL, "track_control: B = %d outside 1..65535", B);
+    if (first != 1 && first != 2) return fail(AHV_EINVAL, "track_control: first = %d must be 1, or 2 with a coast slot", first);
+    if (!positive(sigma_min_rad) || !positive(sigma_max_rad) || sigma_min_rad > sigma_max_rad)
+        return fail(AHV_EINVAL, "track_control: sigma_min = %g and sigma_max = %g must be finite with 0 < sigma_min <= sigma_max",
+                    (double)sigma_min_rad, (double)sigma_max_rad);
+    if (!positive(sigma0_rad)) return fail(AHV_EINVAL, "track_control: sigma0 = %g must be finite and > 0", (double)sigma0_rad);
+    if (!(sigma_vel0_rad >= 0.0f && sigma_vel0_rad < __builtin_inff()))
+        return fail(AHV_EINVAL, "track_control: sigma_vel0 = %g must be finite and >= 0", (double)sigma_vel0_rad);
+    if (!positive(gain)) return fail(AHV_EINVAL, "track_control: gain = %g must be finite and > 0", (double)gain);
+    if (!(rate > 0.0f && rate <= 1.0f)) return fail(AHV_EINVAL, "track_control: rate = %g outside (0, 1]", (double)rate);
+    if (score_floor != score_floor) return fail(AHV_EINVAL, "track_control: score_floor is NaN (-inf: no floor)");
+    if (n_fresh0 < 0 || n_fresh0 > M)
+        return fail(AHV_EINVAL, "track_control: n_fresh0 = %lld outside 0..M = %lld", (long long)n_fresh0, (long long)M);
+    if (n_fresh_lost < 0 || n_fresh_lost > M)
+        return fail(AHV_EINVAL, "track_control: n_fresh_lost = %lld outside 0..M = %lld", (long long)n_fresh_lost, (long long)M);
+    hipError_t e = ahv::launch_track_control(R_cur, V_cur, idx, score, B, M, first, sigma0_rad, sigma_vel0_rad, (int)n_fresh0,
+                                             sigma_min_rad, sigma_max_rad, gain, rate, score_floor, (int)n_fresh_lost, control,
+                                             reacquired, static_cast<hipStream_t>(stream));
+    if (e != hipSuccess) return hip_fail("track_control: launch", e);
     return AHV_OK;
 }
 

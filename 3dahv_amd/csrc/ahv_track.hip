@@ -70,11 +70,10 @@ __device__ __forceinline__ void compose_rotation_vector(const float (&r)[9], flo
     quaternion_matrix(pr, pi, pj, pk, o);
 }
 
-__global__ __launch_bounds__(256) void diffuse_rotations_kernel(const long long* __restrict__ idx, const float* __restrict__ R,
-                                                                long r_batch_stride, long N, const key_t* __restrict__ best_key,
-                                                                long M, long n_fresh, unsigned long long seed,
-                                                                const long long* __restrict__ step, float sigma, float max_angle,
-                                                                float* __restrict__ out, float* __restrict__ omega)
+__device__ __forceinline__ void diffuse_slot(const long long* __restrict__ idx, const float* __restrict__ R, long r_batch_stride,
+                                             long N, const key_t* __restrict__ best_key, long M, long n_fresh,
+                                             unsigned long long seed, const long long* __restrict__ step, float sigma,
+                                             float max_angle, float* __restrict__ out, float* __restrict__ omega)
 {
     const long j = (long)blockIdx.x * 256 + threadIdx.x;
     if (j >= M) return;
@@ -111,6 +110,15 @@ __global__ __launch_bounds__(256) void diffuse_rotations_kernel(const long long*
     }
 }
 
+__global__ __launch_bounds__(256) void diffuse_rotations_kernel(const long long* __restrict__ idx, const float* __restrict__ R,
+                                                                long r_batch_stride, long N, const key_t* __restrict__ best_key,
+                                                                long M, long n_fresh, unsigned long long seed,
+                                                                const long long* __restrict__ step, float sigma, float max_angle,
+                                                                float* __restrict__ out, float* __restrict__ omega)
+{
+    diffuse_slot(idx, R, r_batch_stride, N, best_key, M, n_fresh, seed, step, sigma, max_angle, out, omega);
+}
+
 // ---------------------------------------------------------------------------------
 // Constant-velocity predict step (ahv_predict_rotations_f32, include/ahv.h): a particle is (R, v), v its body-frame rotation
 // vector per frame.  One thread per slot (b, j), as diffuse_rotations_kernel; slot classes in this precedence:
@@ -121,14 +129,12 @@ __global__ __launch_bounds__(256) void diffuse_rotations_kernel(const long long*
 //          out = R_i exp([w]x) composed as unit quaternions and normalised, exactly as diffuse_rotations_kernel does
 // z is the block diffuse_rotations_kernel draws (third counter word kDiffuseTag), y a second block (kVelocityTag).
 // ---------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void predict_rotations_kernel(const long long* __restrict__ idx, const float* __restrict__ R,
-                                                                long r_batch_stride, const float* __restrict__ V,
-                                                                long v_batch_stride, long N, const key_t* __restrict__ best_key,
-                                                                long M, long n_fresh, unsigned long long seed,
-                                                                const long long* __restrict__ step, float sigma, float sigma_vel,
-                                                                float damping, float max_angle, float max_speed, int coast,
-                                                                float* __restrict__ out, float* __restrict__ vel_out,
-                                                                float* __restrict__ omega)
+__device__ __forceinline__ void predict_slot(const long long* __restrict__ idx, const float* __restrict__ R, long r_batch_stride,
+                                             const float* __restrict__ V, long v_batch_stride, long N,
+                                             const key_t* __restrict__ best_key, long M, long n_fresh, unsigned long long seed,
+                                             const long long* __restrict__ step, float sigma, float sigma_vel, float damping,
+                                             float max_angle, float max_speed, int coast, float* __restrict__ out,
+                                             float* __restrict__ vel_out, float* __restrict__ omega)
 {
     const long j = (long)blockIdx.x * 256 + threadIdx.x;
     if (j >= M) return;
@@ -188,6 +194,155 @@ __global__ __launch_bounds__(256) void predict_rotations_kernel(const long long*
         float* w = omega + i * 3;
         w[0] = w0; w[1] = w1; w[2] = w2;
     }
+}
+
+__global__ __launch_bounds__(256) void predict_rotations_kernel(const long long* __restrict__ idx, const float* __restrict__ R,
+                                                                long r_batch_stride, const float* __restrict__ V,
+                                                                long v_batch_stride, long N, const key_t* __restrict__ best_key,
+                                                                long M, long n_fresh, unsigned long long seed,
+                                                                const long long* __restrict__ step, float sigma, float sigma_vel,
+                                                                float damping, float max_angle, float max_speed, int coast,
+                                                                float* __restrict__ out, float* __restrict__ vel_out,
+                                                                float* __restrict__ omega)
+{
+    predict_slot(idx, R, r_batch_stride, V, v_batch_stride, N, best_key, M, n_fresh, seed, step, sigma, sigma_vel, damping, max_angle,
+                 max_speed, coast, out, vel_out, omega);
+}
+
+// ---------------------------------------------------------------------------------
+// Noise scale and fresh slots decided on the device (ahv_predict_rotations_ctl_f32 / ahv_track_control_f32, include/ahv.h).
+// The control record of sample b is eight 32-bit words the caller owns; the predict step reads words 0-2 and the control step,
+// one launch after select_rotation, rewrites all eight from what the frame showed.
+// ---------------------------------------------------------------------------------
+struct TrackControl {
+    float sigma, sigma_vel;  // what the next predict step uses, radians
+    int n_fresh;             // its fresh slots; any int: a reader clamps to [0, M]
+    unsigned flags;          // kControlLost | kControlReacquired | kControlUpdated of the last decision
+    float m;                 // running per-axis variance of the motion, rad^2
+    float innovation;        // of the last decision, radians; NaN when not computed
+    float score;             // the MAP score the last decision saw
+    unsigned reserved;       // 0
+};
+static_assert(sizeof(TrackControl) == 4 * 8, "the record is AHV_TRACK_CONTROL_WORDS = 8 32-bit words (include/ahv.h)");
+constexpr unsigned kControlLost = 1u, kControlReacquired = 2u, kControlUpdated = 4u;
+
+// q(R) of a rotation matrix by Shepperd's branch, as compose_rotation_vector has it inline; unit up to rounding, either sign.
+// A second copy on purpose: with that function calling this one the compiler scheduled the three kernels that compose
+// differently (same instructions, another order), and their instruction sequences are pinned.
+__device__ __forceinline__ void rotation_quaternion(const float (&r)[9], float& qr, float& qi, float& qj, float& qk)
+{
+    const float tr = r[0] + r[4] + r[8];
+    if (tr > 0.0f) {
+        const float s = 2.0f * sqrtf(tr + 1.0f);
+        qr = 0.25f * s; qi = (r[7] - r[5]) / s; qj = (r[2] - r[6]) / s; qk = (r[3] - r[1]) / s;
+    } else if (r[0] > r[4] && r[0] > r[8]) {
+        const float s = 2.0f * sqrtf(1.0f + r[0] - r[4] - r[8]);
+        qr = (r[7] - r[5]) / s; qi = 0.25f * s; qj = (r[1] + r[3]) / s; qk = (r[2] + r[6]) / s;
+    } else if (r[4] > r[8]) {
+        const float s = 2.0f * sqrtf(1.0f + r[4] - r[0] - r[8]);
+        qr = (r[2] - r[6]) / s; qi = (r[1] + r[3]) / s; qj = 0.25f * s; qk = (r[5] + r[7]) / s;
+    } else {
+        const float s = 2.0f * sqrtf(1.0f + r[8] - r[0] - r[4]);
+        qr = (r[3] - r[1]) / s; qi = (r[2] + r[6]) / s; qj = (r[5] + r[7]) / s; qk = 0.25f * s;
+    }
+}
+
+__device__ __forceinline__ long clamp_fresh(int n_fresh, long M) { return n_fresh < 0 ? 0 : (n_fresh > M ? M : (long)n_fresh); }
+
+// The predict step with sigma, sigma_vel and n_fresh of sample blockIdx.y read from its record: the slot functions of the two
+// kernels above with those three values in the place of the launch arguments, so that a record holding the launch's values
+// gives that kernel's bytes.  kWalk: diffuse_rotations_kernel's slots (no velocities, no coast slot, vel_out not written).
+template <bool kWalk>
+__global__ __launch_bounds__(256) void predict_rotations_ctl_kernel(const long long* __restrict__ idx, const float* __restrict__ R,
+                                                                    long r_batch_stride, const float* __restrict__ V,
+                                                                    long v_batch_stride, long N, const key_t* __restrict__ best_key,
+                                                                    long M, const TrackControl* __restrict__ control,
+                                                                    unsigned long long seed, const long long* __restrict__ step,
+                                                                    float damping, float max_angle, float max_speed, int coast,
+                                                                    float* __restrict__ out, float* __restrict__ vel_out,
+                                                                    float* __restrict__ omega)
+{
+    const TrackControl* c = control + blockIdx.y;
+    const float sigma = c->sigma, sigma_vel = c->sigma_vel;
+    const long n_fresh = clamp_fresh(c->n_fresh, M);
+    if constexpr (kWalk)
+        diffuse_slot(idx, R, r_batch_stride, N, best_key, M, n_fresh, seed, step, sigma, max_angle, out, omega);
+    else
+        predict_slot(idx, R, r_batch_stride, V, v_batch_stride, N, best_key, M, n_fresh, seed, step, sigma, sigma_vel, damping,
+                     max_angle, max_speed, coast, out, vel_out, omega);
+}
+
+// The control step: one thread per sample, no LDS, no atomics.  In this order (include/ahv.h states the contract):
+//   nf          the record's n_fresh clamped to [0, M]: what the predict step of THIS frame used
+//   reacquired  idx >= max(M - nf, first): the winner sits in a fresh slot
+//   lost        !(score >= score_floor); a NaN score is lost
+//   a           the innovation: the angle between P, the pose slot 0 (the previous MAP pose, bit for bit) coasts to, and the
+//               winner R_cur[idx], as 2 atan2(|q_v|, |q_w|) of q = q(P)* q(R_cur[idx]) -- acos of a trace loses half the digits
+//               near 0, where sigma_min lives.  NaN for an idx outside [0, M) and for a non-finite angle.
+//   m           (1 - rate) m + rate a^2 / 3 unless lost, reacquired or a is NaN: a jump into a fresh slot is a re-acquisition, not
+//               motion, and a lost track's innovation means nothing
+//   sigma       lost ? sigma_max : clamp(gain sqrt(m), sigma_min, sigma_max); a NaN lands on sigma_min (fmaxf drops it)
+//   sigma_vel   sigma_vel0 (sigma / sigma0);  n_fresh  lost ? n_fresh_lost : n_fresh0
+__global__ __launch_bounds__(256) void track_control_kernel(const float* __restrict__ R_cur, const float* __restrict__ V_cur,
+                                                            const long long* __restrict__ idx, const float* __restrict__ score, int B,
+                                                            long M, long first, float sigma0, float sigma_vel0, int n_fresh0,
+                                                            float sigma_min, float sigma_max, float gain, float rate,
+                                                            float score_floor, int n_fresh_lost, TrackControl* __restrict__ control,
+                                                            unsigned char* __restrict__ reacquired)
+{
+    const int b = blockIdx.x * 256 + threadIdx.x;
+    if (b >= B) return;
+    const TrackControl c = control[b];
+    const long nf = clamp_fresh(c.n_fresh, M);
+    const long long i = idx[b];
+    const float s = score[b];
+    const bool reacq = i >= (M - nf > first ? M - nf : first);
+    const bool lost = !(s >= score_floor);
+    float a = __builtin_nanf("");
+    if (i >= 0 && i < M) {
+        const float* r0 = R_cur + (long)b * M * 9;
+        const float e[9] = {r0[0], r0[1], r0[2], r0[3], r0[4], r0[5], r0[6], r0[7], r0[8]};
+        float p[9];
+        if (V_cur) {
+            const float* v = V_cur + (long)b * M * 3;
+            compose_rotation_vector(e, v[0], v[1], v[2], p);
+        } else {
+#pragma unroll
+            for (int k = 0; k < 9; ++k) p[k] = e[k];
+        }
+        const float* rw = r0 + i * 9;
+        const float w[9] = {rw[0], rw[1], rw[2], rw[3], rw[4], rw[5], rw[6], rw[7], rw[8]};
+        float pr, pi, pj, pk, wr, wi, wj, wk;
+        rotation_quaternion(p, pr, pi, pj, pk);
+        rotation_quaternion(w, wr, wi, wj, wk);
+        // q(P)* q(R): Hamilton product with the first factor conjugated, the vector part as differences of paired products and
+        // with no contraction: each difference of equal factors is exactly 0, so a winner that holds slot 0's bytes (no V) has
+        // the innovation 0 and not a rounding residue of 1e-8.
+        float qr, qi, qj, qk;
+        {
+#pragma clang fp contract(off)
+            qr = pr * wr + pi * wi + pj * wj + pk * wk;
+            qi = (pr * wi - pi * wr) + (pk * wj - pj * wk);
+            qj = (pr * wj - pj * wr) + (pi * wk - pk * wi);
+            qk = (pr * wk - pk * wr) + (pj * wi - pi * wj);
+        }
+        const float ang = 2.0f * atan2f(sqrtf(qi * qi + qj * qj + qk * qk), fabsf(qr));
+        if (finite_f(ang)) a = ang;
+    }
+    const bool updated = !lost && !reacq && finite_f(a);
+    const float m = updated ? (1.0f - rate) * c.m + rate * (a * a * (1.0f / 3.0f)) : c.m;
+    const float sigma = lost ? sigma_max : fminf(fmaxf(gain * sqrtf(m), sigma_min), sigma_max);
+    TrackControl n;
+    n.sigma = sigma;
+    n.sigma_vel = sigma_vel0 * (sigma / sigma0);
+    n.n_fresh = lost ? n_fresh_lost : n_fresh0;
+    n.flags = (lost ? kControlLost : 0u) | (reacq ? kControlReacquired : 0u) | (updated ? kControlUpdated : 0u);
+    n.m = m;
+    n.innovation = a;
+    n.score = s;
+    n.reserved = 0u;
+    control[b] = n;
+    reacquired[b] = reacq ? 1 : 0;
 }
 
 // Start of a tracker step (ahv_track_advance): u[b] of step t + 1, then the counter itself.  One workgroup: the barrier
@@ -663,6 +818,34 @@ hipError_t launch_predict_rotations(const int64_t* idx, const float* R, int64_t 
                        reinterpret_cast<const key_t*>(best_key), (long)M, (long)n_fresh, (unsigned long long)seed,
                        reinterpret_cast<const long long*>(step), sigma, sigma_vel, damping, max_angle, max_speed, coast, out,
                        vel_out, omega);
+    return hipGetLastError();
+}
+
+hipError_t launch_predict_rotations_ctl(const int64_t* idx, const float* R, int64_t r_batch_stride, const float* V,
+                                        int64_t v_batch_stride, int64_t N, const int64_t* best_key, int64_t M, const uint32_t* control,
+                                        int B, uint64_t seed, const int64_t* step, float damping, float max_angle, float max_speed,
+                                        int coast, float* out, float* vel_out, float* omega, hipStream_t stream)
+{
+    const dim3 grid((unsigned)((M + 255) / 256), (unsigned)B);
+    const auto launch = [&](auto kernel) {
+        hipLaunchKernelGGL(kernel, grid, dim3(256), 0, stream, reinterpret_cast<const long long*>(idx), R, (long)r_batch_stride, V,
+                           (long)v_batch_stride, (long)N, reinterpret_cast<const key_t*>(best_key), (long)M,
+                           reinterpret_cast<const TrackControl*>(control), (unsigned long long)seed,
+                           reinterpret_cast<const long long*>(step), damping, max_angle, max_speed, coast, out, vel_out, omega);
+    };
+    if (vel_out) launch(predict_rotations_ctl_kernel<false>);
+    else launch(predict_rotations_ctl_kernel<true>);  // the walk: the caller passed neither V nor a coast slot
+    return hipGetLastError();
+}
+
+hipError_t launch_track_control(const float* R_cur, const float* V_cur, const int64_t* idx, const float* score, int B, int64_t M,
+                                int first, float sigma0, float sigma_vel0, int n_fresh0, float sigma_min, float sigma_max, float gain,
+                                float rate, float score_floor, int n_fresh_lost, uint32_t* control, uint8_t* reacquired,
+                                hipStream_t stream)
+{
+    hipLaunchKernelGGL(track_control_kernel, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, stream, R_cur, V_cur,
+                       reinterpret_cast<const long long*>(idx), score, B, (long)M, (long)first, sigma0, sigma_vel0, n_fresh0, sigma_min,
+                       sigma_max, gain, rate, score_floor, n_fresh_lost, reinterpret_cast<TrackControl*>(control), reacquired);
     return hipGetLastError();
 }
 

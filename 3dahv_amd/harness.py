@@ -237,7 +237,7 @@ def evaluate_category(cfg, model, sequences: Iterable[dict], num_frames: int = 2
 def track_sequence(model, item: dict, tracker, ref: int = 0, proposals: Optional[torch.Tensor] = None, device=None,
                    encoder_fn: Optional[Callable] = None, row_vector_R: bool = False, smoothed: bool = False,
                    marginals: bool = False, refs: Optional[Sequence[int]] = None, views_per_step: Optional[int] = None,
-                   max_view_angle_deg: Optional[float] = None) -> dict:
+                   max_view_angle_deg: Optional[float] = None, adapt=None) -> dict:
     """Track ONE sequence with a ``track.PoseTracker`` (batch 1).  ``item`` is what ``SyntheticSequences`` or
     ``co3d.Co3dSequences`` yields.  Frame ``ref`` is the reference view; every other frame is tracked in order: per frame the
     encoder runs on (reference, frame) -- ``encoder_fn`` or ``model.forward_features`` for ``layer4`` inputs, else ``model`` --,
@@ -270,7 +270,22 @@ def track_sequence(model, item: dict, tracker, ref: int = 0, proposals: Optional
     the other way round, (frame, reference): its rotation ``R_t^T R_v`` is ``Q A_v^T`` with ``Q = R_t^T`` and ``A_v = R_v^T``.
     Build the tracker with ``views=item["R"][refs].transpose(-1, -2)``; the frame's volume is then the one the scorer rotates,
     the reference's the target, the tracker's poses are ``R_t^T`` and ``err`` is taken against that.
-    ``refs=None``: the single-reference function above."""
+    ``refs=None``: the single-reference function above.
+    ``adapt`` (a tracker built with ``adapt=``; True, or the ``track.AdaptiveNoise`` the tracker was built with, whose settings
+    it must repeat): the result also has ``"control"``, the tracker's control record after every step decoded by
+    ``ops.decode_track_control`` -- ``sigma_deg``, ``sigma_vel_deg`` and ``n_fresh`` the NEXT frame uses, ``lost``, ``reacquired``,
+    ``updated``, ``innovation_deg`` and ``score`` of the frame, each ``(F,)`` with the row of the ``init`` frame holding the
+    fresh record; the records stay on the device until the end and cost a second host copy."""
+    if adapt is not None and adapt is not False:
+        rule = getattr(tracker, "adapt", None)
+        if rule is None:
+            raise RuntimeError("adapt= needs a tracker built with adapt=AdaptiveNoise(...)")
+        if adapt is not True and vars(adapt) != vars(rule):
+            raise RuntimeError("adapt = %r differs from the rule the tracker was built with, %r" % (vars(adapt), vars(rule)))
+        if refs is not None:
+            raise RuntimeError("adapt= together with refs= is not built")
+    else:
+        adapt = None
     if refs is not None:
         return _track_sequence_views(model, item, tracker, list(refs), proposals, device, encoder_fn, row_vector_R, smoothed,
                                      marginals, views_per_step, max_view_angle_deg)
@@ -294,10 +309,12 @@ def track_sequence(model, item: dict, tracker, ref: int = 0, proposals: Optional
         proposals = random_rotations(4096, generator=torch.Generator().manual_seed(0))
     proposals = proposals.to(device)
     order = [t for t in range(n) if t != ref]
-    R_map, score, err, truth = [], [], [], []
+    R_map, score, err, truth, records = [], [], [], [], []
     for k, t in enumerate(order):
         vol_src, vol_tgt = embed(frames[ref:ref + 1], frames[t:t + 1])
         res = tracker.init(vol_src, vol_tgt, proposals) if k == 0 else tracker.step(vol_src, vol_tgt)
+        if adapt is not None:
+            records.append(tracker.control_record[0].clone())
         R_gt = rots[ref].transpose(0, 1) @ rots[t] if row_vector_R else rots[t] @ rots[ref].transpose(0, 1)
         R_map.append(res.R_map[0].clone())          # (the tracker's outputs are buffers it reuses two steps later)
         score.append(res.score[0].clone())
@@ -305,7 +322,11 @@ def track_sequence(model, item: dict, tracker, ref: int = 0, proposals: Optional
         truth.append(R_gt)
     if not order:
         return {"frames": [], "R_map": torch.zeros(0, 3, 3), "score": torch.zeros(0), "err": torch.zeros(0)}
-    return _track_result(tracker, order, R_map, score, err, truth, smoothed, marginals)
+    out = _track_result(tracker, order, R_map, score, err, truth, smoothed, marginals)
+    if adapt is not None:
+        from . import ops
+        out["control"] = ops.decode_track_control(torch.stack(records))._asdict()
+    return out
 
 
 def _track_result(tracker, order, R_map, score, err, truth, smoothed, marginals) -> dict:

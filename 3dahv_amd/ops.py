@@ -17,6 +17,7 @@ to torch's current stream.  The plain ops carry no autograd graph; the ``*_autog
 from __future__ import annotations
 
 import collections
+import functools
 import contextvars
 import math
 import struct
@@ -1401,6 +1402,162 @@ def predict_rotations(R: torch.Tensor, V: torch.Tensor | None = None, idx: torch
           n_fresh, B, int(seed) & (2**64 - 1), step.data_ptr(), sigma, sigma_vel, damping, max_angle, max_speed,
           1 if coast else 0, out.data_ptr(), vel_out.data_ptr(), omega.data_ptr() if omega is not None else None)
     return (out, vel_out, omega) if omega is not None else (out, vel_out)
+
+
+# ---- noise scale and fresh slots adapted on the device ---------------------------------------------------------------
+# The control record (``ahv_track_control_f32`` / ``ahv_predict_rotations_ctl_f32``, include/ahv.h): ``(B,8)`` int32 words on the
+# device.  ``track_control`` decides sigma, sigma_vel and n_fresh of the next frame from the innovation and the score of this
+# one, ``predict_rotations_controlled`` reads them there; nothing crosses to the host, so both live inside a captured step.
+
+TrackControl = collections.namedtuple(
+    "TrackControl", ["sigma_deg", "sigma_vel_deg", "n_fresh", "lost", "reacquired", "updated", "innovation_deg", "score"])
+
+
+def _control_record(control, B: int, dev) -> torch.Tensor:
+    W = _lib.AHV_TRACK_CONTROL_WORDS
+    if (not isinstance(control, torch.Tensor) or control.dtype != torch.int32 or tuple(control.shape) != (B, W)
+            or not control.is_contiguous() or control.device != dev):
+        raise RuntimeError("control must be a contiguous int32 (B, %d) = (%d, %d) tensor on %s (track_control_state)"
+                           % (W, B, W, dev))
+    return control
+
+
+def track_control_state(B: int, sigma_deg: float, sigma_vel_deg: float, n_fresh: int, device) -> torch.Tensor:
+    """A fresh control record ``(B,8)`` int32 on ``device``: ``sigma_deg``, ``sigma_vel_deg`` (radians, fp32) and ``n_fresh`` in
+    words 0-2, no flags, ``m = sigma^2``, NaN for the innovation and the score.  Built on the host and copied: not for the
+    inside of a captured step (``PoseTracker.init`` copies one into the record it owns)."""
+    B = int(B)
+    if not 1 <= B <= 65535:
+        raise RuntimeError("B = %d outside 1..65535" % B)
+    sigma, sigma_vel = _angle_rad(sigma_deg, "sigma_deg"), _angle_rad(sigma_vel_deg, "sigma_vel_deg")
+    if int(n_fresh) < 0:
+        raise RuntimeError("n_fresh = %d must be >= 0" % int(n_fresh))
+    f = torch.tensor([sigma, sigma_vel, 0.0, 0.0, sigma, float("nan"), float("nan"), 0.0], dtype=torch.float32)
+    f[4] = f[4] * f[4]
+    rec = f.view(torch.int32).clone()
+    rec[2], rec[3], rec[7] = int(n_fresh), 0, 0
+    return rec[None].repeat(B, 1).to(device)
+
+
+def decode_track_control(control: torch.Tensor) -> TrackControl:
+    """The record as a ``TrackControl`` of ``(B,)`` tensors ON THE HOST: ``sigma_deg``, ``sigma_vel_deg`` (float32),
+    ``n_fresh`` (int32), ``lost``, ``reacquired``, ``updated`` (bool), ``innovation_deg`` (NaN when none was computed) and
+    ``score``.  It copies the record to the host, which synchronises: for logging and tests, not for the inside of a step."""
+    W = _lib.AHV_TRACK_CONTROL_WORDS
+    if not isinstance(control, torch.Tensor) or control.dtype != torch.int32 or control.dim() != 2 or control.shape[1] != W:
+        raise RuntimeError("control must be an int32 (B, %d) tensor, got %s"
+                           % (W, tuple(control.shape) if isinstance(control, torch.Tensor) else type(control)))
+    rec = control.detach().cpu().contiguous()
+    f = rec.view(torch.float32)
+    flags = rec[:, 3]
+    bit = lambda mask: (flags & mask) != 0
+    return TrackControl(torch.rad2deg(f[:, 0]), torch.rad2deg(f[:, 1]), rec[:, 2].clone(), bit(_lib.AHV_TRACK_LOST),
+                        bit(_lib.AHV_TRACK_REACQUIRED), bit(_lib.AHV_TRACK_UPDATED), torch.rad2deg(f[:, 5]), f[:, 6].clone())
+
+
+@functools.lru_cache(maxsize=64)
+def _control_params(first, sigma_deg, sigma_vel_deg, n_fresh, sigma_min_deg, sigma_max_deg, gain, rate, score_floor, n_fresh_lost, M):
+    """The by-value arguments of ``ahv_track_control_f32``, checked: ``(first, sigma0, sigma_vel0, n_fresh0, sigma_min, sigma_max,
+    gain, rate, score_floor, n_fresh_lost)``, angles in fp32 radians.  Cached: a tracker passes the same eleven values every
+    step, and the eager step is bound by the host."""
+    if int(first) not in (1, 2):
+        raise RuntimeError("first = %r must be 1, or 2 with a coast slot" % (first,))
+    sigma0, sigma_vel0 = _angle_rad(sigma_deg, "sigma_deg"), _angle_rad(sigma_vel_deg, "sigma_vel_deg")
+    smin, smax = _angle_rad(sigma_min_deg, "sigma_min_deg"), _angle_rad(sigma_max_deg, "sigma_max_deg")
+    if not sigma0 > 0.0:
+        raise RuntimeError("sigma_deg = %r must be > 0 (sigma_vel follows sigma / sigma_deg)" % (sigma_deg,))
+    if not 0.0 < smin <= smax:
+        raise RuntimeError("sigma_min_deg = %r and sigma_max_deg = %r: need 0 < sigma_min <= sigma_max" % (sigma_min_deg, sigma_max_deg))
+    gain, rate = float(gain), float(rate)
+    if not (gain > 0.0 and math.isfinite(gain)):
+        raise RuntimeError("gain = %r must be finite and > 0" % (gain,))
+    if not 0.0 < rate <= 1.0:
+        raise RuntimeError("rate = %r outside (0, 1]" % (rate,))
+    floor = -math.inf if score_floor is None else float(score_floor)
+    if math.isnan(floor):
+        raise RuntimeError("score_floor is NaN (None: no floor)")
+    n_fresh = int(n_fresh)
+    n_lost = n_fresh if n_fresh_lost is None else int(n_fresh_lost)
+    for name, n in (("n_fresh", n_fresh), ("n_fresh_lost", n_lost)):
+        if not 0 <= n <= M:
+            raise RuntimeError("%s = %d outside 0..M = %d" % (name, n, M))
+    return int(first), sigma0, sigma_vel0, n_fresh, smin, smax, gain, rate, floor, n_lost
+
+
+@torch.no_grad()
+def track_control(control: torch.Tensor, R: torch.Tensor, idx: torch.Tensor, score: torch.Tensor, V: torch.Tensor | None = None,
+                  first: int = 1, sigma_deg: float = 3.0, sigma_vel_deg: float = 1.0, n_fresh: int = 0,
+                  sigma_min_deg: float = 0.5, sigma_max_deg: float = 8.0, gain: float = 1.5, rate: float = 0.5,
+                  score_floor: float | None = None, n_fresh_lost: int | None = None, reacquired: torch.Tensor | None = None):
+    """The decision of an adaptive tracker step (``ahv_track_control_f32``, one launch, after ``select_rotation``): from the
+    step's particle set ``R (B,M,3,3)``, its velocities ``V (B,M,3)`` or None, the winner's slot ``idx (B,)`` int64 and its
+    ``score (B,)``, rewrite ``control (B,8)`` in place.  The innovation ``a`` is the angle between the winner and the pose slot
+    0 -- the previous MAP pose -- coasts to; ``lost = not score >= score_floor`` (None: no floor), ``reacquired = idx >=
+    max(M - n_fresh used this frame, first)``; ``m <- (1 - rate) m + rate a^2 / 3`` unless lost or reacquired; the next frame's
+    ``sigma = clamp(gain sqrt(m), sigma_min, sigma_max)`` (``sigma_max`` when lost), ``sigma_vel = sigma_vel_deg sigma /
+    sigma_deg`` and ``n_fresh`` (``n_fresh_lost`` when lost; None: ``n_fresh``).  ``sigma_deg``, ``sigma_vel_deg`` and
+    ``n_fresh`` are the tracker's constants; ``first`` is 1, or 2 with a coast slot.  Returns ``reacquired (B,)`` bool (pass one
+    to allocate nothing).  Nothing is read on the host."""
+    if not isinstance(R, torch.Tensor) or R.dim() != 4 or tuple(R.shape[2:]) != (3, 3):
+        raise RuntimeError("R must be (B,M,3,3), got %s" % (tuple(R.shape) if isinstance(R, torch.Tensor) else type(R),))
+    dev = _need_gpu(R, score) if V is None else _need_gpu(R, score, V)
+    B, M = R.shape[0], _draws(R.shape[1])
+    if not 1 <= B <= 65535:
+        raise RuntimeError("B = %d outside 1..65535" % B)
+    if V is not None and (tuple(V.shape) != (B, M, 3) or not V.is_contiguous()):
+        raise RuntimeError("V must be a contiguous (B,M,3) = (%d,%d,3) tensor, got %s" % (B, M, tuple(V.shape)))
+    if tuple(score.shape) != (B,) or not score.is_contiguous():
+        raise RuntimeError("score must be a contiguous (B,) = (%d,) tensor, got %s" % (B, tuple(score.shape)))
+    if (not isinstance(idx, torch.Tensor) or idx.dtype != torch.int64 or tuple(idx.shape) != (B,) or not idx.is_contiguous()
+            or idx.device != dev):
+        raise RuntimeError("idx must be a contiguous int64 (B,) = (%d,) tensor on %s" % (B, dev))
+    control = _control_record(control, B, dev)
+    first, sigma0, sigma_vel0, n_fresh, smin, smax, gain, rate, floor, n_lost = _control_params(
+        first, sigma_deg, sigma_vel_deg, n_fresh, sigma_min_deg, sigma_max_deg, gain, rate, score_floor, n_fresh_lost, M)
+    if reacquired is None:
+        reacquired = torch.empty((B,), dtype=torch.bool, device=dev)
+    elif (not isinstance(reacquired, torch.Tensor) or reacquired.dtype != torch.bool or tuple(reacquired.shape) != (B,)
+          or not reacquired.is_contiguous() or reacquired.device != dev):
+        raise RuntimeError("reacquired must be a contiguous bool (B,) = (%d,) tensor on %s" % (B, dev))
+    Rc = R if R.is_contiguous() else R.contiguous()
+    _call(dev, "ahv_track_control_f32", Rc.data_ptr(), V.data_ptr() if V is not None else None, idx.data_ptr(), score.data_ptr(), B,
+          M, int(first), sigma0, sigma_vel0, n_fresh, smin, smax, gain, rate, floor, n_lost, control.data_ptr(),
+          reacquired.data_ptr())
+    return reacquired
+
+
+@torch.no_grad()
+def predict_rotations_controlled(R: torch.Tensor, control: torch.Tensor, V: torch.Tensor | None = None,
+                                 idx: torch.Tensor | None = None, m: int | None = None, damping: float = 1.0,
+                                 step: torch.Tensor | None = None, seed: int = 0, best_key: torch.Tensor | None = None,
+                                 coast: bool = False, max_angle_deg: float | None = None, max_speed_deg: float | None = None,
+                                 out: torch.Tensor | None = None, vel_out: torch.Tensor | None = None, velocities: bool = True,
+                                 want_omega: bool = False, omega_out: torch.Tensor | None = None):
+    """``predict_rotations`` with ``sigma``, ``sigma_vel`` and ``n_fresh`` read ON THE DEVICE, per sample, from ``control (B,8)``
+    (``ahv_predict_rotations_ctl_f32``, one launch): a replayed graph follows the record.  For a record that holds the same
+    three values in every sample the outputs are the bytes of ``predict_rotations`` with them.  ``velocities=False`` (then no
+    ``V``, no ``vel_out``, no ``coast``) is the random walk: the bytes of ``diffuse_rotations``, and only ``out`` (or ``(out,
+    omega)``) is returned.  Other arguments and results as ``predict_rotations``."""
+    dev, step, B, M, N, rstride, vstride, _ = _predict_args(R, idx, m, step, best_key, 0, V)
+    control = _control_record(control, B, dev)
+    damping = _unit_interval(damping, "damping")
+    max_angle = _angle_rad(max_angle_deg, "max_angle_deg", allow_none=True)
+    max_speed = _angle_rad(max_speed_deg, "max_speed_deg", allow_none=True)
+    _check_best_key(best_key, B, dev)
+    if not velocities and (V is not None or vel_out is not None or coast):
+        raise RuntimeError("velocities=False is the random walk: it takes no V, no vel_out and no coast slot")
+    out = _output(out, "out", (B, M, 3, 3), dev)
+    vel_out = _output(vel_out, "vel_out", (B, M, 3), dev, wanted=velocities)
+    omega = _output(omega_out, "omega_out", (B, M, 3), dev, wanted=want_omega)
+    Rc = R.detach().contiguous()
+    Vc = V.detach().contiguous() if V is not None else None
+    _refuse_overlap(((Rc, "R"), (Vc, "V")), (("out", out), ("vel_out", vel_out), ("omega_out", omega)))
+    ptr = lambda t: t.data_ptr() if t is not None else None
+    _call(dev, "ahv_predict_rotations_ctl_f32", ptr(idx), Rc.data_ptr(), rstride, ptr(Vc), vstride, N, ptr(best_key), M,
+          control.data_ptr(), B, int(seed) & (2**64 - 1), step.data_ptr(), damping, max_angle, max_speed, 1 if coast else 0,
+          out.data_ptr(), ptr(vel_out), ptr(omega))
+    res = (out,) + ((vel_out,) if velocities else ()) + ((omega,) if omega is not None else ())
+    return res[0] if len(res) == 1 else res
 
 
 # ---- trajectory smoothing ------------------------------------------------------------------------------------------

@@ -45,7 +45,13 @@ degrees, the limit ``fuse_view_scores`` cites), so past that range a single-refe
 ``Q A_v^T``), and per step it picks, on the device, the ``views_per_step`` views nearest the previous MAP pose
 (``nearest_views``), stages their volumes (``gather_views``) and scores the set against those alone, fused under the angle
 limit (``verify_views_staged``) -- all inside the captured chain, with no host read.
-Not built: sigma adapted from the entropy, per-view weights other than present / absent and per-particle view selection inside
+A constant ``sigma_deg`` is wrong for a pose whose speed changes: too narrow and the cloud is left behind, too wide and every
+slow frame pays for it, and after an abrupt change of pose a fixed tracker may never find the object again.  ``adapt=
+AdaptiveNoise(...)`` lets the device decide: one launch after ``select_rotation`` (``track_control``) measures the innovation --
+how far the MAP pose landed from where the previous one predicted it -- and the MAP score, and writes the next frame's sigma,
+sigma_vel and n_fresh into a control record the predict step (``predict_rotations_controlled``) reads.  Not the entropy: this
+filter resamples every step, so the weights of a converged cloud are as flat as those of a lost one.
+Not built: adaptation together with views or symmetry and of the smoothers' transition scale, per-view weights other than present / absent and per-particle view selection inside
 the tracker, the compact multi-view path inside the tracker, symmetry together with views, a fixed-lag marginal
 inside the captured step, the velocity-noise term of the constant-velocity transition (the smoother's transition is
 pose-only), and symmetry-aware transitions inside the smoothers (the fold makes them unnecessary for a tracked cloud).
@@ -64,6 +70,32 @@ from .dist import KEY_EMPTY
 TrackStep = collections.namedtuple(
     "TrackStep", ["score", "idx", "R_map", "particles", "scores", "draws", "R_mean", "spread_deg", "mode_mass", "entropy",
                   "reacquired"])
+
+
+class AdaptiveNoise:
+    """The rule ``PoseTracker(adapt=...)`` runs on the device per step (``ops.track_control``): the running per-axis variance of
+    the motion ``m <- (1 - rate) m + rate a^2 / 3`` from the innovation ``a``, the next frame's ``sigma = clamp(gain sqrt(m),
+    sigma_min_deg, sigma_max_deg)``, and below ``score_floor`` (None: never) a lost track: ``sigma_max_deg`` and
+    ``n_fresh_lost`` fresh slots (None: the tracker's ``n_fresh``).  ``gain`` is above 1 because the innovation of a cloud that
+    lags under-estimates the motion: at 1.0 the tracker loses an accelerating sequence that 1.5 holds."""
+
+    def __init__(self, sigma_min_deg: float = 0.5, sigma_max_deg: float = 8.0, gain: float = 1.5, rate: float = 0.5,
+                 score_floor: Optional[float] = None, n_fresh_lost: Optional[int] = None):
+        self.sigma_min_deg, self.sigma_max_deg = float(sigma_min_deg), float(sigma_max_deg)
+        if not 0.0 < ops._angle_rad(self.sigma_min_deg, "sigma_min_deg") <= ops._angle_rad(self.sigma_max_deg, "sigma_max_deg"):
+            raise RuntimeError("sigma_min_deg = %r and sigma_max_deg = %r: need 0 < sigma_min <= sigma_max"
+                               % (sigma_min_deg, sigma_max_deg))
+        self.gain, self.rate = float(gain), float(rate)
+        if not (self.gain > 0.0 and math.isfinite(self.gain)):
+            raise RuntimeError("gain = %r must be finite and > 0" % (gain,))
+        if not 0.0 < self.rate <= 1.0:
+            raise RuntimeError("rate = %r outside (0, 1]" % (rate,))
+        self.score_floor = None if score_floor is None else float(score_floor)
+        if self.score_floor is not None and math.isnan(self.score_floor):
+            raise RuntimeError("score_floor is NaN (None: no floor)")
+        self.n_fresh_lost = None if n_fresh_lost is None else int(n_fresh_lost)
+        if self.n_fresh_lost is not None and self.n_fresh_lost < 0:
+            raise RuntimeError("n_fresh_lost = %d must be >= 0" % self.n_fresh_lost)
 
 
 class PoseTracker:
@@ -132,6 +164,16 @@ class PoseTracker:
     changed since the capture; ``view_inputs`` are the static ``(B,V,...)`` inputs of the first kind, ``buffers`` of the second.
     ``symmetry=`` together with ``views`` is refused.  ``views=None``: the previous tracker, call for call.
 
+    ``adapt=AdaptiveNoise(...)`` (``backend`` then also provides ``predict_rotations_controlled`` and ``track_control``; refused
+    at construction otherwise, and together with ``views=`` or ``symmetry=``: not built): the tracker owns one control record
+    ``(B,8)`` (``control_record``; ``control()`` decodes it on the host), which ``init`` resets to ``sigma_deg``,
+    ``sigma_vel_deg`` and ``n_fresh``.  A step is ``track_advance`` -> ``resample`` -> ``predict_rotations_controlled`` (sigma,
+    sigma_vel and n_fresh read from the record on the device; in the place of ``diffuse_rotations`` / ``predict_rotations``) ->
+    ``verify_pair`` -> ``select_rotation`` -> ``track_control`` (in the place of the comparison that computes ``reacquired``; it
+    writes the same buffer and the record of the next frame).  Posterior and smoothers follow unchanged; the ring's scale stays
+    a constant, so with ``history`` ``smooth_sigma_deg`` must be given.  With ``use_graph=True`` all of it sits inside the
+    captured chain and a replay follows the record.  ``adapt=None``: the previous tracker, call for call.
+
     ``use_graph=True`` (HIP backend only; refused with a ``backend`` or on the CPU): the first step after ``init`` reads the N0-sized set and runs eagerly; the two halves of
     the ping-pong are then captured as one hipGraph each, by the second and the third step, and every later step replays the
     graph of its half.  Each graph is the linear chain of the step's launches.  The two capturing steps synchronise with the
@@ -145,9 +187,21 @@ class PoseTracker:
                  motion: str = "walk", sigma_vel_deg: float = 1.0, damping: float = 1.0, max_speed_deg: Optional[float] = None,
                  coast: bool = True, history: int = 0, smooth_sigma_deg: Optional[float] = None, smooth_jump: float = 8.0,
                  marginals: bool = False, symmetry=None, views: Optional[torch.Tensor] = None,
-                 views_per_step: Optional[int] = None, max_view_angle_deg: Optional[float] = None):
+                 views_per_step: Optional[int] = None, max_view_angle_deg: Optional[float] = None,
+                 adapt: Optional[AdaptiveNoise] = None):
         dev = W1.device
         self.ops = ops if backend is None else backend
+        self.adapt = adapt
+        if adapt is not None:
+            if not isinstance(adapt, AdaptiveNoise):
+                raise RuntimeError("adapt must be an AdaptiveNoise or None, got %s" % type(adapt).__name__)
+            if views is not None or symmetry is not None:
+                raise RuntimeError("adapt= together with views= or symmetry= is not built")
+            if not all(hasattr(self.ops, n) for n in ("predict_rotations_controlled", "track_control")):
+                raise RuntimeError("adapt= needs a backend that provides predict_rotations_controlled and track_control")
+            if history and smooth_sigma_deg is None:
+                raise RuntimeError("adapt= with history: give smooth_sigma_deg (the ring's scale stays a constant; it does not "
+                                   "follow the adapted sigma)")
         self.symmetry = symmetry
         self.views = None
         if views is None:
@@ -194,6 +248,12 @@ class PoseTracker:
         ops._unit_interval(self.damping, "damping")
         self.temperature = float(temperature)
         ops.inverse_temperature(self.temperature)     # raises unless finite and > 0
+        if adapt is not None:
+            if not self.sigma_deg > 0.0:
+                raise RuntimeError("adapt= needs sigma_deg > 0 (sigma_vel follows sigma / sigma_deg), got %r" % (sigma_deg,))
+            self._n_fresh_lost = self.n_fresh if adapt.n_fresh_lost is None else adapt.n_fresh_lost
+            if not 0 <= self._n_fresh_lost <= self.M:
+                raise RuntimeError("n_fresh_lost = %d outside 0..particles = %d" % (self._n_fresh_lost, self.M))
         self.history = int(history)
         if self.history != 0 and not 2 <= self.history < (1 << 31):
             raise RuntimeError("history = %d: 0 (no smoothing) or at least 2 frames" % self.history)
@@ -237,6 +297,10 @@ class PoseTracker:
         # the smoother's ring (any backend: plain tensors); after init the counter is 0 and the first step records frame 1
         self._hist = ops.smooth_history(B, M, self.history, dev, velocities=motion != "walk") if self.history else None
         self._marg = ops.marginal_history(B, M, self.history, dev) if self.marginals else None
+        # the control record (adapt): what the next predict step reads; init copies _ctl0 into it
+        self._ctl0 = ops.track_control_state(B, self.sigma_deg, self.sigma_vel_deg if motion != "walk" else 0.0, self.n_fresh,
+                                             dev) if adapt is not None else None
+        self._ctl = self._ctl0.clone() if adapt is not None else None
         self._cur = None      # (R, scores, key) of the set the next step draws from
         self._anchor = None   # (B,3,3): the previous frame's MAP pose, the anchor of the fold (symmetry)
         self._n = 0           # steps since init
@@ -286,6 +350,18 @@ class PoseTracker:
         return self._vsel
 
     @property
+    def control_record(self) -> Optional[torch.Tensor]:
+        """The raw control record ``(B,8)`` int32 (``adapt``; None without): what the next step's predict reads."""
+        return self._ctl
+
+    def control(self):
+        """The control record decoded ON THE HOST (``ops.decode_track_control``: it synchronises): sigma, sigma_vel and n_fresh
+        of the next step, and lost / reacquired / updated, the innovation and the score of the last one."""
+        if self._ctl is None:
+            raise RuntimeError("control() needs a tracker built with adapt=")
+        return ops.decode_track_control(self._ctl)
+
+    @property
     def step_counter(self) -> torch.Tensor:
         """The int64 device counter (one element): 0 after ``init``, moved by one per step ON THE DEVICE."""
         return self._step
@@ -324,6 +400,8 @@ class PoseTracker:
         if self.ops is ops and R0.is_cuda and (self._ws0 is None or self._ws0_n != n0):
             self._ws0, self._ws0_n = ops.resample_workspace(self.B, n0, R0.device), n0
         self._step.zero_()
+        if self._ctl is not None:
+            self._ctl.copy_(self._ctl0)
         self._cur, self._n, self._vel = (R0, scores, key), 0, None
         self._anchor = R_map   # the pose the next step folds around (symmetry)
         post = self._posterior(scores, R0, R_map)
@@ -337,7 +415,15 @@ class PoseTracker:
         u = o.track_advance(self._step, self.seed, self.B, u=self._u)
         draws = o.resample(s_prev, self.M, self.temperature, u=u, out=self._draws, workspace=ws)
         first = 1
-        if self.motion == "walk":
+        if self.adapt is not None:   # sigma, sigma_vel and n_fresh come from the record, on the device
+            cv = self.motion != "walk"
+            first = 2 if cv and self.coast else 1
+            R = o.predict_rotations_controlled(R_prev, self._ctl, self._vel, idx=draws, damping=self.damping if cv else 1.0,
+                                               step=self._step, seed=self.seed, best_key=key_prev, coast=cv and self.coast,
+                                               max_angle_deg=self.max_angle_deg, max_speed_deg=self.max_speed_deg if cv else None,
+                                               out=self._R[p], vel_out=self._V[p] if cv else None, velocities=cv)
+            R = R[0] if cv else R
+        elif self.motion == "walk":
             R = o.diffuse_rotations(R_prev, idx=draws, sigma_deg=self.sigma_deg, step=self._step, seed=self.seed,
                                     best_key=key_prev, n_fresh=self.n_fresh, max_angle_deg=self.max_angle_deg, out=self._R[p])
         else:
@@ -358,7 +444,15 @@ class PoseTracker:
                                                 scores_out=self._scores[p], best_key=self._keys[p], reset_best=True)
         score, idx, R_map = o.select_rotation(key, R, out=self._sel[p])
         # the winner sits in a fresh slot (slot 0 is the elite, and slot 1 the coasting one, even when every slot is fresh)
-        reacq = torch.ge(idx, max(self.M - self.n_fresh, first), out=self._reacq[p])
+        if self.adapt is None:
+            reacq = torch.ge(idx, max(self.M - self.n_fresh, first), out=self._reacq[p])
+        else:   # the same comparison against the n_fresh this frame used, and the record of the next frame
+            a = self.adapt
+            reacq = o.track_control(self._ctl, R, idx, score, V=self._V[p] if self._V is not None else None, first=first,
+                                    sigma_deg=self.sigma_deg, sigma_vel_deg=self.sigma_vel_deg if self._V is not None else 0.0,
+                                    n_fresh=self.n_fresh, sigma_min_deg=a.sigma_min_deg, sigma_max_deg=a.sigma_max_deg, gain=a.gain,
+                                    rate=a.rate, score_floor=a.score_floor, n_fresh_lost=self._n_fresh_lost,
+                                    reacquired=self._reacq[p])
         post = self._posterior(scores, R, R_map, self._pstate, self._pws)
         if self._hist is not None:   # observes the step, changes none of its outputs
             o.smooth_step(self._hist, R, scores, self._step, self.temperature, self.smooth_sigma_deg, jump=self.smooth_jump,
