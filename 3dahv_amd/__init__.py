@@ -14,7 +14,7 @@ generation, host logic tests) never touch the GPU library.
 import importlib as _importlib
 
 __version__ = "0.1.0"
-_SUBMODULES = ("rotations", "_lib", "ops", "aligner", "estimator", "dist", "harness", "checkpoint", "patch", "deferred", "refine", "co3d", "track")
+_SUBMODULES = ("rotations", "_lib", "ops", "aligner", "estimator", "dist", "harness", "checkpoint", "patch", "deferred", "refine", "co3d", "track", "posegraph")
 
 
 def __getattr__(name):

@@ -34,6 +34,9 @@ AHV_VIEW_SLOT_EXCLUDED = -1
 AHV_VIEW_SLOT_OVERFLOW = -2
 AHV_GATHER_BROADCAST = 1
 AHV_TRACK_CONTROL_WORDS = 8
+AHV_GRAPH_MAX_NODES = 16
+AHV_GRAPH_MAX_EDGES = 256
+AHV_GRAPH_EDGE_OUTGOING = 1 << 30
 AHV_TRACK_LOST, AHV_TRACK_REACQUIRED, AHV_TRACK_UPDATED = 1, 2, 4
 
 _vp = ctypes.c_void_p
@@ -130,6 +133,14 @@ SIGNATURES["ahv_fuse_view_scores_compact_f32"] = (_int, [_vp, _vp, _vp, _int, _i
 SIGNATURES["ahv_nearest_views_f32"] = (_int, [_vp, _vp, _int, _int, _int, _vp, _vp, _vp])
 # (src, view_idx: int32 or NULL with AHV_GATHER_BROADCAST, B, V, K, L, dst, flags, stream)
 SIGNATURES["ahv_gather_views_f32"] = (_int, [_vp, _vp, _int, _int, _int, _i64, _vp, _u32, _vp])
+# (pair_R, pair_score, edges: int32 [E][2], B, V, E, root, A, parent_edge: int32, reached: int32, stream)
+SIGNATURES["ahv_pose_graph_init_f32"] = (_int, [_vp, _vp, _vp, _int, _int, _int, _int, _vp, _vp, _vp, _vp])
+# (A, pair_R, pair_score, edges, incident: int32 [D], B, V, E, k, D, N, n_fresh, seed, counter: DEVICE int64 or NULL, sweep, sigma_rad,
+#  Q, Rrel, stream)
+SIGNATURES["ahv_pose_graph_propose_f32"] = (_int, [_vp] * 5 + [_int] * 5 + [_i64, _i64, ctypes.c_uint64, _vp, _int, ctypes.c_float,
+                                                   _vp, _vp, _vp])
+# (key, Q, B, V, k, N, A, node_score, stream)
+SIGNATURES["ahv_pose_graph_commit_f32"] = (_int, [_vp, _vp, _int, _int, _int, _i64, _vp, _vp, _vp])
 SIGNATURES["ahv_resample_workspace_bytes"] = (ctypes.c_size_t, [_int, _i64])
 # (scores, B, N, beta, M, u: DEVICE floats or NULL, idx, workspace, workspace_bytes, flags, stream)
 SIGNATURES["ahv_resample_f32"] = (_int, [_vp, _int, _i64, ctypes.c_float, _i64, _vp, _vp, _vp, ctypes.c_size_t, _u32, _vp])

@@ -77,6 +77,11 @@ hipError_t launch_marginal_step(const float*, const float*, const int64_t*, int6
                                 const float*, const float*, float*, float*, hipStream_t);
 hipError_t launch_marginal_smooth(const float*, const float*, const float*, const float*, const int64_t*, int64_t, int, int64_t,
                                   int64_t, int64_t, float, float, float*, int64_t*, float*, hipStream_t);
+hipError_t launch_pose_graph_init(const float*, const float*, const int32_t*, int, int, int, int, float*, int32_t*, int32_t*,
+                                  hipStream_t);
+hipError_t launch_pose_graph_propose(const float*, const float*, const float*, const int32_t*, const int32_t*, int, int, int, int, int,
+                                     int64_t, int64_t, uint64_t, const int64_t*, int, float, float*, float*, hipStream_t);
+hipError_t launch_pose_graph_commit(const int64_t*, const float*, int, int, int, int64_t, float*, float*, hipStream_t);
 hipError_t launch_score_backward(const float*, const float*, const float*, int64_t, const float*, const float*,
                                  const float*, int, int64_t, const float*, float*, float*, float*, float*, float*,
                                  float*, float*, int, hipStream_t, bool);
@@ -893,6 +898,77 @@ int ahv_gather_views_f32(const float* src, const int32_t* view_idx, int B, int V
         return fail(AHV_EINVAL, "gather_views: src and dst must be 16-byte aligned (the rows move as 16-byte words)");
     hipError_t e = ahv::launch_gather_views(src, view_idx, B, V, K, L / 4, dst, broadcast, static_cast<hipStream_t>(stream));
     if (e != hipSuccess) return hip_fail("gather_views: launch", e);
+    return AHV_OK;
+}
+
+// ---- joint pose inference over an unposed image set --------------------------------------------------------------------
+static int graph_sizes(const char* who, int B, int V)
+{
+    if (V < 2 || V > AHV_GRAPH_MAX_NODES) return fail(AHV_EINVAL, "%s: V = %d outside 2..%d", who, V, AHV_GRAPH_MAX_NODES);
+    if (B < 1 || B > 65535) return fail(AHV_EINVAL, "%s: B = %d outside 1..65535", who, B);
+    return AHV_OK;
+}
+
+static int graph_edges(const char* who, int E)
+{
+    if (E < 1 || E > AHV_GRAPH_MAX_EDGES) return fail(AHV_EINVAL, "%s: E = %d outside 1..%d", who, E, AHV_GRAPH_MAX_EDGES);
+    return AHV_OK;
+}
+
+static int graph_node(const char* who, const char* what, int k, int V)
+{
+    if (k < 0 || k >= V) return fail(AHV_EINVAL, "%s: %s = %d outside 0..V-1 = %d", who, what, k, V - 1);
+    return AHV_OK;
+}
+
+int ahv_pose_graph_init_f32(const float* pair_R, const float* pair_score, const int32_t* edges, int B, int V, int E, int root,
+                            float* A, int32_t* parent_edge, int32_t* reached, void* stream)
+{
+    if (int rc = graph_sizes("pose_graph_init", B, V)) return rc;
+    if (int rc = graph_edges("pose_graph_init", E)) return rc;
+    if (int rc = graph_node("pose_graph_init", "root", root, V)) return rc;
+    if (!pair_R || !pair_score || !edges || !A || !parent_edge || !reached) return fail(AHV_EINVAL, "pose_graph_init: null pointer");
+    hipError_t e = ahv::launch_pose_graph_init(pair_R, pair_score, edges, B, V, E, root, A, parent_edge, reached,
+                                               static_cast<hipStream_t>(stream));
+    if (e != hipSuccess) return hip_fail("pose_graph_init: launch", e);
+    return AHV_OK;
+}
+
+int ahv_pose_graph_propose_f32(const float* A, const float* pair_R, const float* pair_score, const int32_t* edges,
+                               const int32_t* incident, int B, int V, int E, int k, int D, int64_t N, int64_t n_fresh, uint64_t seed,
+                               const int64_t* counter, int sweep, float sigma_rad, float* Q, float* Rrel, void* stream)
+{
+    if (int rc = graph_sizes("pose_graph_propose", B, V)) return rc;
+    if (int rc = graph_edges("pose_graph_propose", E)) return rc;
+    if (int rc = graph_node("pose_graph_propose", "k", k, V)) return rc;
+    if (D < 1 || D > AHV_VIEWS_MAX)
+        return fail(AHV_EINVAL, "pose_graph_propose: D = %d outside 1..%d (the fuse kernel takes the incident edges as its views)", D,
+                    AHV_VIEWS_MAX);
+    if (n_fresh < 0) return fail(AHV_EINVAL, "pose_graph_propose: n_fresh = %lld must be >= 0", (long long)n_fresh);
+    if (N >= (int64_t)1 << 31) return fail(AHV_EINVAL, "pose_graph_propose: N = %lld must be below 2^31", (long long)N);
+    if (n_fresh >= (int64_t)1 << 31 || N < 1 + D + n_fresh)
+        return fail(AHV_EINVAL, "pose_graph_propose: N = %lld candidates do not hold 1 + D + n_fresh = %lld slots", (long long)N,
+                    (long long)(1 + D + n_fresh));
+    if (sweep < 0 || sweep > 255) return fail(AHV_EINVAL, "pose_graph_propose: sweep = %d outside 0..255", sweep);
+    if (!(sigma_rad >= 0.0f && sigma_rad < __builtin_inff()))
+        return fail(AHV_EINVAL, "pose_graph_propose: sigma = %g must be finite and >= 0", (double)sigma_rad);
+    if (!A || !pair_R || !pair_score || !edges || !incident || !Q || !Rrel)
+        return fail(AHV_EINVAL, "pose_graph_propose: null pointer (only counter may be NULL)");
+    hipError_t e = ahv::launch_pose_graph_propose(A, pair_R, pair_score, edges, incident, B, V, E, k, D, N, n_fresh, seed, counter, sweep,
+                                                  sigma_rad, Q, Rrel, static_cast<hipStream_t>(stream));
+    if (e != hipSuccess) return hip_fail("pose_graph_propose: launch", e);
+    return AHV_OK;
+}
+
+int ahv_pose_graph_commit_f32(const int64_t* key, const float* Q, int B, int V, int k, int64_t N, float* A, float* node_score,
+                              void* stream)
+{
+    if (int rc = graph_sizes("pose_graph_commit", B, V)) return rc;
+    if (int rc = graph_node("pose_graph_commit", "k", k, V)) return rc;
+    if (N < 1 || N >= (int64_t)1 << 31) return fail(AHV_EINVAL, "pose_graph_commit: N = %lld outside 1..2^31-1", (long long)N);
+    if (!key || !Q || !A || !node_score) return fail(AHV_EINVAL, "pose_graph_commit: null pointer");
+    hipError_t e = ahv::launch_pose_graph_commit(key, Q, B, V, k, N, A, node_score, static_cast<hipStream_t>(stream));
+    if (e != hipSuccess) return hip_fail("pose_graph_commit: launch", e);
     return AHV_OK;
 }
 

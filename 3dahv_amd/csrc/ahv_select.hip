@@ -5,6 +5,7 @@
 // read scores, keys and rotation matrices only: no volume, no MFMA.  (unpack_best_kernel, the decode without a gather, sits
 // with the scorer in ahv_score.hip.)
 #include "ahv_device.h"
+#include "ahv_so3.h"
 #include "ahv_sym.h"
 
 namespace ahv {
@@ -637,26 +638,6 @@ constexpr int kViewsMax = 16;
 struct ViewWeights {
     float w[kViewsMax];
 };
-
-// o = Q_n A_v^T with the bits of view_rotations_kernel (q = Q_n, d = A_v: entry (a, c) is row a of Q_n times row c of A_v).
-// That kernel states the entry as p0 + p1 + p2 and leaves the contraction to the compiler, which -- vectorising the nine entries
-// in pairs -- does not contract them alike: the last product is always fused, fma(q2, d2, .), onto fma(q0, d0, rn(p1)) in
-// columns 0 and 2, onto fma(q1, d1, rn(p0)) in column 1, and entry (2, 2) is fma(q2, d2, rn(rn(p0) + rn(p1))).  The same
-// expression at a second site is contracted differently again (it was tried: 1 ulp apart in entry (0, 1)), so this site spells
-// the dense kernel's operations out; the dense kernel stays as it is, and tests/test_gpu_views_compact.py compares the two bit
-// for bit on every shape, which is what notices a compiler that changes its mind.
-__device__ __forceinline__ void view_compose_pinned(const float (&q)[9], const float* d, float* o)
-{
-#pragma clang fp contract(off)
-#pragma unroll
-    for (int a = 0; a < 3; ++a)
-#pragma unroll
-        for (int c = 0; c < 3; ++c) {
-            const float p0 = q[a * 3] * d[c * 3], p1 = q[a * 3 + 1] * d[c * 3 + 1];
-            const float inner = (a == 2 && c == 2) ? p0 + p1 : c == 1 ? fmaf(q[a * 3 + 1], d[c * 3 + 1], p0) : fmaf(q[a * 3], d[c * 3], p1);
-            o[a * 3 + c] = fmaf(q[a * 3 + 2], d[c * 3 + 2], inner);
-        }
-}
 
 // t(Q_n, A_v) = sum_ab Q_n[a][b] A_v[a][b]: ONE fp32 fmaf chain in one order for every kernel that decides participation
 __device__ __forceinline__ float view_trace(const float (&q)[9], const float* a)

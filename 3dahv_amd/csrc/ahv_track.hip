@@ -35,41 +35,6 @@ __device__ __forceinline__ float clip_norm(float& x, float& y, float& z, float l
     return a;
 }
 
-// o = M(normalise(q(r) q(w))), the matrix of r exp([w]x), composed as unit quaternions and normalised.
-__device__ __forceinline__ void compose_rotation_vector(const float (&r)[9], float w0, float w1, float w2, float* __restrict__ o)
-{
-    const float a = sqrtf(w0 * w0 + w1 * w1 + w2 * w2);
-    // q(w) = (cos a/2, sin(a/2) w / a); sin(a/2) / a -> 1/2 - a^2/48 as a -> 0
-    float sh, ch;
-    sincosf(0.5f * a, &sh, &ch);
-    const float kq = a < 1e-3f ? 0.5f - a * a * (1.0f / 48.0f) : sh / a;
-    const float dr = ch, di = kq * w0, dj = kq * w1, dk = kq * w2;
-    // q(R) by Shepperd's branch: divide by the largest of the four components
-    float qr, qi, qj, qk;
-    const float tr = r[0] + r[4] + r[8];
-    if (tr > 0.0f) {
-        const float s = 2.0f * sqrtf(tr + 1.0f);
-        qr = 0.25f * s; qi = (r[7] - r[5]) / s; qj = (r[2] - r[6]) / s; qk = (r[3] - r[1]) / s;
-    } else if (r[0] > r[4] && r[0] > r[8]) {
-        const float s = 2.0f * sqrtf(1.0f + r[0] - r[4] - r[8]);
-        qr = (r[7] - r[5]) / s; qi = 0.25f * s; qj = (r[1] + r[3]) / s; qk = (r[2] + r[6]) / s;
-    } else if (r[4] > r[8]) {
-        const float s = 2.0f * sqrtf(1.0f + r[4] - r[0] - r[8]);
-        qr = (r[2] - r[6]) / s; qi = (r[1] + r[3]) / s; qj = 0.25f * s; qk = (r[5] + r[7]) / s;
-    } else {
-        const float s = 2.0f * sqrtf(1.0f + r[8] - r[0] - r[4]);
-        qr = (r[3] - r[1]) / s; qi = (r[2] + r[6]) / s; qj = (r[5] + r[7]) / s; qk = 0.25f * s;
-    }
-    // Hamilton product q(R) q(w): the matrix of a product is the product of the matrices, R exp([w]x)
-    float pr = qr * dr - qi * di - qj * dj - qk * dk;
-    float pi = qr * di + qi * dr + qj * dk - qk * dj;
-    float pj = qr * dj - qi * dk + qj * dr + qk * di;
-    float pk = qr * dk + qi * dj - qj * di + qk * dr;
-    const float inv = 1.0f / sqrtf(fmaxf(pr * pr + pi * pi + pj * pj + pk * pk, 1e-30f));
-    pr *= inv; pi *= inv; pj *= inv; pk *= inv;
-    quaternion_matrix(pr, pi, pj, pk, o);
-}
-
 __device__ __forceinline__ void diffuse_slot(const long long* __restrict__ idx, const float* __restrict__ R, long r_batch_stride,
                                              long N, const key_t* __restrict__ best_key, long M, long n_fresh,
                                              unsigned long long seed, const long long* __restrict__ step, float sigma,

@@ -416,6 +416,57 @@ def _track_sequence_views(model, item, tracker, refs, proposals, device, encoder
     return _track_result(tracker, order, R_map, score, err, truth, smoothed, marginals)
 
 
+def solve_views(model, item: dict, frames: Sequence[int], graph, proposals: Optional[torch.Tensor] = None,
+                row_vector_R: bool = False, device=None, encoder_fn: Optional[Callable] = None) -> dict:
+    """All the rotations of an UNPOSED set of frames of one sequence at once, with a ``posegraph.PoseGraph`` (batch 1, ``n_views
+    = len(frames)``; its default edge list is every ordered pair, what ``get_permutations`` yields).  ``item`` is what
+    ``SyntheticSequences`` or ``co3d.Co3dSequences`` yields.  The encoder -- ``encoder_fn`` or ``model.forward_features`` for
+    ``layer4`` inputs, else ``model`` -- runs ONCE on the batch of the graph's E edges, pair (frames[i], frames[j]) for edge
+    ``i -> j``, and ``graph.solve`` scores every pair against ``proposals (N0,3,3)`` (default: 4 096 Haar rotations, seed 0),
+    builds the tree and runs the ascent.
+    Ground truth of edge ``i -> j``: ``R_j R_i^-1``, which reads ``item["R"]`` as absolute rotations acting on column vectors.
+    ``row_vector_R=True`` (``Co3dSequences``), under ``track_sequence``'s rule for several views: a model trained on annotations
+    that act on row vectors gives the pair (src, tgt) the rotation ``R_src^T R_tgt``, which is ``A_j A_i^T`` with ``A_v = R_v^T``
+    when the pair of edge ``i -> j`` is encoded the other way round, (frames[j], frames[i]); the graph's rotations are then
+    ``R_v^T`` up to the gauge and the ground truth of the edge is ``R_j^T R_i``.
+    Returns host tensors, after ONE synchronisation at the end: ``{"frames", "edges" (E,2), "A" (V,3,3), "node_score" (V,),
+    "pair_score" (E,), "pair_err", "tree_err", "joint_err" (E,) degrees}`` -- per edge the error of its own arg-max, of the
+    spanning tree's solution and of the joint solution against the ground truth."""
+    if graph.B != 1:
+        raise RuntimeError("solve_views solves one sequence: the graph must have batch = 1, got %d" % graph.B)
+    frames = [int(t) for t in frames]
+    n = int(item["n"])
+    if len(frames) != graph.V or len(set(frames)) != len(frames) or not all(0 <= t < n for t in frames):
+        raise RuntimeError("frames must be %d distinct frames of the sequence's %d (the graph's n_views), got %s" % (graph.V, n, frames))
+    if device is None:
+        device = graph.W1.device
+    device = torch.device(device)
+    if "get_data" in item:   # lazy source (co3d.Co3dSequences): decode the chosen frames
+        item = dict(item, **item["get_data"](np.arange(n)))
+    uses_l4 = "layer4" in item
+    where = torch.tensor(frames, dtype=torch.int64)
+    inputs = (item["layer4"] if uses_l4 else item["image"]).index_select(0, where).to(device=device, dtype=torch.float32)
+    rots = item["R"].index_select(0, where).to(device=device, dtype=torch.float32)
+    embed = (encoder_fn or model.forward_features) if uses_l4 else model
+    if proposals is None:
+        proposals = random_rotations(4096, generator=torch.Generator().manual_seed(0))
+    proposals = proposals.to(device)
+    edges = torch.tensor(graph.topology.edges, dtype=torch.int64, device=device)
+    src, tgt = inputs.index_select(0, edges[:, 0]), inputs.index_select(0, edges[:, 1])
+    vol_src, vol_tgt = embed(tgt, src) if row_vector_R else embed(src, tgt)
+    res = graph.solve(vol_src[None], vol_tgt[None], proposals)
+    A_gt = rots.transpose(-1, -2) if row_vector_R else rots
+    R_gt = A_gt[edges[:, 1]] @ A_gt[edges[:, 0]].transpose(-1, -2)
+    E = edges.shape[0]
+    packed = torch.cat([geodesic_deg(res.pair_R[0], R_gt), geodesic_deg(graph.relative(res.init_A)[0], R_gt),
+                        geodesic_deg(graph.relative(res.A)[0], R_gt), res.pair_score[0], res.node_score[0],
+                        res.A[0].reshape(-1)]).cpu()
+    V = graph.V
+    return {"frames": frames, "edges": edges.cpu(), "pair_err": packed[:E], "tree_err": packed[E:2 * E],
+            "joint_err": packed[2 * E:3 * E], "pair_score": packed[3 * E:4 * E], "node_score": packed[4 * E:4 * E + V],
+            "A": packed[4 * E + V:].reshape(V, 3, 3)}
+
+
 def evaluate_pairwise(cfg, model, categories: Dict[str, Iterable[dict]], num_frames: int = 2, print_results=True,
                       **kw):
     """Counterpart of ``evaluate_pairwise`` (test_co3d.py:157-198)."""

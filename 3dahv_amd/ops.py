@@ -2213,6 +2213,242 @@ def verify_views_staged(vol_refs: torch.Tensor, vol_query: torch.Tensor, Q: torc
     return scores_out, best_key
 
 
+# ---- joint pose inference over an unposed image set --------------------------------------------------------------
+# V images, E directed edges with an independent pairwise estimate each, all absolute rotations wanted (``ahv_pose_graph_*_f32``,
+# include/ahv.h; the loop is ``posegraph.PoseGraph``).
+
+PoseGraphInit = collections.namedtuple("PoseGraphInit", ["A", "parent_edge", "reached"])
+
+
+class PoseGraphTopology:
+    """The static graph of a ``PoseGraph``, validated on the host and uploaded once: ``edges`` a list of ``(i, j)`` (None: every
+    ordered pair, i-major), ``root`` the gauge node.  Host side: ``n_views``, ``edges``, ``incident[k]`` = the ``(edge id,
+    outgoing)`` pairs of node k in edge order, ``degree[k]`` (both directions count).  Device side, int32: ``edges_dev (E,2)``
+    and ``incident_dev``, the nodes' lists one after another (``offset[k]`` where k's starts), an entry ``e |
+    AHV_GRAPH_EDGE_OUTGOING`` for an edge k -> j.  A degree above ``AHV_VIEWS_MAX`` is refused: the fuse kernel takes a node's
+    incident edges as its views (a complete ordered graph goes up to V = 9; larger sets need a sparser edge list)."""
+
+    def __init__(self, n_views: int, edges=None, root: int = 0, device=None):
+        V = int(n_views)
+        if not 2 <= V <= _lib.AHV_GRAPH_MAX_NODES:
+            raise RuntimeError("n_views = %d outside 2..%d" % (V, _lib.AHV_GRAPH_MAX_NODES))
+        if edges is None:
+            edges = [(i, j) for i in range(V) for j in range(V) if i != j]
+        if isinstance(edges, torch.Tensor):
+            edges = edges.detach().cpu().tolist()
+        edges = [tuple(int(x) for x in e) for e in edges]
+        if not 1 <= len(edges) <= _lib.AHV_GRAPH_MAX_EDGES:
+            raise RuntimeError("%d edges: outside 1..%d" % (len(edges), _lib.AHV_GRAPH_MAX_EDGES))
+        incident = [[] for _ in range(V)]
+        for e, ij in enumerate(edges):
+            if len(ij) != 2:
+                raise RuntimeError("edge %d = %r is not a pair (i, j)" % (e, ij))
+            i, j = ij
+            if not (0 <= i < V and 0 <= j < V):
+                raise RuntimeError("edge %d = (%d, %d) names a node outside 0..V-1 = %d" % (e, i, j, V - 1))
+            if i == j:
+                raise RuntimeError("edge %d = (%d, %d) is a self-loop" % (e, i, j))
+            incident[i].append((e, True))
+            incident[j].append((e, False))
+        self.degree = [len(l) for l in incident]
+        for k, d in enumerate(self.degree):
+            if d > _lib.AHV_VIEWS_MAX:
+                raise RuntimeError("node %d has degree %d > %d (both directions count): give a sparser edge list"
+                                   % (k, d, _lib.AHV_VIEWS_MAX))
+        self.root = int(root)
+        if not 0 <= self.root < V:
+            raise RuntimeError("root = %d outside 0..V-1 = %d" % (self.root, V - 1))
+        self.n_views, self.edges, self.incident = V, edges, incident
+        self.offset = [sum(self.degree[:k]) for k in range(V)]
+        flat = [e | (_lib.AHV_GRAPH_EDGE_OUTGOING if out else 0) for l in incident for e, out in l]
+        self.edges_dev = torch.tensor(edges, dtype=torch.int32, device=device).reshape(len(edges), 2)
+        self.incident_dev = torch.tensor(flat, dtype=torch.int32, device=device)
+
+    @property
+    def n_edges(self) -> int:
+        return len(self.edges)
+
+
+def _graph_pairs(topology, pair_R, pair_score):
+    if not isinstance(topology, PoseGraphTopology):
+        raise RuntimeError("topology must be a PoseGraphTopology, got %s" % type(topology).__name__)
+    E = topology.n_edges
+    if pair_R.dim() != 4 or tuple(pair_R.shape[1:]) != (E, 3, 3):
+        raise RuntimeError("pair_R must be (B,E,3,3) with E = %d, got %s" % (E, tuple(pair_R.shape)))
+    B = pair_R.shape[0]
+    if tuple(pair_score.shape) != (B, E):
+        raise RuntimeError("pair_score must be (B,E) = %s, got %s" % ((B, E), tuple(pair_score.shape)))
+    if not 1 <= B <= 65535:
+        raise RuntimeError("B = %d outside 1..65535" % B)
+    return B, E
+
+
+def _graph_out(t, name, shape, dtype, dev):
+    if t is None:
+        return torch.empty(shape, dtype=dtype, device=dev)
+    if not isinstance(t, torch.Tensor) or tuple(t.shape) != shape or t.dtype != dtype or t.device != dev or not t.is_contiguous():
+        raise RuntimeError("%s must be a contiguous %s %s tensor on %s" % (name, str(dtype).replace("torch.", ""), shape, dev))
+    return t
+
+
+def _graph_device(topology, dev) -> None:
+    if topology.edges_dev.device != dev:
+        raise RuntimeError("Expected all tensors to be on the same device, found %s and the topology on %s"
+                           % (dev, topology.edges_dev.device))
+
+
+@torch.no_grad()
+def pose_graph_init(pair_R: torch.Tensor, pair_score: torch.Tensor, topology: PoseGraphTopology, out=None) -> PoseGraphInit:
+    """The tree start of a joint solve (``ahv_pose_graph_init_f32``, ONE launch): Prim's maximum spanning tree from
+    ``topology.root`` by ``pair_score (B,E)`` (non-finite: the edge is absent; ties to the lower edge index) and the absolute
+    rotations it implies from ``pair_R (B,E,3,3)``, the pairs' estimates of ``A_j A_i^T``.  Returns ``PoseGraphInit(A (B,V,3,3),
+    parent_edge (B,V) int32, reached (B,V) int32)``: the root and every node it is not connected to keep the identity and a
+    parent of -1.  ``out``: three tensors of those shapes to write to."""
+    B, E = _graph_pairs(topology, pair_R, pair_score)
+    V = topology.n_views
+    dev = _need_gpu(pair_R, pair_score)
+    _graph_device(topology, dev)
+    A, parent, reached = (None, None, None) if out is None else out
+    A = _graph_out(A, "A", (B, V, 3, 3), torch.float32, dev)
+    parent = _graph_out(parent, "parent_edge", (B, V), torch.int32, dev)
+    reached = _graph_out(reached, "reached", (B, V), torch.int32, dev)
+    Pc, sc = pair_R.detach().contiguous(), pair_score.detach().contiguous()
+    _call(dev, "ahv_pose_graph_init_f32", Pc.data_ptr(), sc.data_ptr(), topology.edges_dev.data_ptr(), B, V, E, topology.root,
+          A.data_ptr(), parent.data_ptr(), reached.data_ptr())
+    return PoseGraphInit(A, parent, reached)
+
+
+def _graph_node(topology, k) -> int:
+    k = int(k)
+    if not 0 <= k < topology.n_views:
+        raise RuntimeError("k = %d outside 0..V-1 = %d" % (k, topology.n_views - 1))
+    return k
+
+
+@torch.no_grad()
+def pose_graph_propose(A: torch.Tensor, pair_R: torch.Tensor, pair_score: torch.Tensor, topology: PoseGraphTopology, k: int,
+                       n: int, sigma_deg: float, sweep: int = 0, seed: int = 0, counter: torch.Tensor | None = None,
+                       n_fresh: int = 0, out=None):
+    """The ``n`` candidates of node k's rotation and what each incident edge makes of them (``ahv_pose_graph_propose_f32``, ONE
+    launch) -> ``(Q (B,n,3,3), Rrel (B,D,n,3,3))``, D = ``topology.degree[k]``.  Slot 0 is ``A[b,k]`` bit for bit; slots 1..D what
+    each incident edge implies from its neighbour's rotation and ``pair_R`` (``A[b,k]`` again where ``pair_score`` is not
+    finite); the last ``n_fresh`` slots are Haar rotations; every slot between is ``A[b,k] exp([sigma z]x)`` with noise that is
+    a function of ``(seed, counter, sweep, b, k, slot)`` alone.  ``counter``: the int64 device counter ``track_advance`` moves
+    (read on the device; None: 0).  ``Rrel[b,d]`` is ``Q A_i^T`` for an incoming edge i -> k (the bytes of ``view_rotations``) and
+    ``A_j Q^T`` for an outgoing one k -> j; ``Rrel.view(B*D, n, 3, 3)`` is the scorer's per-sample set.  ``out``: ``(Q, Rrel)``
+    to write to; neither may overlap ``A``."""
+    B, E = _graph_pairs(topology, pair_R, pair_score)
+    V = topology.n_views
+    k = _graph_node(topology, k)
+    D = topology.degree[k]
+    if D < 1:
+        raise RuntimeError("node %d has no incident edge: nothing to propose against" % k)
+    if tuple(A.shape) != (B, V, 3, 3):
+        raise RuntimeError("A must be (B,V,3,3) = %s, got %s" % ((B, V, 3, 3), tuple(A.shape)))
+    N, n_fresh, sweep = int(n), int(n_fresh), int(sweep)
+    if n_fresh < 0:
+        raise RuntimeError("n_fresh = %d must be >= 0" % n_fresh)
+    if N < 1 + D + n_fresh or N >= 1 << 31:
+        raise RuntimeError("n = %d candidates do not hold 1 + D + n_fresh = 1 + %d + %d slots (or n >= 2^31)" % (N, D, n_fresh))
+    if not 0 <= sweep <= 255:
+        raise RuntimeError("sweep = %d outside 0..255" % sweep)
+    sigma = _angle_rad(sigma_deg, "sigma_deg")
+    dev = _need_gpu(A, pair_R, pair_score)
+    _graph_device(topology, dev)
+    if counter is not None:
+        _step_counter(counter, dev)
+    if not A.is_contiguous():
+        raise RuntimeError("A must be contiguous (pose_graph_commit writes into it)")
+    Q, Rrel = (None, None) if out is None else out
+    Q = _graph_out(Q, "Q", (B, N, 3, 3), torch.float32, dev)
+    Rrel = _graph_out(Rrel, "Rrel", (B, D, N, 3, 3), torch.float32, dev)
+    _refuse_overlap(((A, "A"),), (("Q", Q), ("Rrel", Rrel)))
+    Pc, sc = pair_R.detach().contiguous(), pair_score.detach().contiguous()
+    _call(dev, "ahv_pose_graph_propose_f32", A.data_ptr(), Pc.data_ptr(), sc.data_ptr(), topology.edges_dev.data_ptr(),
+          topology.incident_dev.data_ptr() + 4 * topology.offset[k], B, V, E, k, D, N, n_fresh, int(seed) & (2**64 - 1),
+          counter.data_ptr() if counter is not None else None, sweep, sigma, Q.data_ptr(), Rrel.data_ptr())
+    return Q, Rrel
+
+
+@torch.no_grad()
+def pose_graph_commit(key: torch.Tensor, Q: torch.Tensor, A: torch.Tensor, node_score: torch.Tensor, k: int):
+    """``A[b,k] = Q[b, decode(key[b])]`` as a bit copy and ``node_score[b,k]`` = the key's score, IN PLACE
+    (``ahv_pose_graph_commit_f32``, ONE launch, no host read): ``key (B,)`` is the packed key of the fused row.  A sample whose
+    key holds no finite score keeps its rotation and its score.  Returns ``(A, node_score)``."""
+    if A.dim() != 4 or tuple(A.shape[2:]) != (3, 3):
+        raise RuntimeError("A must be (B,V,3,3), got %s" % (tuple(A.shape),))
+    B, V = A.shape[:2]
+    k = int(k)
+    if not 0 <= k < V:
+        raise RuntimeError("k = %d outside 0..V-1 = %d" % (k, V - 1))
+    if Q.dim() != 4 or Q.shape[0] != B or tuple(Q.shape[2:]) != (3, 3) or Q.shape[1] < 1:
+        raise RuntimeError("Q must be (B,N,3,3) with B = %d, got %s" % (B, tuple(Q.shape)))
+    if tuple(node_score.shape) != (B, V):
+        raise RuntimeError("node_score must be (B,V) = %s, got %s" % ((B, V), tuple(node_score.shape)))
+    dev = _need_gpu(A, Q, node_score)
+    if not isinstance(key, torch.Tensor) or key.dtype != torch.int64 or key.numel() != B or key.device != dev or not key.is_contiguous():
+        raise RuntimeError("key must be a contiguous int64 tensor of B = %d elements on %s" % (B, dev))
+    if not (A.is_contiguous() and Q.is_contiguous() and node_score.is_contiguous()):
+        raise RuntimeError("A, Q and node_score must be contiguous (A and node_score are written in place)")
+    _call(dev, "ahv_pose_graph_commit_f32", key.data_ptr(), Q.data_ptr(), B, V, k, Q.shape[1], A.data_ptr(), node_score.data_ptr())
+    return A, node_score
+
+
+class pose_graph_workspace:
+    """What ``pose_graph_score`` needs between its two launches on (B, D, N): the per-edge scores ``(B,D,N)``, the scoring
+    launch's own keys ``(B*D,)`` and, on first use, the target features of the split-f16 scorer."""
+
+    def __init__(self, B: int, D: int, N: int, device):
+        self.B, self.D, self.N = int(B), int(D), int(N)
+        self.scores = torch.empty((self.B, self.D, self.N), dtype=torch.float32, device=device)
+        self.keys = torch.empty((self.B * self.D,), dtype=torch.int64, device=device)
+        self.feat = None
+
+    def features(self) -> torch.Tensor:
+        if self.feat is None:
+            self.feat = torch.empty((self.B * self.D, 32, 64), dtype=torch.float32, device=self.scores.device)
+        return self.feat
+
+
+def pose_graph_score(vol_src: torch.Tensor, vol_tgt: torch.Tensor, Rrel: torch.Tensor, W1: torch.Tensor, W2: torch.Tensor,
+                     b2: torch.Tensor, weights=None, workspace: pose_graph_workspace | None = None,
+                     scores_out: torch.Tensor | None = None, best_key: torch.Tensor | None = None, split_f16: bool | None = None):
+    """One node's candidates against all its incident edges: the scoring launch of ``verify_pair`` over the B*D (edge) samples
+    -- ``vol_src, vol_tgt (B,D,16,8,8,8)`` the staged volumes of the incident edges, ``Rrel (B,D,N,3,3)`` from
+    ``pose_graph_propose`` -- and ``fuse_view_scores``' launch with no angle limit: the weighted mean over the edges in the order
+    d = 0 .. D-1 in fp32 and its arg-max key, ``(fused (B,N), best_key (B,))``.  ``weights``: D host floats (None: ones; 0
+    removes an edge, which is then never read).  ``workspace`` (``pose_graph_workspace(B, D, N, device)``), ``scores_out`` and
+    ``best_key`` given: no allocation.  The key always starts from empty.  Inference only."""
+    _refuse_grad("pose_graph_score", vol_src, vol_tgt, Rrel, W1, W2, b2)
+    if Rrel.dim() != 5 or tuple(Rrel.shape[3:]) != (3, 3):
+        raise RuntimeError("Rrel must be (B,D,N,3,3), got %s" % (tuple(Rrel.shape),))
+    B, D, N = Rrel.shape[:3]
+    if not 1 <= D <= _lib.AHV_VIEWS_MAX:
+        raise RuntimeError("D = %d outside 1..%d" % (D, _lib.AHV_VIEWS_MAX))
+    for name, v in (("vol_src", vol_src), ("vol_tgt", vol_tgt)):
+        if tuple(v.shape) != (B, D) + _VOL:
+            raise RuntimeError("%s must be (B,D,16,8,8,8) = %s, got %s" % (name, (B, D) + _VOL, tuple(v.shape)))
+    w = _view_weights(weights, D)
+    dev = _need_gpu(vol_src, vol_tgt, Rrel, W1, W2, b2)
+    ws = workspace
+    if ws is None:
+        ws = pose_graph_workspace(B, D, N, dev)
+    elif (ws.B, ws.D, ws.N) != (B, D, N) or ws.scores.device != dev:
+        raise RuntimeError("workspace was made for (B, D, N) = %s on %s, the call has %s on %s"
+                           % ((ws.B, ws.D, ws.N), ws.scores.device, (B, D, N), dev))
+    scores_out = _graph_out(scores_out, "scores_out", (B, N), torch.float32, dev)
+    best_key = _graph_out(best_key, "best_key", (B,), torch.int64, dev)
+    split = bool(_SPLIT_F16.get() if split_f16 is None else split_f16)
+    with torch.no_grad():
+        _score_hypotheses_nograd(vol_src.detach().reshape((B * D,) + _VOL), vol_tgt.detach().reshape((B * D,) + _VOL),
+                                 Rrel.detach().reshape(B * D, N, 3, 3), W1, W2, b2, 0, True, ws.keys, True, split, None,
+                                 tgt_is_volume=True, feat_tgt_out=ws.features() if split else None,
+                                 scores_out=ws.scores.view(B * D, N))
+        _call(dev, "ahv_fuse_view_scores_f32", ws.scores.data_ptr(), None, 0, None, w, B, D, N, 0, 0.0, scores_out.data_ptr(),
+              best_key.data_ptr(), _lib.AHV_VIEWS_NO_ANGLE_LIMIT | _lib.AHV_VIEWS_RESET_BEST)
+    return scores_out, best_key
+
+
 # ---- rotation gradient of the score, gradient-based pose polishing ------------------------------------------
 
 @torch.no_grad()
