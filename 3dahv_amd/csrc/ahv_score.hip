@@ -437,7 +437,10 @@ __device__ __forceinline__ void score_hypotheses_body(
                 ++team_rounds;
                 if (nf_w || (unsigned)__builtin_amdgcn_readfirstlane((int)lds_nf.tgt_gen) == gen) team_head_exact(v, u, f0);
                 else team_head(v, u, f0);
-                const float inv = 1.0f / fmaxf(sqrtf(team_sumsq(v)), 1e-12f);  // F.normalize(dim=1), eps 1e-12
+                // F.normalize(dim=1), eps 1e-12: |v|.clamp_min(eps) KEEPS a NaN norm (a column with +-inf beside NaN is NaN
+                // throughout; fmaxf would hand back eps and leave the +-inf in it) -- clamped_norm's rule in ahv_ops.hip
+                const float nrm = sqrtf(team_sumsq(v));
+                const float inv = 1.0f / (nrm < 1e-12f ? 1e-12f : nrm);
 #pragma unroll
                 for (int m2 = 0; m2 < 2; ++m2) {
                     const f32x4 x = v[m2] * inv;

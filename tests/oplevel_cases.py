@@ -228,8 +228,17 @@ def adjoint_chain_allowance(like, R, grad_out):
     return sd.reshape(like.shape), int(n_adds.mean())
 
 
+def _score_hypotheses(vol_src, vol_tgt, R, W1, W2, b2):
+    """torch_ref.score_hypotheses' scores (B,N), in chunks of 256 hypotheses.  It takes R (N,3,3) shared by the batch; for
+    R (B,N,3,3) per sample it is called sample by sample (tests/fused_cases.py)."""
+    if R.dim() == 3:
+        return torch_ref.score_hypotheses(vol_src, vol_tgt, R, W1, W2, b2, chunk=256)[0]
+    return torch.cat([torch_ref.score_hypotheses(vol_src[b:b + 1], vol_tgt[b:b + 1], R[b], W1, W2, b2, chunk=256)[0]
+                      for b in range(R.shape[0])])
+
+
 _OPS = {"forward_3d2d": torch_ref.forward_3d2d, "rotate_volume": _rotate, "score_features": _score_literal,
-        "rotate_volume_adjoint": _rotate_adjoint}
+        "rotate_volume_adjoint": _rotate_adjoint, "score_hypotheses": _score_hypotheses}
 
 
 def _ref(dtype, op, *args):
