@@ -10,97 +10,6 @@
 #include "../../include/ahv_diag.h"
 #include "ahv_launch.h"
 
-namespace ahv {
-hipError_t launch_unpack_best(const int64_t*, int, float*, int64_t*, hipStream_t);
-hipError_t launch_rotate_volume(const float*, int64_t, const float*, int64_t, int, int, int, int, float*, int,
-                                hipStream_t);
-hipError_t launch_rotate_volume_backward(const float*, int64_t, const float*, int64_t, int, int, int, int, float*, int,
-                                         hipStream_t);
-hipError_t launch_forward_3d2d(const float*, const float*, const float*, const float*, int64_t, float*, int,
-                               hipStream_t);
-hipError_t launch_score_features(const float*, const float*, int, int64_t, float*, int, hipStream_t);
-hipError_t launch_argmax(const float*, int, int64_t, int64_t, int64_t*, int, hipStream_t);
-hipError_t launch_fill_keys(int64_t*, int, hipStream_t);
-int topk_parts(int64_t N);
-hipError_t launch_topk(const float*, int, int64_t, int64_t, int, int64_t*, int64_t*, bool, hipStream_t);
-hipError_t launch_topk_merge(const int64_t*, int, int, int, int64_t*, bool, hipStream_t);
-hipError_t launch_select_topk(int64_t*, int, const float*, int64_t, int64_t, int64_t, int, float*, float*, int64_t*, bool,
-                              hipStream_t);
-hipError_t launch_compose_rotations_topk(const int64_t*, int, const float*, int64_t, int64_t, int64_t, const float*, int64_t,
-                                         int, float*, hipStream_t);
-int64_t topk_modes_state_stride(int64_t N);
-hipError_t launch_topk_modes(const float*, const float*, int64_t, int, int64_t, int64_t, int, float, int64_t*, int64_t*,
-                             hipStream_t);
-hipError_t launch_topk_modes_sym(const float*, const float*, int64_t, int, int64_t, int64_t, int, float, const float*, int64_t, int,
-                                 const float*, int64_t, int64_t*, int64_t*, hipStream_t);
-hipError_t launch_sym_fold(const float*, int64_t, int, int64_t, const float*, int64_t, int, const float*, int64_t, const float*, int,
-                           float, int64_t, const float*, float*, float*, int32_t*, int32_t*, float*, hipStream_t);
-hipError_t launch_view_rotations(const float*, int64_t, const float*, int, int, int64_t, float*, hipStream_t);
-hipError_t launch_fuse_views(const float*, const float*, int64_t, const float*, const float*, int, int, int64_t, int64_t, float,
-                             bool, float*, int64_t*, hipStream_t);
-hipError_t launch_nearest_views(const float*, const float*, int, int, int, int32_t*, float*, hipStream_t);
-hipError_t launch_gather_views(const void*, const int32_t*, int, int, int, int64_t, void*, bool, hipStream_t);
-int64_t view_compact_tiles(int64_t N);
-hipError_t launch_view_rotations_compact(const float*, int64_t, const float*, const float*, int, int, int64_t, float, int64_t,
-                                         float*, int32_t*, int64_t*, void*, hipStream_t);
-hipError_t launch_fuse_views_compact(const float*, const int32_t*, const float*, int, int, int64_t, int64_t, int64_t, float*,
-                                     int64_t*, hipStream_t);
-size_t posterior_state_stride(int K);
-int posterior_parts(int64_t N);
-hipError_t launch_posterior(const float*, const float*, int64_t, int, int64_t, const float*, int, float, float, void*, void*, bool,
-                            hipStream_t);
-hipError_t launch_posterior_merge(const void*, int, int, int, float, void*, bool, hipStream_t);
-hipError_t launch_posterior_finish(const void*, int, int, float, float*, float*, float*, int64_t*, float*, float*, float*, float*,
-                                   float*, float*, hipStream_t);
-size_t resample_stride(int64_t N);
-hipError_t launch_resample(const float*, int, int64_t, float, int64_t, const float*, int64_t*, void*, hipStream_t);
-hipError_t launch_compose_rotations_indexed(const int64_t*, const float*, int64_t, int64_t, const float*, int64_t, int, float*,
-                                            hipStream_t);
-hipError_t launch_random_rotations(uint64_t, uint64_t, int64_t, float*, hipStream_t);
-hipError_t launch_so3_grid(int64_t, int64_t, int64_t, float*, hipStream_t);
-hipError_t launch_diffuse_rotations(const int64_t*, const float*, int64_t, int64_t, const int64_t*, int64_t, int64_t, int, uint64_t,
-                                    const int64_t*, float, float, float*, float*, hipStream_t);
-hipError_t launch_predict_rotations(const int64_t*, const float*, int64_t, const float*, int64_t, int64_t, const int64_t*, int64_t,
-                                    int64_t, int, uint64_t, const int64_t*, float, float, float, float, float, int, float*, float*,
-                                    float*, hipStream_t);
-hipError_t launch_track_advance(uint64_t, int64_t*, int, float*, hipStream_t);
-hipError_t launch_predict_rotations_ctl(const int64_t*, const float*, int64_t, const float*, int64_t, int64_t, const int64_t*, int64_t,
-                                        const uint32_t*, int, uint64_t, const int64_t*, float, float, float, int, float*, float*,
-                                        float*, hipStream_t);
-hipError_t launch_track_control(const float*, const float*, const int64_t*, const float*, int, int64_t, int, float, float, int, float,
-                                float, float, float, float, int, uint32_t*, uint8_t*, hipStream_t);
-hipError_t launch_smooth_step(const float*, const float*, const float*, const int64_t*, int64_t, int, int64_t, int64_t, float, float,
-                              float, float, float*, float*, float*, int32_t*, hipStream_t);
-hipError_t launch_smooth_backtrace(const float*, const float*, const int32_t*, const int64_t*, int64_t, int, int64_t, int64_t,
-                                   int64_t, int64_t*, float*, hipStream_t);
-hipError_t launch_marginal_step(const float*, const float*, const int64_t*, int64_t, int, int64_t, int64_t, float, float, float,
-                                const float*, const float*, float*, float*, hipStream_t);
-hipError_t launch_marginal_smooth(const float*, const float*, const float*, const float*, const int64_t*, int64_t, int, int64_t,
-                                  int64_t, int64_t, float, float, float*, int64_t*, float*, hipStream_t);
-hipError_t launch_pose_graph_init(const float*, const float*, const int32_t*, int, int, int, int, float*, int32_t*, int32_t*,
-                                  hipStream_t);
-hipError_t launch_pose_graph_propose(const float*, const float*, const float*, const int32_t*, const int32_t*, int, int, int, int, int,
-                                     int64_t, int64_t, uint64_t, const int64_t*, int, float, float*, float*, hipStream_t);
-hipError_t launch_pose_graph_commit(const int64_t*, const float*, int, int, int, int64_t, float*, float*, hipStream_t);
-hipError_t launch_score_backward(const float*, const float*, const float*, int64_t, const float*, const float*,
-                                 const float*, int, int64_t, const float*, float*, float*, float*, float*, float*,
-                                 float*, float*, int, hipStream_t, bool);
-hipError_t launch_zero_fill(void* const* ptrs, const size_t* bytes, int count, hipStream_t stream);
-hipError_t launch_score_rotation_grad(const float*, const float*, const float*, int64_t, const float*, const float*,
-                                      const float*, int, int64_t, const float*, float*, float*, int, hipStream_t);
-hipError_t launch_rotate_volume_rotation_grad(const float*, const float*, int64_t, const float*, int64_t, int, int, int, int,
-                                              float*, int, hipStream_t);
-hipError_t launch_so3_ascent_candidates(const float*, const float*, const float*, const float*, int, int, int, float*,
-                                        hipStream_t);
-hipError_t launch_so3_ascent_select(const float*, const float*, const float*, int, int, int, float*, float*, float*,
-                                    hipStream_t);
-size_t transformer_workspace_floats(int B);
-int transformer_blocks(const ahv_block_weights*, int, float*, float*, int, float*, hipStream_t, const char**);
-size_t forward_2d3d_workspace_floats(int B);
-int forward_2d3d(const ahv_aligner_weights*, const float*, const float*, int, float*, float*, float*, hipStream_t,
-                 const char**);
-}  // namespace ahv
-
 namespace {
 
 thread_local char g_err[256] = "";

@@ -23,6 +23,7 @@
 #include <cstdint>
 
 #include "ahv_device.h"
+#include "ahv_launch.h"
 #define AHV_FP32_LOW_HALF  // these kernels leave registers free on their SIMDs: see low_half (ahv_dual.h)
 #include "ahv_dual.h"
 #include "ahv_trilinear.h"
@@ -1198,7 +1199,6 @@ __global__ __launch_bounds__(kRmwThreads, 2) void score_backward_volume_rmw_kern
 #endif
 }
 
-hipError_t launch_zero_fill(void* const* ptrs, const size_t* bytes, int count, hipStream_t stream);  // ahv_ops.hip
 
 // ---- host-side launcher -------------------------------------------------------------------------------
 hipError_t launch_score_backward(const float* vol_src, const float* feat_tgt, const float* R, int64_t r_batch_stride,

@@ -233,76 +233,6 @@ __device__ __forceinline__ float key_score(key_t key)
 
 __device__ __forceinline__ long key_index(key_t key) { return (long)(0xFFFFFFFFu - (unsigned)((unsigned long long)key & 0xFFFFFFFFull)); }
 
-__device__ __forceinline__ key_t wave_max_key(key_t k)
-{
-#pragma unroll
-    for (int s = 32; s >= 1; s >>= 1) {
-        const key_t o = __shfl_xor(k, s, 64);
-        k = o > k ? o : k;
-    }
-    return k;
-}
-
-// The same maximum with DPP row operations instead of six ds_bpermute round trips, for loops that have it on their critical
-// path (the knock-out rounds of the top-K kernels, ahv_ops.hip: one reduction per round, K rounds in a row).  wave_max_key
-// above stays for the one-off reductions at the end of a kernel, where the shorter code is worth more than the latency.
-// The key is reduced as its two halves: a signed 32-bit max of the score words (one DPP-modified v_max per step), then
-// the index word of the lane that holds that score -- read straight from it when it is the only one, else an unsigned max
-// over the tied lanes (lowest index = largest word).  A 64-bit compare-and-select per step cost three times as much.
-// A lane a step does not reach keeps its own value.  Every lane gets the result.
-template <int kCtrl, int kRows>
-__device__ __forceinline__ int max_i32_dpp_step(int x)
-{
-    const int o = __builtin_amdgcn_update_dpp(x, x, kCtrl, kRows, 0xF, false);
-    return o > x ? o : x;
-}
-
-template <int kCtrl, int kRows>
-__device__ __forceinline__ unsigned max_u32_dpp_step(unsigned x)
-{
-    const unsigned o = (unsigned)__builtin_amdgcn_update_dpp((int)x, (int)x, kCtrl, kRows, 0xF, false);
-    return o > x ? o : x;
-}
-
-__device__ __forceinline__ key_t wave_max_key_dpp(key_t k)
-{
-    const int hi = (int)(k >> 32);
-    const unsigned lo = (unsigned)((unsigned long long)k & 0xFFFFFFFFull);
-    int h = hi;
-    h = max_i32_dpp_step<0x111, 0xF>(h);  // row_shr:1
-    h = max_i32_dpp_step<0x112, 0xF>(h);  // row_shr:2
-    h = max_i32_dpp_step<0x114, 0xF>(h);  // row_shr:4
-    h = max_i32_dpp_step<0x118, 0xF>(h);  // row_shr:8  -> lane 15 of each row holds the row's max
-    h = max_i32_dpp_step<0x142, 0xA>(h);  // row_bcast:15
-    h = max_i32_dpp_step<0x143, 0xC>(h);  // row_bcast:31 -> lane 63 holds the wave's max
-    const int mh = __builtin_amdgcn_readlane(h, 63);
-    const unsigned long long tied = __ballot(hi == mh);
-    unsigned ml;
-    if (__popcll(tied) == 1) {  // uniform: the usual case, one lane holds the largest score
-        ml = (unsigned)__builtin_amdgcn_readlane((int)lo, __ffsll((long long)tied) - 1);
-    } else {
-        unsigned l = hi == mh ? lo : 0u;
-        l = max_u32_dpp_step<0x111, 0xF>(l);
-        l = max_u32_dpp_step<0x112, 0xF>(l);
-        l = max_u32_dpp_step<0x114, 0xF>(l);
-        l = max_u32_dpp_step<0x118, 0xF>(l);
-        l = max_u32_dpp_step<0x142, 0xA>(l);
-        l = max_u32_dpp_step<0x143, 0xC>(l);
-        ml = (unsigned)__builtin_amdgcn_readlane((int)l, 63);
-    }
-    return (key_t)(((unsigned long long)(unsigned)mh << 32) | (unsigned long long)ml);
-}
-
-// sum over the 64 lanes with DPP row operations (no LDS round trips); result valid in lane 63
-__device__ __forceinline__ float wave_sum_dpp(float x)
-{
-    x += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x), 0x111, 0xF, 0xF, true));  // row_shr:1
-    x += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x), 0x112, 0xF, 0xF, true));  // row_shr:2
-    x += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x), 0x114, 0xF, 0xE, true));  // row_shr:4
-    x += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x), 0x118, 0xF, 0xC, true));  // row_shr:8
-    x += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x), 0x142, 0xA, 0xF, true));  // row_bcast:15
-    x += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x), 0x143, 0xC, 0xF, true));  // row_bcast:31
-    return x;
-}
-
 }  // namespace ahv
+
+#include "ahv_wave.h"  // the wave reductions (wave_max_key, wave_max_key_dpp, wave_sum_dpp, ...): they need key_t

@@ -18,6 +18,7 @@
 #include <stdint.h>
 
 #include "../../include/ahv.h"
+#include "ahv_launch.h"
 
 // Every launch in this file goes through AHV_ENC_LAUNCH so that tools/kbench_enc.cpp (built with -DAHV_ENC_PROBE) can
 // cut a forward after k launches -- the marginal cost of every launch with no profiler attached -- and collect an

@@ -10,6 +10,7 @@
 // validate every index they read from them (a foreign list stays in bounds; the host refuses it before).  Plain launches: no
 // atomics, no workgroup waits on another one, every sum in one stated order.
 #include "ahv_device.h"
+#include "ahv_launch.h"
 #include "ahv_so3.h"
 
 namespace ahv {

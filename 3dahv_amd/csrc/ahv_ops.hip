@@ -3,9 +3,11 @@
 // (rotate_volume -> forward_3d2d -> mul/sum/mean -> max) runs unchanged on HIP.
 // These are the HBM-bound siblings of the fused scorer (ahv_score.hip): forward_3d2d* and score_features here, rotate_volume
 // and its adjoint in ahv_rotate.hip.  Also here: the hypothesis generators (random_rotations, so3_grid) and the library's
-// zero fill.  What happens once the scores exist -- the arg-max of that sequence, lists, modes, posterior, ascent -- is
-// ahv_select.hip; tracking a pose over a frame sequence is ahv_track.hip.
+// zero fill.  What happens once the scores exist -- the arg-max of that sequence, lists, modes, ascent -- is ahv_select.hip,
+// with the multi-view kernels in ahv_views.hip and the posterior and its draws in ahv_posterior.hip; tracking a pose over a
+// frame sequence is ahv_track.hip.
 #include "ahv_device.h"
+#include "ahv_launch.h"
 #include "ahv_dual.h"
 #include "ahv_exact.h"
 #include "ahv_so3.h"

@@ -5,6 +5,7 @@
 // un-contracts FMAs of the generic gradient), these were tuned under the default ones.  The trilinear rule all of them
 // share is ahv_trilinear.h.
 #include "ahv_device.h"
+#include "ahv_launch.h"
 #include "ahv_dual.h"
 #include "ahv_exact.h"
 #include "ahv_trilinear.h"

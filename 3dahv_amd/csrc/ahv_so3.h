@@ -1,7 +1,7 @@
 // ahv_so3.h -- the counter-based rotation sampler shared by the hypothesis generators (ahv_ops.hip) and the tracker's predict
 // step (ahv_track.hip): Philox-4x32-10 -> 4 uniforms -> Box-Muller -> normalised Gaussian quaternion -> matrix.  Below it the two
 // compositions more than one source needs bit for bit: R exp([w]x) as unit quaternions (ahv_track.hip, ahv_graph.hip) and Q A^T
-// with the bits of view_rotations_kernel (ahv_select.hip, ahv_graph.hip).
+// with the bits of view_rotations_kernel (ahv_views.hip, ahv_graph.hip).
 #pragma once
 #include "ahv_device.h"
 

@@ -1,5 +1,5 @@
 // ahv_sym.h -- pose selection modulo an object's symmetry group: the symmetric trace and its maximiser, ONE copy of the maths for
-// the fold (sym_fold_kernel) and the symmetric mode selection (topk_modes_sym_kernel) in ahv_select.hip.
+// the fold (sym_fold_kernel) and the symmetric mode selection (topk_modes_sym_kernel) in ahv_select.hip (tile rule: ahv_tile.h).
 //
 // Hypotheses are relative rotations R (source view -> target view); the group, written in the source view's frame, acts on the
 // right: R and R S are the same pose.  A group is G <= kSymMaxG matrices S_g (S_0 the identity, exactly) and, optionally, a unit

@@ -2,8 +2,9 @@
 // predict_rotations, track_advance) and the two smoothers over the particle history, Viterbi (smooth_step, smooth_backtrace)
 // and forward-backward marginals (marginal_step, marginal_smooth).  The smoothers share one pairwise pass over a frame's
 // particles (pairwise_walk) and differ in what they accumulate.  The sets the filter tracks are scored by ahv_score.hip and
-// resampled by ahv_select.hip; the Haar stream of the fresh slots is ahv_so3.h's, shared with the hypothesis generators.
+// resampled by ahv_posterior.hip; the Haar stream of the fresh slots is ahv_so3.h's, shared with the hypothesis generators.
 #include "ahv_device.h"
+#include "ahv_launch.h"
 #include "ahv_so3.h"
 
 namespace ahv {
@@ -851,8 +852,6 @@ hipError_t launch_marginal_step(const float* R_cur, const float* scores, const i
     return hipGetLastError();
 }
 
-// F - 1 backward launches (frames t - 1, t - 2, ...: each reads the beta the launch before wrote) and the finish, in stream
-// order: a linear chain under capture.
 hipError_t launch_marginal_smooth(const float* hist_R, const float* hist_P, const float* hist_alpha, const float* hist_emit,
                                   const int64_t* step, int64_t first_step, int B, int64_t M, int64_t H, int64_t F, float inv4s2,
                                   float jump, float* logw, int64_t* idx, float* R, hipStream_t stream)
