@@ -44,6 +44,9 @@ int cu_count()
     return cached_cu;
 }
 
+// A pointer some kernel reads through a vector type without testing the address: refused here, never launched misaligned.
+bool misaligned(const void* p, unsigned bytes) { return (reinterpret_cast<uintptr_t>(p) & (uintptr_t)(bytes - 1)) != 0; }
+
 }  // namespace
 
 extern "C" {
@@ -82,6 +85,8 @@ static int score_common(const char* who, const float* vol_src, const float* tgt,
         return fail(AHV_EINVAL, "%s: n_offset + N must fit in 32 bits", who);
     if (flags & ~(AHV_SCORE_RESET_BEST | AHV_SCORE_SPLIT_F16 | AHV_SCORE_NO_TEAMS | AHV_SCORE_SPARE_CUS_MASK))
         return fail(AHV_EINVAL, "%s: unknown flags 0x%x", who, flags);
+    if (tgt_is_volume && misaligned(tgt, 8))   // tgt_regs_load<true> reads it as float2
+        return fail(AHV_EINVAL, "%s: vol_tgt must be 8-byte aligned", who);
     const bool split = (flags & AHV_SCORE_SPLIT_F16) != 0;
     hipStream_t s = static_cast<hipStream_t>(stream);
     if (best_key && (flags & AHV_SCORE_RESET_BEST) && B > 0) {
@@ -171,7 +176,8 @@ int ahv_rotate_volume_f32(const float* vol, int64_t vol_batch_stride, const floa
 {
     if (N < 0 || C < 1 || D < 1 || H < 1 || W < 1)
         return fail(AHV_EINVAL, "rotate_volume: bad shape N=%lld C=%d D=%d H=%d W=%d", (long long)N, C, D, H, W);
-    if (vol_batch_stride < 0) return fail(AHV_EINVAL, "rotate_volume: negative batch stride");
+    if (vol_batch_stride != 0 && vol_batch_stride < (int64_t)C * D * H * W)
+        return fail(AHV_EINVAL, "rotate_volume: vol_batch_stride = %lld: the batch stride must be 0 or >= C*D*H*W", (long long)vol_batch_stride);
     if (N == 0) return AHV_OK; /* empty batch: nothing to read or write, pointers may be null */
     if (!vol || !R || !out) return fail(AHV_EINVAL, "rotate_volume: null pointer");
     const int cu = cu_count();
@@ -189,13 +195,15 @@ int ahv_rotate_volume_backward_f32(const float* grad_out, int64_t vol_batch_stri
         return fail(AHV_EINVAL, "rotate_volume_backward: bad shape N=%lld C=%d D=%d H=%d W=%d", (long long)N, C, D, H, W);
     const int64_t vol_elems = (int64_t)C * D * H * W;
     if (vol_batch_stride != 0 && vol_batch_stride < vol_elems)
-        return fail(AHV_EINVAL, "rotate_volume_backward: batch stride must be 0 or >= C*D*H*W");
+        return fail(AHV_EINVAL, "rotate_volume_backward: vol_batch_stride = %lld: the batch stride must be 0 or >= C*D*H*W", (long long)vol_batch_stride);
     if (!grad_vol) return fail(AHV_EINVAL, "rotate_volume_backward: null grad_vol");
     hipStream_t s = static_cast<hipStream_t>(stream);
     const int64_t n_vol = vol_batch_stride == 0 ? 1 : N;
     if (n_vol > 0) {
-        const size_t bytes = sizeof(float) * (size_t)(vol_batch_stride == 0 ? vol_elems : (N - 1) * vol_batch_stride + vol_elems);
-        hipError_t e = zero_span(grad_vol, bytes, s);
+        // packed volumes are one span; strided ones are zeroed volume by volume: the caller's bytes between them stay
+        const bool packed = vol_batch_stride == 0 || vol_batch_stride == vol_elems;
+        hipError_t e = packed ? zero_span(grad_vol, sizeof(float) * (size_t)(n_vol * vol_elems), s)
+                              : ahv::launch_zero_fill_strided(grad_vol, vol_elems, vol_batch_stride, n_vol, s);
         if (e != hipSuccess) return hip_fail("rotate_volume_backward: zero fill", e);
     }
     if (N == 0) return AHV_OK;
@@ -213,7 +221,7 @@ int ahv_rotate_volume_rotation_grad_f32(const float* grad_out, const float* vol,
     if (N < 0 || C < 1 || D < 1 || H < 1 || W < 1)
         return fail(AHV_EINVAL, "rotate_volume_rotation_grad: bad shape N=%lld C=%d D=%d H=%d W=%d", (long long)N, C, D, H, W);
     if (vol_batch_stride != 0 && vol_batch_stride < (int64_t)C * D * H * W)
-        return fail(AHV_EINVAL, "rotate_volume_rotation_grad: batch stride must be 0 or >= C*D*H*W");
+        return fail(AHV_EINVAL, "rotate_volume_rotation_grad: vol_batch_stride = %lld: the batch stride must be 0 or >= C*D*H*W", (long long)vol_batch_stride);
     if (N == 0) return AHV_OK; /* nothing to read or write, pointers may be null */
     if (!grad_out || !vol || !R || !grad_R) return fail(AHV_EINVAL, "rotate_volume_rotation_grad: null pointer");
     const int cu = cu_count();
@@ -230,6 +238,7 @@ int ahv_forward_3d2d_f32(const float* vol, const float* W1, const float* W2, con
     if (M < 0) return fail(AHV_EINVAL, "forward_3d2d: negative M");
     if (M == 0) return AHV_OK;
     if (!vol || !W1 || !W2 || !b2 || !out) return fail(AHV_EINVAL, "forward_3d2d: null pointer");
+    if (misaligned(vol, 8)) return fail(AHV_EINVAL, "forward_3d2d: vol must be 8-byte aligned");   // staged as float2
     const int cu = cu_count();
     if (cu < 0) return fail(AHV_EDEVICE, "no usable HIP device");
     hipError_t e = ahv::launch_forward_3d2d(vol, W1, W2, b2, M, out, cu, static_cast<hipStream_t>(stream));
@@ -242,6 +251,8 @@ int ahv_score_features_f32(const float* f_src, const float* f_tgt, int B, int64_
     if (B < 0 || N < 0) return fail(AHV_EINVAL, "score_features: negative size");
     if (B == 0 || N == 0) return AHV_OK;
     if (!f_src || !f_tgt || !scores) return fail(AHV_EINVAL, "score_features: null pointer");
+    if (misaligned(f_src, 16)) return fail(AHV_EINVAL, "score_features: f_src must be 16-byte aligned");   // read as float4
+    if (misaligned(f_tgt, 16)) return fail(AHV_EINVAL, "score_features: f_tgt must be 16-byte aligned");
     const int cu = cu_count();
     if (cu < 0) return fail(AHV_EDEVICE, "no usable HIP device");
     hipError_t e = ahv::launch_score_features(f_src, f_tgt, B, N, scores, cu, static_cast<hipStream_t>(stream));
@@ -256,7 +267,7 @@ int ahv_compose_rotations_f32(const int64_t* best_key, const float* R, int64_t r
     if (B == 0 || N2 == 0) return AHV_OK;
     if (!best_key || !R || !D || !out) return fail(AHV_EINVAL, "compose_rotations: null pointer");
     if (N == 0) return fail(AHV_EINVAL, "compose_rotations: empty rotation set");
-    if (r_batch_stride != 0 && r_batch_stride < N * 9) return fail(AHV_EINVAL, "compose_rotations: bad r_batch_stride");
+    if (r_batch_stride != 0 && r_batch_stride < N * 9) return fail(AHV_EINVAL, "compose_rotations: r_batch_stride %lld must be 0 or >= N*9", (long long)r_batch_stride);
     hipError_t e = ahv::launch_compose_rotations_topk(best_key, 1, R, r_batch_stride, n_offset, N, D, N2, B, out,
                                                       static_cast<hipStream_t>(stream));  // one seed: the list at K = 1
     if (e != hipSuccess) return hip_fail("compose_rotations: launch", e);
@@ -278,6 +289,7 @@ int ahv_coarse_to_fine_f32(const float* vol_src, const float* vol_tgt, const flo
         return fail(AHV_EINVAL, "coarse_to_fine: r_batch_stride %lld must be 0 or >= N*9", (long long)r_batch_stride);
     if (N > 4294967296ll || N2 > 4294967296ll) return fail(AHV_EINVAL, "coarse_to_fine: indices must fit in 32 bits");
     if (flags & ~(AHV_SCORE_NO_TEAMS | AHV_SCORE_SPARE_CUS_MASK)) return fail(AHV_EINVAL, "coarse_to_fine: unknown flags 0x%x", flags);
+    if (misaligned(vol_tgt, 8)) return fail(AHV_EINVAL, "coarse_to_fine: vol_tgt must be 8-byte aligned");
     const int cu = cu_count();
     if (cu < 0) return fail(AHV_EDEVICE, "no usable HIP device");
     ahv::CoarseToFineLaunch a;
@@ -312,7 +324,7 @@ int ahv_select_rotation_f32(int64_t* best_key, const float* R, int64_t r_batch_s
     if (B == 0) return AHV_OK;
     if (!best_key) return fail(AHV_EINVAL, "select_rotation: null best_key");
     if (R_out && (!R || N == 0)) return fail(AHV_EINVAL, "select_rotation: R_out needs a rotation set");
-    if (r_batch_stride != 0 && r_batch_stride < N * 9) return fail(AHV_EINVAL, "select_rotation: bad r_batch_stride");
+    if (r_batch_stride != 0 && r_batch_stride < N * 9) return fail(AHV_EINVAL, "select_rotation: r_batch_stride %lld must be 0 or >= N*9", (long long)r_batch_stride);
     hipError_t e = ahv::launch_select_topk(best_key, 1, R, r_batch_stride, n_offset, N, B, R_out, best_score, best_idx,
                                            (flags & AHV_SELECT_RESET_KEY) != 0, static_cast<hipStream_t>(stream));  // B lists of one
     if (e != hipSuccess) return hip_fail("select_rotation: launch", e);
@@ -574,7 +586,7 @@ int ahv_select_topk_f32(int64_t* keys, int K, const float* R, int64_t r_batch_st
     if (B == 0) return AHV_OK;
     if (!keys) return fail(AHV_EINVAL, "select_topk: null keys");
     if (R_out && (!R || N == 0)) return fail(AHV_EINVAL, "select_topk: R_out needs a rotation set");
-    if (r_batch_stride != 0 && r_batch_stride < N * 9) return fail(AHV_EINVAL, "select_topk: bad r_batch_stride");
+    if (r_batch_stride != 0 && r_batch_stride < N * 9) return fail(AHV_EINVAL, "select_topk: r_batch_stride %lld must be 0 or >= N*9", (long long)r_batch_stride);
     hipError_t e = ahv::launch_select_topk(keys, K, R, r_batch_stride, n_offset, N, B, R_out, scores_out, idx_out,
                                            (flags & AHV_SELECT_RESET_KEY) != 0, static_cast<hipStream_t>(stream));
     if (e != hipSuccess) return hip_fail("select_topk: launch", e);
@@ -589,7 +601,7 @@ int ahv_compose_rotations_topk_f32(const int64_t* keys, int K, const float* R, i
     if (B == 0 || N2 == 0) return AHV_OK;
     if (!keys || !R || !D || !out) return fail(AHV_EINVAL, "compose_rotations_topk: null pointer");
     if (N == 0) return fail(AHV_EINVAL, "compose_rotations_topk: empty rotation set");
-    if (r_batch_stride != 0 && r_batch_stride < N * 9) return fail(AHV_EINVAL, "compose_rotations_topk: bad r_batch_stride");
+    if (r_batch_stride != 0 && r_batch_stride < N * 9) return fail(AHV_EINVAL, "compose_rotations_topk: r_batch_stride %lld must be 0 or >= N*9", (long long)r_batch_stride);
     hipError_t e = ahv::launch_compose_rotations_topk(keys, K, R, r_batch_stride, n_offset, N, D, N2, B, out,
                                                       static_cast<hipStream_t>(stream));
     if (e != hipSuccess) return hip_fail("compose_rotations_topk: launch", e);

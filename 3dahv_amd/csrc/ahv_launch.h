@@ -65,6 +65,8 @@ hipError_t launch_score_features(const float* f_src, const float* f_tgt, int B, 
 hipError_t launch_random_rotations(uint64_t seed, uint64_t offset, int64_t N, float* out, hipStream_t stream);
 hipError_t launch_so3_grid(int64_t n_total, int64_t offset, int64_t N, float* out, hipStream_t stream);
 hipError_t launch_zero_fill(void* const* ptrs, const size_t* bytes, int count, hipStream_t stream);
+// rows of `elems` floats, `stride` floats apart (stride >= elems): only the rows are written
+hipError_t launch_zero_fill_strided(float* p, int64_t elems, int64_t stride, int64_t rows, hipStream_t stream);
 
 // ---- ahv_rotate.hip ----
 hipError_t launch_rotate_volume(const float* vol, int64_t vol_batch_stride, const float* R, int64_t N, int C, int D, int H, int W,

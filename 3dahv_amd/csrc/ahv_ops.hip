@@ -200,11 +200,15 @@ __global__ __launch_bounds__(512) void forward_3d2d_small_kernel(
     const int q = wave & 3, kh = wave >> 2;
     const int n = lane & 15, kq = lane >> 4, i0 = n >> 3, j = n & 7, row = lane & 15;
     const float* V = vol + (long)blockIdx.x * (16 * 512);
-    for (int i = tid; i < 32 * 96; i += 512) {  // 96 float4 per W1 row
-        const int r = i / 96, k4 = i - r * 96;
-        const f32x4 w = *reinterpret_cast<const f32x4*>(W1 + r * 384 + 4 * k4);
-        float* d = w1s + r * kW1PadStride + 4 * k4;
-        d[0] = w[0]; d[1] = w[1]; d[2] = w[2]; d[3] = w[3];
+    if ((reinterpret_cast<unsigned long long>(W1) & 15ull) == 0) {
+        for (int i = tid; i < 32 * 96; i += 512) {  // 96 float4 per W1 row
+            const int r = i / 96, k4 = i - r * 96;
+            const f32x4 w = *reinterpret_cast<const f32x4*>(W1 + r * 384 + 4 * k4);
+            float* d = w1s + r * kW1PadStride + 4 * k4;
+            d[0] = w[0]; d[1] = w[1]; d[2] = w[2]; d[3] = w[3];
+        }
+    } else {  // a view that starts off a 16-byte boundary (stage_w1_table's rule): same map, one float at a time
+        for (int i = tid; i < 32 * 384; i += 512) w1s[(i / 384) * kW1PadStride + i % 384] = W1[i];
     }
     {   // quarter q of channel c = 128 contiguous floats at c*512 + q*128; the two waves of a quarter take 8 channels each
         float* buf = qbuf[q];
@@ -453,6 +457,25 @@ hipError_t launch_zero_fill(void* const* ptrs, const size_t* bytes, int count, h
     if (blocks < 1) blocks = 1;
     if (blocks > 2048) blocks = 2048;
     hipLaunchKernelGGL(zero_fill_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, a);
+    return hipGetLastError();
+}
+
+// Rows with the caller's bytes between them (ahv_rotate_volume_backward_f32 with a padded batch stride): one float per
+// thread, row by row over gridDim.y, nothing between the rows is touched.
+__global__ __launch_bounds__(256) void zero_fill_strided_kernel(float* __restrict__ p, long elems, long stride, long rows)
+{
+    const long i0 = (long)blockIdx.x * 256 + threadIdx.x, step = (long)gridDim.x * 256;
+    for (long r = blockIdx.y; r < rows; r += gridDim.y)
+        for (long i = i0; i < elems; i += step) p[r * stride + i] = 0.0f;
+}
+
+hipError_t launch_zero_fill_strided(float* p, int64_t elems, int64_t stride, int64_t rows, hipStream_t stream)
+{
+    if (elems <= 0 || rows <= 0) return hipSuccess;
+    if (stride < elems) return hipErrorInvalidValue;
+    const int64_t bx = (elems + 255) / 256;
+    hipLaunchKernelGGL(zero_fill_strided_kernel, dim3((unsigned)(bx < 64 ? bx : 64), (unsigned)(rows < 1024 ? rows : 1024)),
+                       dim3(256), 0, stream, p, (long)elems, (long)stride, (long)rows);
     return hipGetLastError();
 }
 

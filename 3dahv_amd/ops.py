@@ -88,6 +88,13 @@ def _refuse_grad(name: str, *tensors: torch.Tensor) -> None:
                            "score_hypotheses_autograd / rotate_volume / forward_3d2d, which are differentiable" % name)
 
 
+def _aligned(t: torch.Tensor, nbytes: int) -> torch.Tensor:
+    """``t`` (contiguous), or a fresh copy of it when it starts off the ``nbytes`` grid: a contiguous view into the middle of
+    a storage may, and the entry points refuse a misaligned pointer their kernels read through a vector type
+    (include/ahv.h states which)."""
+    return t if t.data_ptr() % nbytes == 0 else t.clone()
+
+
 def _head(W1: torch.Tensor, W2: torch.Tensor, b2: torch.Tensor):
     if W1.numel() != 32 * 384 or W2.numel() != 32 * 32 or b2.numel() != 32:
         raise RuntimeError("head weights must be (32,384[,1,1]), (32,32[,1,1]), (32,)")
@@ -205,7 +212,7 @@ def _forward_3d2d_nograd(img_feat: torch.Tensor, W1: torch.Tensor, W2: torch.Ten
         raise RuntimeError("img_feat must be (M,16,8,8,8), got %s" % (tuple(img_feat.shape),))
     _need_gpu(img_feat, W1, W2, b2)
     W1, W2, b2 = _head(W1, W2, b2)
-    x = img_feat.detach().contiguous()
+    x = _aligned(img_feat.detach().contiguous(), 8)
     M = x.shape[0]
     out = torch.empty((M, 32, 64), dtype=torch.float32, device=x.device)
     _call(out.device, "ahv_forward_3d2d_f32", x.data_ptr(), W1.data_ptr(), W2.data_ptr(), b2.data_ptr(), M,
@@ -220,7 +227,7 @@ def score_features(f_src: torch.Tensor, f_tgt: torch.Tensor) -> torch.Tensor:
         raise RuntimeError("expected f_src (B,N,32,64) and f_tgt (B,32,64)")
     _need_gpu(f_src, f_tgt)
     B, N = f_src.shape[:2]
-    a, t = f_src.detach().contiguous(), f_tgt.detach().contiguous()
+    a, t = _aligned(f_src.detach().contiguous(), 16), _aligned(f_tgt.detach().contiguous(), 16)
     out = torch.empty((B, N), dtype=torch.float32, device=a.device)
     _call(out.device, "ahv_score_features_f32", a.data_ptr(), t.data_ptr(), B, N, out.data_ptr())
     return out
@@ -339,6 +346,8 @@ def _score_hypotheses_nograd(vol_src, feat_tgt, R, W1, W2, b2, n_offset, want_sc
     dev = _need_gpu(vol_src, feat_tgt, R, W1, W2, b2)
     W1, W2, b2 = _head(W1, W2, b2)
     vs, ft, Rc = vol_src.detach().contiguous(), feat_tgt.detach().contiguous(), R.detach().contiguous()
+    if tgt_is_volume:
+        ft = _aligned(ft, 8)
     scores = None
     if want_scores and scores_out is not None:
         if (scores_out.dtype != torch.float32 or tuple(scores_out.shape) != (B, N) or not scores_out.is_contiguous()
@@ -2693,6 +2702,7 @@ def _coarse_to_fine_nograd(vol_src, vol_tgt, R, D, W1, W2, b2, state, want_score
     elif state.B != B or state.keys.device != dev:
         raise RuntimeError("the CoarseToFineState was made for B = %d on %s" % (state.B, state.keys.device))
     vs, vt, Rc, Dc = (t.detach().contiguous() for t in (vol_src, vol_tgt, R, D))
+    vt = _aligned(vt, 8)
     o = out if out is not None else {}
     def buf(name, shape, dtype=torch.float32, wanted=True):
         if not wanted:
