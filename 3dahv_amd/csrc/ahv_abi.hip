@@ -386,12 +386,7 @@ int ahv_forward_2d3d_f32(const ahv_aligner_weights* w, const float* layer4_src, 
 size_t ahv_score_hypotheses_backward_workspace_bytes(int B, int64_t N)
 {
     if (B <= 0 || N <= 0) return 0;
-    // dL/du per hypothesis + one reserved word per sample (rounded up to 16 bytes; unused since the dV kernel stopped
-    // needing max |du|, kept so the size stays ABI 2.3's) + one partial dW1 (32 x 384) per workgroup of the persistent
-    // grid (at most one per CU; 1024 covers any device if the query fails)
-    const int cu = cu_count();
-    const size_t wgs = cu > 0 ? (size_t)cu : 1024;
-    return sizeof(float) * (2048 * (size_t)B * (size_t)N + (((size_t)B + 3) & ~(size_t)3) + wgs * 32 * 384);
+    return sizeof(float) * ahv::BackwardWs(B, N, cu_count()).floats();   // the layout: ahv_launch.h
 }
 
 static int score_backward_common(const float* vol_src, const float* feat_tgt, const float* R,
@@ -467,10 +462,9 @@ static int score_backward_common(const float* vol_src, const float* feat_tgt, co
     }
     const int cu = cu_count();
     if (cu <= 0) return fail(AHV_EDEVICE, "score_backward: no usable HIP device");
-    // workspace: du (2048 floats per hypothesis), one reserved word per sample (rounded up to 16 bytes), dW1 partials
     hipError_t e = ahv::launch_score_backward(vol_src, feat_tgt, R, r_batch_stride, W1, W2, b2, B, N, grad_scores,
                                               static_cast<float*>(workspace),
-                                              static_cast<float*>(workspace) + 2048 * (size_t)B * (size_t)N + (((size_t)B + 3) & ~(size_t)3),
+                                              static_cast<float*>(workspace) + ahv::BackwardWs(B, N, cu).partials_offset(),
                                               grad_vol_src, grad_feat_tgt, grad_W1, grad_W2, grad_b2, cu,
                                               static_cast<hipStream_t>(stream), saved_u);
     if (e != hipSuccess) return hip_fail("score_backward: launch", e);

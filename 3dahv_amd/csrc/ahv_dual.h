@@ -359,7 +359,7 @@ __device__ __forceinline__ void hat_axis(float i, float& jf, float& w0, float& w
 // wave of another kernel sharing their SIMD.  Rounds 3-4 ruled that out for the scorers by occupancy -- two waves of 249-256
 // registers take all 512 of a SIMD (tests/test_isa_hazard.py still checks the allocation) -- but the waves of a workgroup
 // retire one by one, and beside the LAST wave of a SIMD a foreign wave fits.  Since round 5 every kernel that uses this
-// gather defines AHV_FP32_LOW_HALF (ahv_score.hip, ahv_backward.hip; ahv_ops.hip issues no MFMAs and does not): measured
+// gather defines AHV_FP32_LOW_HALF (ahv_score.hip; ahv_bwd.h for the three files of the backward; ahv_ops.hip issues no MFMAs and does not): measured
 // cost 0.2-0.7 % (0.6809 -> 0.6828 ms per 50 000 hypotheses, 2.576 -> 2.588 ms per backward; profiles/r04d_low_half_ab.txt).
 // The A/B builds with and without it, and the unprotected split-f16 build that shows the hazard itself, are described in
 // HISTORY.md; their code was last in commit 86a1f1c.

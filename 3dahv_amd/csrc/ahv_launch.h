@@ -187,11 +187,52 @@ hipError_t launch_pose_graph_propose(const float* A, const float* pair_R, const 
 hipError_t launch_pose_graph_commit(const int64_t* key, const float* Q, int B, int V, int k, int64_t N, float* A, float* node_score,
                                     hipStream_t stream);
 
+// ---- the scorer's backward: its grid rule and its workspace, plain host code (the launchers below, ahv_abi.hip and
+// tools/kbench_bwd.cpp all take them from here) ----
+// Persistent grid: y strides the batch, x the hypotheses -- one workgroup per CU, but no more along x than a list of N
+// has turns of `per_workgroup` hypotheses (a short list is spread over more workgroups), and at least one.  B, N >= 1.
+constexpr int kBwdHeadPerWg = 4, kBwdHeadSavedPerWg = 8, kBwdW1PerWg = 4, kBwdVolumePerWg = 2;
+constexpr int kBwdHeadDuPerWg = 1;   // the head pass of the rotation gradient: a short list goes one hypothesis per workgroup
+inline dim3 backward_grid(int num_cu, int B, int64_t N, int per_workgroup)
+{
+    const int gy = B < num_cu ? B : num_cu;
+    int gx = num_cu / gy;
+    const int64_t need = (N + per_workgroup - 1) / per_workgroup;
+    if (gx > need) gx = (int)need;
+    if (gx < 1) gx = 1;
+    return dim3(gx, gy);
+}
+
+// The workspace of a backward, in floats: du (2 048 per hypothesis; u on entry of the saved-u backward), one reserved word
+// per sample (rounded up to 16 bytes; unused since the dV kernel stopped needing max |du|, kept so the size stays ABI 2.3's),
+// then one partial dW1 (32 x 384) per workgroup of kernel 2a.  Kernel 2a runs on backward_grid(num_cu, B, N, kBwdW1PerWg),
+// where gx * gy <= (num_cu / gy) * gy <= num_cu: one partial per CU always suffices.  num_cu <= 0 (the device query
+// failed: the size is then reported without a device) counts as 1 024, which covers any device.
+struct BackwardWs {
+    size_t du_floats, pad_floats, partials;
+    BackwardWs(int B, int64_t N, int num_cu)
+        : du_floats(2048 * (size_t)B * (size_t)N), pad_floats(((size_t)B + 3) & ~(size_t)3),
+          partials(num_cu > 0 ? (size_t)num_cu : 1024) {}
+    size_t partials_offset() const { return du_floats + pad_floats; }
+    size_t floats() const { return partials_offset() + partials * 32 * 384; }
+};
+
 // ---- ahv_backward.hip ----
 hipError_t launch_score_backward(const float* vol_src, const float* feat_tgt, const float* R, int64_t r_batch_stride,
                                  const float* W1, const float* W2, const float* b2, int B, int64_t N, const float* grad_scores,
                                  float* du_ws, float* dw1_partials, float* grad_vol, float* grad_feat_tgt, float* grad_W1,
                                  float* grad_W2, float* grad_b2, int num_cu, hipStream_t stream, bool saved_u);
+// the head pass that leaves du of every hypothesis in du_ws and nothing else (score_backward_head_kernel<false>: no sums
+// across hypotheses, no atomics); grad_scores may be null (= all ones)
+hipError_t launch_score_backward_head_du(const float* vol_src, const float* feat_tgt, const float* R, int64_t r_batch_stride,
+                                         const float* W1, const float* W2, const float* b2, int B, int64_t N,
+                                         const float* grad_scores, float* du_ws, int num_cu, hipStream_t stream);
+
+// ---- ahv_bwd_volume.hip ----
+hipError_t launch_score_backward_volume(const float* R, int64_t r_batch_stride, const float* W1, int B, int64_t N,
+                                        const float* du_ws, float* grad_vol, int num_cu, hipStream_t stream);
+
+// ---- ahv_rotgrad.hip ----
 hipError_t launch_score_rotation_grad(const float* vol_src, const float* feat_tgt, const float* R, int64_t r_batch_stride,
                                       const float* W1, const float* W2, const float* b2, int B, int64_t N,
                                       const float* grad_scores, float* du_ws, float* grad_R, int num_cu, hipStream_t stream);

@@ -1,6 +1,6 @@
 // ahv_rotate.hip -- the op-level rotate_volume: the tensor utils.rotate_volume returns (utils.py:113-131) and its adjoint
 // w.r.t. the volume.  Three kernels: the (16,8,8,8) shared-volume forward, the generic forward, the volume adjoint.  The
-// gradient w.r.t. the rotations (rotate_volume_rotation_grad_*_kernel) is in ahv_backward.hip, next to
+// gradient w.r.t. the rotations (rotate_volume_rotation_grad_*_kernel) is in ahv_rotgrad.hip, next to
 // score_rotation_grad_kernel whose gather it reuses: those kernels need that file's build flags (no SLP vectoriser: it
 // un-contracts FMAs of the generic gradient), these were tuned under the default ones.  The trilinear rule all of them
 // share is ahv_trilinear.h.
@@ -161,7 +161,7 @@ __global__ __launch_bounds__(256) void rotate_volume_generic_kernel(
 // corners outside the volume).  grad_vol is zeroed by the caller; sums use float atomics, so the
 // result is reproducible to rounding, not bitwise.  With vol_batch_stride = 0 (the stride-0 expand
 // the reference passes) all N hypotheses accumulate into ONE volume.  Compatibility path for
-// unmodified reference scripts; the training path proper is the fused backward (ahv_backward.hip).
+// unmodified reference scripts; the training path proper is the fused backward (ahv_backward.hip, ahv_bwd_volume.hip).
 // ---------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void rotate_volume_backward_kernel(
     const float* __restrict__ grad_out, long vol_batch_stride, const float* __restrict__ R, long N, int C, int D,

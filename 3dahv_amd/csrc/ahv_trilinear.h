@@ -1,5 +1,5 @@
 // ahv_trilinear.h -- the trilinear rule of the op-level rotate_volume family (ahv_rotate.hip) and of score_rotation_grad_kernel
-// (ahv_backward.hip), stated once.
+// and the rotation gradient of rotate_volume (both ahv_rotgrad.hip), stated once.
 //
 // Semantics = F.affine_grid + F.grid_sample(bilinear, zeros, align_corners=False) as called by utils.rotate_volume
 // (utils.py:123-129).  Voxel (d, h, w) of a (D, H, W) volume:

@@ -1,4 +1,4 @@
-"""Matrix families for the dV scatter of the backward (3dahv_amd/csrc/ahv_backward.hip, score_backward_volume_rmw_kernel).
+"""Matrix families for the dV scatter of the backward (3dahv_amd/csrc/ahv_bwd_volume.hip, score_backward_volume_rmw_kernel).
 
 The kernel classifies every hypothesis with rmw_rotation_like -- max |R^T R - I| <= 0.04 entrywise -- and scatters the
 8 voxels of a step in ONE instruction when the matrix passes, one voxel per instruction otherwise.  ``inside`` holds

@@ -1,4 +1,4 @@
-"""CPU model of the dV scatter's lane map (3dahv_amd/csrc/ahv_backward.hip, kernel 2b): the plain read-modify-write of
+"""CPU model of the dV scatter's lane map (3dahv_amd/csrc/ahv_bwd_volume.hip, kernel 2b): the plain read-modify-write of
 score_backward_volume_rmw_kernel is a data race unless the 8 voxels of one scatter instruction have disjoint LIVE
 footprints for every matrix rmw_rotation_like accepts.  The acceptance threshold is read out of the source, so loosening
 it fails here, on the CPU, without touching this file.
@@ -27,7 +27,7 @@ LIVE_EPS = 1e-5
 
 
 def _source():
-    return open(os.path.join(REPO, "3dahv_amd", "csrc", "ahv_backward.hip")).read()
+    return open(os.path.join(REPO, "3dahv_amd", "csrc", "ahv_bwd_volume.hip")).read()
 
 
 def parsed_threshold():
