@@ -51,8 +51,9 @@ def ops(ahv):
     return ahv.ops
 
 
-def ref_rotation_grad(vs, ft, R, W1, W2, b2, gs=None, dtype=torch.float64, chunk=128):
-    """(grad_R (B,N,3,3), ambiguous (B,N) bool) by torch autograd on the CPU in ``dtype``."""
+def ref_rotation_grad(vs, ft, R, W1, W2, b2, gs=None, dtype=torch.float64, chunk=128, scale=1.0):
+    """(grad_R (B,N,3,3), ambiguous (B,N) bool) by torch autograd on the CPU in ``dtype``.  ``scale``: the magnitude of the case's
+    pre-activations relative to the ~1 that KINK_TAU is stated for (tests/backward_cases.py)."""
     from oracle import torch_ref
     import torch.nn.functional as F
     vs, ft, R, W1, W2, b2 = (t.detach().cpu().to(dtype) for t in (vs, ft, R, W1, W2, b2))
@@ -79,7 +80,7 @@ def ref_rotation_grad(vs, ft, R, W1, W2, b2, gs=None, dtype=torch.float64, chunk
             grad[b, n0:n0 + n] = g
             i = torch.einsum("nab,pb->npa", Rb.detach(), P) + 3.5
             frac = (i - i.round()).abs()
-            amb[b, n0:n0 + n] = ((u.detach().abs() < KINK_TAU) & (u.detach() != 0)).flatten(1).any(dim=1) | ((frac > 0) & (frac < KINK_TAU)).flatten(1).any(dim=1)
+            amb[b, n0:n0 + n] = ((u.detach().abs() < KINK_TAU * scale) & (u.detach() != 0)).flatten(1).any(dim=1) | ((frac > 0) & (frac < KINK_TAU)).flatten(1).any(dim=1)
     return grad, amb
 
 
