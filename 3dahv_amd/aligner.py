@@ -7,7 +7,7 @@ with ``load_state_dict``.
 * ``forward_3d2d`` (per hypothesis, hot) runs the HIP kernel through the C ABI.
 * ``forward_2d3d`` (once per pair: conv embedding, sin/cos position code, the
   bidirectional 3D-aware transformer of transformer/attention.py:196-396, 3-D res-block) runs as ONE
-  C-ABI call (``ahv_forward_2d3d_f32``, csrc/ahv_encoder.hip) for inference calls on the GPU at the
+  C-ABI call (``ahv_forward_2d3d_f32``, csrc/ahv_encoder.hip and its ahv_enc_*.h) for inference calls on the GPU at the
   reference's configuration (768 -> 256, 4 heads); training-style calls (autograd recording) and other widths
   (the ``encoder_small`` fixture) use stock torch operators.  Pinned to the reference by the ``encoder_small``
   (shrunken) and ``encoder_full`` (768/256/4x64/depth 4) golden fixtures.
@@ -362,7 +362,7 @@ class BidirectionTransformer(nn.Module):
         self.use_hip = True  # token stage on the HIP kernels when the tensors are on the GPU
         self.register_load_state_dict_post_hook(lambda module, incompatible: module.invalidate_packed())
 
-    # ---- HIP token stage (csrc/ahv_encoder.hip) -------------------------------------------------
+    # ---- HIP token stage (csrc/ahv_encoder.hip, kernels in ahv_enc_*.h) -------------------------------------------------
     def invalidate_packed(self):
         """Drop the packed weight table (call after changing parameters in place)."""
         _PACKED.pop(self, None)
@@ -498,7 +498,7 @@ class Feature_Aligner(nn.Module):
         ay, ax = ys[None] * omega[:, None, None], xs[None] * omega[:, None, None]
         return torch.cat((ax.sin(), ax.cos(), ay.sin(), ay.cos()), dim=0).type(dtype)
 
-    # ---- whole forward_2d3d on the HIP kernels (csrc/ahv_encoder.hip) -----------------------------
+    # ---- whole forward_2d3d on the HIP kernels (csrc/ahv_encoder.hip, ahv_enc_*.h) -----------------------------
     def _hip_2d3d_eligible(self, x):
         return (self.use_hip_encoder and x.is_cuda and x.dtype == torch.float32 and self.in_channel == 768
                 and self.mid_channel == 256 and tuple(x.shape[1:]) == (768, 8, 8) and self.att.n_heads == 4

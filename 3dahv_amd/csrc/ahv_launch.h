@@ -240,7 +240,8 @@ hipError_t launch_rotate_volume_rotation_grad(const float* grad_out, const float
                                               int64_t N, int C, int D, int H, int W, float* grad_R, int num_cu,
                                               hipStream_t stream);
 
-// ---- ahv_encoder.hip (int: 0, or the hipError_t of the launch that *what then names) ----
+// ---- ahv_encoder.hip: host side; kernels in ahv_enc_linear.h / ahv_enc_rows.h, shape decisions in ahv_enc_plan.h
+// (int: 0, or the hipError_t of the launch that *what then names) ----
 size_t transformer_workspace_floats(int B);
 int transformer_blocks(const ahv_block_weights* blocks, int depth, float* x_src, float* x_tgt, int B, float* ws, hipStream_t s,
                        const char** what);

@@ -1,5 +1,5 @@
 """fp64 truth, stock fp32 operators and the per-sample acceptance rule for the encoder's HIP kernels
-(csrc/ahv_encoder.hip), shared by tests/test_gpu_encoder_batch.py.
+(csrc/ahv_encoder.hip and its ahv_enc_*.h), shared by tests/test_gpu_encoder_batch.py.
 
 The modules of 3dahv_amd/aligner.py route anything but fp32 inference on the GPU to stock torch operators, so the same
 module in fp64 is the truth and the same module with its HIP switches off is the yardstick: a HIP result may be as far

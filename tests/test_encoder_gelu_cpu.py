@@ -1,4 +1,4 @@
-"""The GELU of the encoder's GEGLU epilogues (csrc/ahv_encoder.hip::gelu_pk) pinned on the CPU: the coefficients are
+"""The GELU of the encoder's GEGLU epilogues (csrc/ahv_enc_linear.h::gelu_pk) pinned on the CPU: the coefficients are
 read out of the kernel source, the same Horner chain is evaluated with fp32 rounding after every fused multiply-add
 (as tools/fit_gelu.py::gelu_pk does -- that module imports scipy at its top, so the chain is repeated here) and the result
 is held to torch's GELU in fp64.  A mistyped coefficient moves GELU by ~1e-4, which no network-level bound can see.
@@ -14,7 +14,7 @@ import torch
 
 from .conftest import REPO
 
-SOURCE = os.path.join(REPO, "3dahv_amd", "csrc", "ahv_encoder.hip")
+SOURCE = os.path.join(REPO, "3dahv_amd", "csrc", "ahv_enc_linear.h")
 f32 = np.float32
 _NUM = r"([-+]?[0-9]+\.[0-9]+(?:e[-+]?[0-9]+)?)f"
 
@@ -24,7 +24,7 @@ def read_coefficients():
     Every statement of the function is matched: a change of its shape fails here, not in the numbers below."""
     text = open(SOURCE).read()
     m = re.search(r"__device__ __forceinline__ f32x2 gelu_pk\(f32x2 g\)\n\{\n(.*?)\n\}\n", text, re.S)
-    assert m, "gelu_pk(f32x2 g) not found in ahv_encoder.hip: this test reads its coefficients from the source"
+    assert m, "gelu_pk(f32x2 g) not found in ahv_enc_linear.h: this test reads its coefficients from the source"
     lines = [ln.strip() for ln in m.group(1).split("\n") if ln.strip()]
     assert len(lines) == 12, "gelu_pk has changed shape (%d statements, 12 expected):\n%s" % (len(lines), m.group(1))
     assert lines[0] == "const f32x2 t = __builtin_elementwise_abs(g);", lines[0]

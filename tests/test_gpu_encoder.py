@@ -1,4 +1,4 @@
-"""HIP token stage of the 3D-aware encoder (csrc/ahv_encoder.hip) against the stock-torch operator path of
+"""HIP token stage of the 3D-aware encoder (csrc/ahv_encoder.hip, kernels in ahv_enc_*.h) against the stock-torch operator path of
 the host mirror -- itself pinned to the reference by the encoder_small fixture (tests/test_aligner_cpu.py)."""
 import pytest
 import torch

@@ -1,4 +1,4 @@
-"""The encoder's HIP kernels (csrc/ahv_encoder.hip) on batches of DISTINCT samples at every edge of the host dispatch
+"""The encoder's HIP kernels (csrc/ahv_encoder.hip, ahv_enc_*.h) on batches of DISTINCT samples at every edge of the host dispatch
 (forward_2d3d / run_block_pair), against the fp64 copy of the same module under the per-sample rule of
 tests/encoder_reference.py: each sample at most 3 x as far from fp64 as the worst sample of the stock fp32 operators, in
 max and in rms, no additive floor.  Beside it: zero padding carrying the whole signal, sample isolation and batch order
@@ -33,7 +33,7 @@ from . import encoder_reference as ref
 
 pytestmark = pytest.mark.gpu
 
-# what each B selects, read from forward_2d3d / run_block_pair (M = 64 B rows per stream)
+# what each B selects, read from plan_encoder (csrc/ahv_enc_plan.h; M = 64 B rows per stream)
 EDGES = {
     3: "skinny conv, gridDim.z 3",
     8: "skinny conv, gridDim.z 8",

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Coefficients of `ahv_encoder.hip::gelu_pk` and their error, regenerated.
+"""Coefficients of `ahv_enc_linear.h::gelu_pk` and their error, regenerated.
 
 GELU(g) = g Phi(g) = max(g, 0) - |g| Phi(-|g|), and log2 Phi(-t) is smooth on t >= 0 (-1 at 0, ~ -t^2 / (2 ln 2) far
 out), so  Phi(-t) = exp2(p(t)),  p(t) = -1 + c1 t + ... + c8 t^8:  eight fused multiply-adds, one v_exp_f32, no branch and

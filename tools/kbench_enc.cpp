@@ -1,4 +1,4 @@
-// kbench_enc.cpp -- developer micro-benchmark of forward_2d3d (ahv_encoder.hip) with no Python and no profiler:
+// kbench_enc.cpp -- developer micro-benchmark of forward_2d3d (ahv_encoder.hip and the ahv_enc_*.h it includes) with no Python and no profiler:
 // random weights, the forward captured in a hipGraph and replayed, and -- with the launch budget of AHV_ENC_PROBE --
 // the marginal cost of every launch (time of the first k launches minus time of the first k - 1).
 // Build: hipcc --offload-arch=gfx950 -O3 -std=c++17 -DAHV_ENC_PROBE -I3dahv_amd/csrc -Iinclude tools/kbench_enc.cpp -o tools/kbench_enc.bin

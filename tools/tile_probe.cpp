@@ -1,4 +1,4 @@
-// tile_probe: linear_tile_kernel (ahv_encoder.hip) alone at chosen (M, K, N / H), events around 20 launches.
+// tile_probe: linear_tile_kernel (ahv_enc_linear.h, through ahv_encoder.hip) alone at chosen (M, K, N / H), events around 20 launches.
 // Build: hipcc --offload-arch=gfx950 -O3 -std=c++17 -I3dahv_amd/csrc -Iinclude tools/tile_probe.cpp -o tools/tile_probe
 #include "../3dahv_amd/csrc/ahv_encoder.hip"
 #include <cstdio>
@@ -27,7 +27,7 @@ static void run(const char* name, int M, int K, int N, int KS, int H, int tile =
     std::vector<float> ts;
     for (int it = 0; it < 25; ++it) {
         CK(hipEventRecord(e0));
-        CK(ahv::launch_linear_tile(sp, 2, K, K, M, K, KS, H, 0, tile));
+        CK(ahv::launch_linear(tile == 64 ? ahv::LinForm::Tile64 : ahv::LinForm::Tile128, sp, 2, K, K, M, K, KS, H, 0));
         CK(hipEventRecord(e1)); CK(hipEventSynchronize(e1));
         float ms; CK(hipEventElapsedTime(&ms, e0, e1));
         if (it >= 5) ts.push_back(ms * 1e3f);
